@@ -13,6 +13,12 @@ Workload: CHM13v2.0 itself is not in this image, so the genome is a seeded synth
 lengths (tools/sim.py CHM13_LIKE, ~3.117 Gbp, 25 contigs) with planted repeats; reads follow the reference's pbsim
 recipe shape (example/simulate_pbsim.sh:7-14: mean 24 kb, 1 % error).  --genome-scale shrinks the contigs for quick runs
 (the JSON names the scale; only scale 1.0 is the BASELINE configuration).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs if given, the JSON line.  --full adds
+everything else the line can carry (accuracy counts, the roofline and its instrumented launch, smaller batches, the CPU baseline, the
+other configurations' kernel-only legs, end to end); the --no-* switches still drop single parts of it.
+
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # DIR/<column>.npy: the last timed step's hits, float64
 """
 import argparse
 import json
@@ -24,6 +30,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+# --dump-outputs: reads written per run (all ranks together); 11 float64 columns of 524,288 reads = 46 MB
+DUMP_READS = 524288
+DUMP_SEED = 20131
+DUMP_COLUMNS = ("status", "ref_id", "rc", "mapq", "q_start", "q_end", "r_start", "r_end", "score", "n_kminmers")
 
 
 def parse():
@@ -77,6 +87,12 @@ def parse():
     ap.add_argument("--no-configs", action="store_true", help="skip the kernel-only legs of the other configurations (human-like, maize-like, -k 7)")
     ap.add_argument("--config-reads", type=int, default=0, help="reads per step of the kernel-only legs (0 = --reads)")
     ap.add_argument("--config-sample-reads", type=int, default=8192, help="reads of each leg that the C oracle maps for the column-by-column check")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: mapeval counts, the roofline (one instrumented launch), smaller_batches, "
+                         "the CPU baseline, the other configurations' legs and end to end (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hits of the last timed step as DIR/<column>.npy (float64; a fixed, seeded sample "
+                         "of %d reads per run when the batch is larger; read_index.npy says which reads)" % DUMP_READS)
     return ap.parse_args()
 
 
@@ -315,6 +331,19 @@ def records_written(torch, d_out, n):
     """How many of the n result records carry a status a wave wrote (0 unmapped, 1 mapped, 2 overflow): n, or a read was lost."""
     st = d_out.view(torch.int32).view(n, -1)[:, 0]
     return int(((st >= 0) & (st <= 2)).sum().item())
+
+
+def dump_outputs(mq, hits, path, rank, world):
+    """--dump-outputs: the hits a caller of the timed path receives, one float64 array per PAF column (q_start / q_end whole, i.e. with
+    their high words) plus read_index.npy.  A batch larger than this rank's share of DUMP_READS is sampled: the same seeded choice of
+    reads for the same batch size, so that two builds compare read for read."""
+    os.makedirs(path, exist_ok=True)
+    n, cap = hits.size, max(1, DUMP_READS // world)
+    idx = np.arange(n, dtype=np.int64) if n <= cap else np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n, cap, replace=False))
+    pre = "" if world == 1 else "rank%d_" % rank
+    np.save(os.path.join(path, pre + "read_index.npy"), idx.astype(np.float64))
+    for c in DUMP_COLUMNS:
+        np.save(os.path.join(path, pre + c + ".npy"), mq.hit_column(hits[idx], c).astype(np.float64))
 
 
 def kernel_leg(mq, sim, O, torch, dev, local_rank, P, po, genome, ctg_off, ctg_names, B, steps, warmup, ncpu, sample_reads, workload, n_reads=None, variant=0,
@@ -659,9 +688,10 @@ def main():
     strong = args.scaling == "strong"
     solo = rank == 0 and world == 1
     # reads kept in host memory as well: what the CPU baseline, the oracle checks and the file legs read (N = 1 only); every 32nd read of
-    # the rest for the strided oracle check.  A rank of a multi-GPU run keeps nothing: its batch exists in HBM only.
+    # the rest for the strided oracle check.  A rank of a multi-GPU run keeps nothing: its batch exists in HBM only; nor does a plain
+    # run, whose checks and legs are --full's.
     keep_first = 0
-    if solo:
+    if solo and args.full:
         keep_first = max(args.cpu_sample_reads or 49152, args.config_sample_reads if not args.no_configs else 0)
         if not args.no_e2e:
             keep_first = max(keep_first, 393216, args.e2e_file_reads, args.e2e_fastq_reads)
@@ -696,7 +726,7 @@ def main():
         del parts
     else:
         B = load_batch(torch, dev, sim, genome, ctg_off, args.reads, args.seed + 1000 + rank, threads, keep_first=keep_first,
-                       keep_stride=32 if solo else 0, stride_from=min(args.cpu_sample_reads or 49152, args.config_sample_reads))
+                       keep_stride=32 if solo and args.full else 0, stride_from=min(args.cpu_sample_reads or 49152, args.config_sample_reads))
     offs = B.offsets
     n = B.n
     total_bases = B.total_bases
@@ -708,10 +738,11 @@ def main():
     stream = torch.cuda.current_stream(dev)
 
     pipe = HostPipeline(mq, ix, dict(bases=B.head_bases, offsets=offs)) if strong else None
+    last_pass = [None]  # strong scaling: the hits in host memory that the last pass handed back
 
     def step():
         if strong:
-            pipe.run_pass()
+            last_pass[0] = pipe.run_pass()
         else:
             ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
 
@@ -752,27 +783,31 @@ def main():
         all_bases, all_reads = float(total_bases), float(n)
         per_rank = None
         per_rank_setup, per_rank_rss = [round(t_first_step, 1)], [rss_setup]
-    if strong:  # the kernel's own launch time for the roofline: one resident launch of this rank's shard, outside the timed region
+    if strong:
         pipe.close()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
-        e0.record(stream)
-        ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        kern_ms = [e0.elapsed_time(e1)]
+        hits = last_pass[0]  # what the last timed pass handed back (host memory)
+        n_written = int((hits["status"] <= 2).sum())  # (the hits of a pass start out as zeros: a lost read would read as unmapped here)
+        kern_ms = None
+        if args.full:  # the kernel's own launch time for the roofline: one resident launch of this rank's shard, outside the timed region
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
+            e0.record(stream)
+            ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            kern_ms = [e0.elapsed_time(e1)]
+            n_written = min(n_written, records_written(torch, d_out, n))  # that launch's buffer was poisoned: a lost read shows there
     else:
         kern_ms = [a.elapsed_time(b) for a, b in ev]
-    avg_kern_s = float(np.mean(kern_ms)) / 1e3
-    # every read of the batch has a record that a wave wrote (the buffer was poisoned before the warm-up)
-    n_written = records_written(torch, d_out, n)
+        # every read of the batch has a record that a wave wrote (the buffer was poisoned before the warm-up)
+        n_written = records_written(torch, d_out, n)
     if n_written != n:
         raise SystemExit("bench.py: %d of %d result records were never written: reads were lost by the launch" % (n - n_written, n))
-    d_step = d_out.clone()  # the timed steps' results: compared below with the instrumented launch and the oracle
 
     # the same kernel on the first m reads of the batch: what a launch's fixed cost (start-up + tail) does to smaller batches
     smaller = {}
-    if not strong and not args.no_smaller_batches:
+    if args.full and not strong and not args.no_smaller_batches:
+        d_step = d_out.clone()  # the timed steps' results: compared below with the instrumented launch and the oracle
         for m in (49152, 196608, 786432):
             if m < n:
                 tb = int(offs[m])
@@ -794,10 +829,14 @@ def main():
             ix.map_batch_device(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out.data_ptr(), stream.cuda_stream)
             torch.cuda.synchronize()
             assert torch.equal(d_out, d_step), "a launch of the same batch gave other results than the timed steps"
-    del d_out
-    d_out = d_step
-    hits = np.frombuffer(d_out.cpu().numpy().tobytes(), dtype=mq.hit_dtype)
-    launch_order = dict(zip(("reads_flagged", "reads_first"), ix.last_map_order()))  # order_reads_kernel: reads taken up first
+        del d_out
+        d_out = d_step
+    if not strong:
+        hits = np.frombuffer(d_out.cpu().numpy().tobytes(), dtype=mq.hit_dtype)
+    if args.dump_outputs:
+        dump_outputs(mq, hits, args.dump_outputs, rank, world)
+    # order_reads_kernel: reads taken up first (strong scaling maps through stream slots: the index itself launched only for --full)
+    launch_order = dict(zip(("reads_flagged", "reads_first"), ix.last_map_order())) if not strong or args.full else None
     if os.environ.get("MQ_BENCH_DUMP_HITS"):  # test hook: this rank's hits (strong scaling: of its shard of the one read set)
         np.save(os.path.join(os.environ["MQ_BENCH_DUMP_HITS"], "hits_rank%d_of_%d.npy" % (rank, world)), hits.view(np.uint8))
     n_kmm = int(hits["n_kminmers"].astype(np.int64).sum())
@@ -808,86 +847,91 @@ def main():
     rl = (offs[1:] - offs[:-1]).astype(np.int64)
     n_unmapped_seeded = int(((hits["status"] == 0) & (rl >= args.l + args.k - 1) & (hits["n_kminmers"] >= 1)).sum())
 
-    # ---- roofline of the dominant (only) kernel of a step: map_kernel
-    # algorithmic bytes per launch = SURVEY.md 8(d): L*b_in + n_kmm*S_slot*p_bar + S_out per read, with b_in = 1 B (ASCII in
-    # HBM), S_slot = 32 B, p_bar = mean probes per lookup MEASURED on this batch by one instrumented launch outside the timed
-    # region, S_out = 40 B (+ 8 B offset)
-    d_out2 = torch.empty_like(d_out)
-    poison(d_out2)
-    lookups, extra = ix.probe_stats(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out2.data_ptr())
-    torch.cuda.synchronize()
-    assert records_written(torch, d_out2, n) == n, "the instrumented launch left result records unwritten"
-    assert torch.equal(d_out, d_out2), "instrumented launch disagrees with the timed one"  # byte for byte: status, columns, n_kminmers of every read
-    del d_out2
-    p_bar = 1.0 + extra / max(lookups, 1)
-    alg_bytes = total_bases * 1 + n_kmm * st["slot_bytes"] * p_bar + n * (8 + 40)  # SURVEY 8(d)'s S_out = 40 B (the result record is 48 B since ABI 3)
-    achieved = alg_bytes / avg_kern_s / 1e9
-    traffic = None
-    traffic_commit = None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            if (tj.get("reads") == n and abs(tj.get("genome_scale", -1) - args.genome_scale) < 1e-9 and not real_ref and args.genome_preset == "planted-repeats"
-                    and args.k == 5 and args.l == 31 and not args.seeding_variant and not args.fast_kh):  # (the counters were taken on the headline workload)
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_commit = tj.get("commit")
-        except Exception:
-            traffic = None
-    roofline = dict(bound="hbm", achieved=round(achieved, 2), peak=8000.0, unit="GB/s", frac=round(achieved / 8000.0, 4),
-                    traffic=traffic, traffic_taken_at_commit=traffic_commit, kernel="map_kernel", avg_launch_ms=round(avg_kern_s * 1e3, 4),
-                    algorithmic_bytes_per_launch=int(alg_bytes), mean_probes_per_lookup=round(p_bar, 4))
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant (only) kernel of a step: map_kernel
+        # algorithmic bytes per launch = SURVEY.md 8(d): L*b_in + n_kmm*S_slot*p_bar + S_out per read, with b_in = 1 B (ASCII in
+        # HBM), S_slot = 32 B, p_bar = mean probes per lookup MEASURED on this batch by one instrumented launch outside the timed
+        # region, S_out = 40 B (+ 8 B offset)
+        avg_kern_s = float(np.mean(kern_ms)) / 1e3
+        d_out2 = torch.empty_like(d_out)
+        poison(d_out2)
+        lookups, extra = ix.probe_stats(d_bases.data_ptr(), d_offs.data_ptr(), n, total_bases, d_out2.data_ptr())
+        torch.cuda.synchronize()
+        assert records_written(torch, d_out2, n) == n, "the instrumented launch left result records unwritten"
+        assert torch.equal(d_out, d_out2), "instrumented launch disagrees with the timed one"  # byte for byte: status, columns, n_kminmers of every read
+        del d_out2
+        p_bar = 1.0 + extra / max(lookups, 1)
+        alg_bytes = total_bases * 1 + n_kmm * st["slot_bytes"] * p_bar + n * (8 + 40)  # SURVEY 8(d)'s S_out = 40 B (the result record is 48 B since ABI 3)
+        achieved = alg_bytes / avg_kern_s / 1e9
+        traffic = None
+        traffic_commit = None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if (tj.get("reads") == n and abs(tj.get("genome_scale", -1) - args.genome_scale) < 1e-9 and not real_ref and args.genome_preset == "planted-repeats"
+                        and args.k == 5 and args.l == 31 and not args.seeding_variant and not args.fast_kh):  # (the counters were taken on the headline workload)
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_commit = tj.get("commit")
+            except Exception:
+                traffic = None
+        roofline = dict(bound="hbm", achieved=round(achieved, 2), peak=8000.0, unit="GB/s", frac=round(achieved / 8000.0, 4),
+                        traffic=traffic, traffic_taken_at_commit=traffic_commit, kernel="map_kernel", avg_launch_ms=round(avg_kern_s * 1e3, 4),
+                        algorithmic_bytes_per_launch=int(alg_bytes), mean_probes_per_lookup=round(p_bar, 4))
 
-    # SURVEY.md 8(d)'s second bound: vector-instruction issue.  wave-instructions per launch and the shader clock come from the PMC
-    # passes of the same workload (profiles/pmc_issue.json, tools/issue_json.py); the launch time is this run's; the ceiling is
-    # what a SIMD issues at map_kernel's occupancy (four waves per SIMD as two 8-wave workgroups per CU) on the instruction mix
-    # of stage B in the microbenchmark (profiles/r03_valu_occ.txt, profiles/r04_valu_enc.txt, profiles/r04_valu_enc_stepb.txt).
-    ipath = os.path.join(ROOT, "profiles", "pmc_issue.json")
-    if os.path.exists(ipath):
-        try:
-            ij = json.load(open(ipath))
-            if (ij.get("reads") == n and abs(ij.get("genome_scale", -1) - args.genome_scale) < 1e-9 and ij.get("k") == args.k and not strong and not real_ref
-                    and args.genome_preset == "planted-repeats" and args.l == 31 and not args.seeding_variant and not args.fast_kh):
-                n_simd = int(ij["n_simd"])
-                # cycles: the launch's busy cycles as the counters gave them (GRBM_GUI_ACTIVE / 8 XCDs) -- a property of the kernel on this
-                # workload; this run's launch time only says what shader clock that implies here (the clock moves with the power state:
-                # 1.95 GHz under the profiler, ~2.15 GHz in a plain run)
-                cyc = float(ij["busy_cycles_per_launch"])
-                cpi = cyc * n_simd / float(ij["wave_instructions_per_launch"])
-                roofline["secondary"] = dict(bound="valu_issue", wave_instructions_per_launch=int(ij["wave_instructions_per_launch"]),
-                                             valu=int(ij["valu"]), salu=int(ij["salu"]), lds=int(ij["lds"]), vmem=int(ij["vmem"]), n_simd=n_simd,
-                                             busy_cycles_per_launch=int(cyc), cycles_per_instruction=round(cpi, 3),
-                                             ceiling_cycles_per_instruction=ij["ceiling_cycles_per_instruction"],
-                                             ceiling_scope="stage B's step only (10 VALU + 1 LDS as built, tools/valu_enc.hip, at this kernel's occupancy): a measured "
-                                                           "floor of the kernel's densest loop, not of its whole instruction mix (80 % VALU / 14 % SALU / 6 % LDS over five stages)",
-                                             frac=round(float(ij["ceiling_cycles_per_instruction"]) / cpi, 4),
-                                             hardware_ceiling_cycles_per_instruction=2.0,
-                                             hardware_ceiling_source="/opt/skills/guides/MI355X_MICROARCH.md: a wave64 VALU instruction issues over 2 cycles on a SIMD-32 "
-                                                                     "(one wave alone sustains one per 4)",
-                                             frac_of_hardware_ceiling=round(2.0 / cpi, 4), waves_per_simd=ij.get("waves_per_simd"),
-                                             implied_shader_clock_mhz_this_run=round(cyc / avg_kern_s / 1e6, 1),
-                                             shader_clock_mhz_in_counter_pass=ij["shader_clock_mhz"],
-                                             counters_taken_at_commit=ij.get("commit"), ceiling_source=ij.get("ceiling_source"),
-                                             wait_share=ij.get("wait_share"), lds_bank_conflict_share=ij.get("lds_bank_conflict_share"),
-                                             note="cycles per wave-instruction per SIMD = busy cycles x SIMDs / instructions, both counted by rocprofv3 --pmc "
-                                                  "on this workload (separate passes); frac = ceiling / achieved: how close the kernel is to what a SIMD "
-                                                  "can issue on stage B's instruction mix at this occupancy")
-        except Exception as ex:  # noqa: BLE001
-            roofline["secondary"] = {"error": repr(ex)[:200]}
+        # SURVEY.md 8(d)'s second bound: vector-instruction issue.  wave-instructions per launch and the shader clock come from the PMC
+        # passes of the same workload (profiles/pmc_issue.json, tools/issue_json.py); the launch time is this run's; the ceiling is
+        # what a SIMD issues at map_kernel's occupancy (four waves per SIMD as two 8-wave workgroups per CU) on the instruction mix
+        # of stage B in the microbenchmark (profiles/r03_valu_occ.txt, profiles/r04_valu_enc.txt, profiles/r04_valu_enc_stepb.txt).
+        ipath = os.path.join(ROOT, "profiles", "pmc_issue.json")
+        if os.path.exists(ipath):
+            try:
+                ij = json.load(open(ipath))
+                if (ij.get("reads") == n and abs(ij.get("genome_scale", -1) - args.genome_scale) < 1e-9 and ij.get("k") == args.k and not strong and not real_ref
+                        and args.genome_preset == "planted-repeats" and args.l == 31 and not args.seeding_variant and not args.fast_kh):
+                    n_simd = int(ij["n_simd"])
+                    # cycles: the launch's busy cycles as the counters gave them (GRBM_GUI_ACTIVE / 8 XCDs) -- a property of the kernel on this
+                    # workload; this run's launch time only says what shader clock that implies here (the clock moves with the power state:
+                    # 1.95 GHz under the profiler, ~2.15 GHz in a plain run)
+                    cyc = float(ij["busy_cycles_per_launch"])
+                    cpi = cyc * n_simd / float(ij["wave_instructions_per_launch"])
+                    roofline["secondary"] = dict(bound="valu_issue", wave_instructions_per_launch=int(ij["wave_instructions_per_launch"]),
+                                                 valu=int(ij["valu"]), salu=int(ij["salu"]), lds=int(ij["lds"]), vmem=int(ij["vmem"]), n_simd=n_simd,
+                                                 busy_cycles_per_launch=int(cyc), cycles_per_instruction=round(cpi, 3),
+                                                 ceiling_cycles_per_instruction=ij["ceiling_cycles_per_instruction"],
+                                                 ceiling_scope="stage B's step only (10 VALU + 1 LDS as built, tools/valu_enc.hip, at this kernel's occupancy): a measured "
+                                                               "floor of the kernel's densest loop, not of its whole instruction mix (80 % VALU / 14 % SALU / 6 % LDS over five stages)",
+                                                 frac=round(float(ij["ceiling_cycles_per_instruction"]) / cpi, 4),
+                                                 hardware_ceiling_cycles_per_instruction=2.0,
+                                                 hardware_ceiling_source="CDNA4 (MI355X) microarchitecture: a wave64 VALU instruction issues over 2 cycles on a SIMD-32 "
+                                                                         "(one wave alone sustains one per 4)",
+                                                 frac_of_hardware_ceiling=round(2.0 / cpi, 4), waves_per_simd=ij.get("waves_per_simd"),
+                                                 implied_shader_clock_mhz_this_run=round(cyc / avg_kern_s / 1e6, 1),
+                                                 shader_clock_mhz_in_counter_pass=ij["shader_clock_mhz"],
+                                                 counters_taken_at_commit=ij.get("commit"), ceiling_source=ij.get("ceiling_source"),
+                                                 wait_share=ij.get("wait_share"), lds_bank_conflict_share=ij.get("lds_bank_conflict_share"),
+                                                 note="cycles per wave-instruction per SIMD = busy cycles x SIMDs / instructions, both counted by rocprofv3 --pmc "
+                                                      "on this workload (separate passes); frac = ceiling / achieved: how close the kernel is to what a SIMD "
+                                                      "can issue on stage B's instruction mix at this occupancy")
+            except Exception as ex:  # noqa: BLE001
+                roofline["secondary"] = {"error": repr(ex)[:200]}
 
     # ---- accuracy on the whole batch (BASELINE metric: "Q60 mapeval parity"): paftools-mapeval-style counts
-    if have_truth:
-        truth = B.truth
-        pafs = {"mapped": (hits["status"] == 1).astype(np.uint32)}
-        for a_ in ("ref_id", "rc", "mapq", "r_start", "r_end"):
-            pafs[a_] = hits[a_]
-        n_m, n_q60, n_q60_wrong = sim.mapeval(truth, pafs)
-    else:  # real reads: no truth in the names -- truth-free counts only (the reference's Table 1 reports the same two for HG002)
-        n_m, n_q60, n_q60_wrong = n_mapped, int(((hits["status"] == 1) & (hits["mapq"] == 60)).sum()), None
+    n_m = n_q60 = n_q60_wrong = None
+    if args.full:
+        if have_truth:
+            truth = B.truth
+            pafs = {"mapped": (hits["status"] == 1).astype(np.uint32)}
+            for a_ in ("ref_id", "rc", "mapq", "r_start", "r_end"):
+                pafs[a_] = hits[a_]
+            n_m, n_q60, n_q60_wrong = sim.mapeval(truth, pafs)
+        else:  # real reads: no truth in the names -- truth-free counts only (the reference's Table 1 reports the same two for HG002)
+            n_m, n_q60, n_q60_wrong = n_mapped, int(((hits["status"] == 1) & (hits["mapq"] == 60)).sum()), None
 
     # ---- CPU baseline: the C oracle ("port") on a bounded sample of the same reads, rank 0 at N=1 only
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         po = O.params(k=args.k, l=args.l, density=args.density)
         t0 = time.time()
@@ -935,7 +979,7 @@ def main():
     # ---- kernel-only legs of the other configurations (rank 0, N=1): a human-like repeat landscape, a maize-like repetitive genome
     # (BASELINE config 5, experiments/simulate_maize.sh:9) and -k 7 (BASELINE config 4, experiments/table1.sh:50)
     configs = None
-    if rank == 0 and world == 1 and not args.no_configs and not strong and not real_ref:  # (synthetic stand-ins of the other configurations)
+    if args.full and rank == 0 and world == 1 and not args.no_configs and not strong and not real_ref:  # (synthetic stand-ins of the other configurations)
         from oracle import oracle as O
         configs = {}
         nr = args.config_reads or args.reads
@@ -999,7 +1043,7 @@ def main():
 
     # ---- end to end (rank 0, N=1): host buffers -> hits through three stream slots, and FASTA files -> PAF through the native driver
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         import tempfile
         e2e = {}
         n_hb = min(n, 393216, B.keep_first)  # (page-locking the whole step batch would take longer than the leg)
@@ -1065,6 +1109,7 @@ def main():
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
+            "full": bool(args.full),
             "dtype": "u64",
             "data": ("real" if args.reads_fastx else "real reference, simulated reads") if real_ref else "synthetic",
             "config": {

@@ -26,7 +26,7 @@ def _free_port():
 
 def _bench(world, mode, dump=None, reads=6000):
     args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--genome-scale", "0.02", "--reads", str(reads), "--scaling", mode,
-            "--no-cpu-baseline", "--no-e2e", "--no-configs"]
+            "--full", "--no-cpu-baseline", "--no-e2e", "--no-configs"]
     env = dict(os.environ, MQ_BENCH_FAKE_RANKS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if dump:
         env["MQ_BENCH_DUMP_HITS"] = str(dump)

@@ -169,7 +169,7 @@ def test_bench_line_small_run(mode):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--genome-scale", "0.01", "--reads", "3000", "--steps", "2", "--warmup", "1",
-           "--scaling", mode, "--no-cpu-baseline", "--e2e-file-reads", "1500"]
+           "--scaling", mode, "--full", "--no-cpu-baseline", "--e2e-file-reads", "1500"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -182,6 +182,39 @@ def test_bench_line_small_run(mode):
     e = j["end_to_end"]
     assert e["host_buffers_hits_identical"] and e["host_buffers_gbases_s"] > 0
     assert e["file_to_paf"].get("paf_lines", 0) > 1300, e
+
+
+@pytest.mark.parametrize("mode", ["weak", "strong"])
+def test_bench_plain_line_and_dump_outputs(mode, tmp_path):
+    """A plain bench run (no --full): the headline keys, exactly --steps timed steps, none of --full's sections; --dump-outputs holds the
+    last timed step's hits as float64 columns, the same arrays a --full run of the same arguments computes."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--genome-scale", "0.01", "--reads", "3000", "--warmup", "1", "--scaling", mode]
+    out = {}
+    for tag, extra in (("plain", ["--steps", "3"]), ("full", ["--steps", "2", "--full", "--no-cpu-baseline", "--no-e2e", "--no-configs"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out[tag] = json.loads(r.stdout.strip().splitlines()[-1])
+    j = out["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert j[k] == out["full"][k], k
+    assert j["full"] is False and out["full"]["full"] is True
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["records_written"] == 3000
+    assert all(j[k] is None for k in ("roofline", "cpu_baseline", "configs", "end_to_end", "smaller_batches", "q60", "q60_wrong", "mapped_reads"))
+    assert out["full"]["roofline"]["bound"] == "hbm" and out["full"]["q60"] > 0.9 * 3000
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert "read_index.npy" in names and "status.npy" in names and "r_start.npy" in names and sorted(os.listdir(tmp_path / "full")) == names
+    for f in names:
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.dtype == np.float64 and a.shape == (3000,) and np.array_equal(a, b), f
+    st = np.load(tmp_path / "plain" / "status.npy")
+    assert set(np.unique(st)) <= {0.0, 1.0, 2.0} and (st == 1).mean() > 0.9
 
 
 def test_bench_line_with_a_real_reference_and_real_reads(simlib, tmp_path):
@@ -210,7 +243,7 @@ def test_bench_line_with_a_real_reference_and_real_reads(simlib, tmp_path):
             s = reads["bases"][int(o[i]):int(o[i + 1])].tobytes()
             f.write(b"@" + n.encode() + b"\n" + s + b"\n+\n" + b"I" * len(s) + b"\n")
             h.write(b">m64011_190830_220126/%d/ccs\n" % i + s + b"\n")
-    base = [sys.executable, os.path.join(root, "bench.py"), "--reads", "3000", "--steps", "2", "--warmup", "1", "--no-e2e", "--cpu-sample-reads", "512",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--reads", "3000", "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--cpu-sample-reads", "512",
             "--reference-fasta", str(ref)]
     out = {}
     for tag, extra in (("fq", ["--reads-fastx", str(fq)]), ("anon", ["--reads-fastx", str(fa), "--no-cpu-baseline"]), ("sim", ["--no-cpu-baseline"])):

@@ -7,7 +7,7 @@ rocprofv3 -L 2>/dev/null | grep -i -o "SQC_ICACHE[A-Z_]*\|SQ_IFETCH[A-Z_]*\|SQC_
 for n in ${ICACHE_SIZES:-4096 8192 196608}; do
   for grp in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES" "SQC_ICACHE_MISSES_DUPLICATE SQ_WAVE_CYCLES" "SQ_IFETCH SQ_BUSY_CYCLES"; do
     d=$OUT/n${n}_$(echo $grp | tr ' ' '+')
-    timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $d -- python3 $ROOT/bench.py --no-cpu-baseline --no-e2e --no-configs --no-smaller-batches --steps 3 --warmup 1 --reads $n > $d.json 2> $d.err < /dev/null
+    timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $d -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-e2e --no-configs --no-smaller-batches --steps 3 --warmup 1 --reads $n > $d.json 2> $d.err < /dev/null
   done
 done
 python3 - $OUT <<'PY'

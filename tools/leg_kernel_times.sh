@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-legs}; OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-e2e --no-smaller-batches --steps 5 --warmup 1 > $OUT/bench_legs.json 2> $OUT/bench_legs.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o run -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-e2e --no-smaller-batches --steps 5 --warmup 1 > $OUT/bench_legs.json 2> $OUT/bench_legs.err
 f=$(find $OUT/trace -name "*kernel_trace.csv" | head -1)
 python3 - $f > $OUT/leg_kernels.txt <<'PY'
 import csv, sys, collections
