@@ -568,7 +568,7 @@ def test_fuzz_params_and_sequences(mq, oracle, simlib):
     """Random (k, l, density, hpc, c, s, g) x random genomes/reads incl. N runs, lowercase, low-complexity stretches."""
     rng = np.random.default_rng(int(os.environ.get("MQ_FUZZ_SEED", "20240")))  # MQ_FUZZ_ITERS / MQ_FUZZ_SEED: longer one-off campaigns
     for it in range(int(os.environ.get("MQ_FUZZ_ITERS", "24"))):
-        k = int(rng.integers(1, 13))
+        k = int(rng.integers(1, 33))
         l = int(rng.choice([1, 2, 5, 8, 12, 15, 16, 17, 24, 31, 32, 33, 47, 63, 64]))
         dens = float(rng.choice([0.002, 0.01, 0.03, 0.1, 0.3]))
         ps = dict(k=k, l=l, density=dens, use_hpc=bool(rng.integers(0, 2)), c=int(rng.integers(0, 6)), s=int(rng.integers(0, 15)),
@@ -620,8 +620,13 @@ def test_fuzz_params_and_sequences(mq, oracle, simlib):
             nerr = int(rng.integers(0, max(2, seg.size // int(rng.choice([30, 140, 1000])))))
             at = rng.integers(0, seg.size, size=nerr)
             seg[at] = rng.choice(np.frombuffer(b"ACGTacgtNR", dtype=np.uint8), size=nerr)
+        if it % 4 == 3:  # every fourth case: mosaic reads of this genome (tests/mosaic.py) -- many Matches, many candidate references, ties
+            import mosaic
+            bases, offs, _ = mosaic.mosaic_reads(g, off, rng, 40, int(rng.choice([3, 30, 200])), (30, int(rng.choice([300, 1500, 4000]))),
+                                                 float(rng.choice([0.2, 0.6])), mosaic.DEFAULT_DELTAS, err=float(rng.choice([0, 0, 0.01])))
         reads2 = dict(reads)
         reads2["bases"] = bases
+        reads2["offsets"] = offs
         # every third case under another reading of the third-party k-min-mer iterator (mq_params.flags bits 8..13 = the oracle's
         # mqo_set_variant; bit 8 needs l >= 2): the variants' code paths see the same damaged inputs as the frozen reading's
         variant = 0
