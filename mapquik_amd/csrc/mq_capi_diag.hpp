@@ -1,5 +1,6 @@
 // mq_capi_diag.hpp -- measurement and diagnostic entry points (include/mapquik_hip_diag.h): probe statistics, stage clocks, launch timers, the
-// random-probe rate of the memory system (part of the one translation unit mq_capi.hip).  Nothing here is on the product path.
+// random-probe rate of the memory system (part of the one translation unit mq_capi.hip).  Nothing here is on the product path.  The entry
+// points run inside guarded() and own what they allocate, like the rest of the C ABI.
 #pragma once
 
 // Diagnostic (tools/probe_rate.py): how many random index probes per second the memory system sustains, detached from
@@ -77,190 +78,168 @@ __global__ void probe_rate_kernel(const Bucket *__restrict__ table, uint64_t mas
 
 extern "C" {
 
-int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general) try {
-    if (!idx || !n_fast || !n_general) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    HIPCHK(hipEventSynchronize(c->ev1));
-    uint32_t v[2] = {0, 0};
-    HIPCHK(hipMemcpy(v, c->d_counter + 4, 8, hipMemcpyDeviceToHost));
-    *n_fast = v[0];
-    *n_general = v[1];
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general) {
+    return guarded([&]() -> int {
+        if (!idx || !n_fast || !n_general) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(c->ev1));
+        uint32_t v[2] = {0, 0};
+        HIPCHK(hipMemcpy(v, c->d_counter + 4, 8, hipMemcpyDeviceToHost));
+        *n_fast = v[0];
+        *n_general = v[1];
+        return MQ_OK;
+    });
 }
 
-int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first) try {
-    if (!idx || !n_flagged || !n_first) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    HIPCHK(hipEventSynchronize(c->ev1));
-    uint32_t v = 0;
-    HIPCHK(hipMemcpy(&v, c->d_counter + WORK_NF, 4, hipMemcpyDeviceToHost));
-    *n_flagged = v;
-    *n_first = v < WORK_FRONT_CAP ? v : WORK_FRONT_CAP;
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first) {
+    return guarded([&]() -> int {
+        if (!idx || !n_flagged || !n_first) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(c->ev1));
+        uint32_t v = 0;
+        HIPCHK(hipMemcpy(&v, c->d_counter + WORK_NF, 4, hipMemcpyDeviceToHost));
+        *n_flagged = v;
+        *n_first = v < WORK_FRONT_CAP ? v : WORK_FRONT_CAP;
+        return MQ_OK;
+    });
 }
 
-int mq_index_table_alloc_ms(mq_index *idx, float *ms) try {
-    if (!idx || !ms) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
-    *ms = (float)idx->table_alloc_ms;
-    return MQ_OK;
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_index_table_alloc_ms(mq_index *idx, float *ms) {
+    return guarded([&]() -> int {
+        if (!idx || !ms) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
+        *ms = (float)idx->table_alloc_ms;
+        return MQ_OK;
+    });
 }
 
-int mq_map_launch_waves(mq_index *idx, uint32_t n_reads, uint32_t *n_waves) try {
-    if (!idx || !n_waves) return set_err(MQ_EINVAL, "bad arguments");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    if ((rc = ensure_geometry(idx))) return rc;
-    const uint32_t grid = std::min<uint32_t>(idx->grid_fused, (n_reads + MAP_WAVES - 1) / MAP_WAVES);  // launch_map's grid
-    *n_waves = grid * (uint32_t)MAP_WAVES;
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_map_launch_waves(mq_index *idx, uint32_t n_reads, uint32_t *n_waves) {
+    return guarded([&]() -> int {
+        if (!idx || !n_waves) return set_err(MQ_EINVAL, "bad arguments");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        if ((rc = ensure_geometry(idx))) return rc;
+        *n_waves = fused_grid(idx, n_reads) * (uint32_t)MAP_WAVES;
+        return MQ_OK;
+    });
 }
 
 int mq_map_probe_stats(mq_index *idx, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases, mq_hit *d_out,
-                       uint64_t *lookups, uint64_t *extra_steps) try {
-    if (!idx || !lookups || !extra_steps) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    int rc = ctx_map_device(c, d_bases, d_offsets, n, total_bases, d_out, nullptr, true);  // the choice travels with this launch: contexts never see it
-    if (rc) return rc;
-    HIPCHK(hipEventSynchronize(c->ev1));
-    uint64_t v[2];
-    HIPCHK(hipMemcpy(v, c->d_counter + 8, 16, hipMemcpyDeviceToHost));
-    *extra_steps = v[0];
-    *lookups = v[1];
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                       uint64_t *lookups, uint64_t *extra_steps) {
+    return guarded([&]() -> int {
+        if (!idx || !lookups || !extra_steps) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        int rc = ctx_map_device(c, d_bases, d_offsets, n, total_bases, d_out, nullptr, true);  // the choice travels with this launch: contexts never see it
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(c->ev1));
+        uint64_t v[2];
+        HIPCHK(hipMemcpy(v, c->d_counter + 8, 16, hipMemcpyDeviceToHost));
+        *extra_steps = v[0];
+        *lookups = v[1];
+        return MQ_OK;
+    });
 }
 
 // Diagnostic: what every read of the last mq_map_probe_stats launch cost its wave (shader-clock cycles from the read's first instruction to
 // its result's store) and when the wave took it up (the 100-MHz constant clock): where a launch's tail comes from.
-int mq_last_read_cycles(mq_index *idx, uint32_t n, uint32_t *cycles, uint64_t *start_ticks) try {
-    if (!idx || !cycles || !start_ticks) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    if (!c->ev_valid || n > c->reads_cap) return set_err(MQ_ESTATE, "no instrumented launch of that size recorded");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    HIPCHK(hipEventSynchronize(c->ev1));
-    HIPCHK(hipMemcpy(cycles, c->mz_count, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(start_ticks, c->mz_base, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_last_read_cycles(mq_index *idx, uint32_t n, uint32_t *cycles, uint64_t *start_ticks) {
+    return guarded([&]() -> int {
+        if (!idx || !cycles || !start_ticks) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        if (!c->ev_valid || n > c->reads_cap) return set_err(MQ_ESTATE, "no instrumented launch of that size recorded");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(c->ev1));
+        HIPCHK(hipMemcpy(cycles, c->mz_count, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(start_ticks, c->mz_base, (size_t)n * 8, hipMemcpyDeviceToHost));
+        return MQ_OK;
+    });
 }
 
 // Diagnostic (-DMQ_STAGE_CLOCKS builds; zeros otherwise): shader-clock cycles the waves of the last map_kernel launch of the default
 // context spent per stage, summed over waves (stage list: mq_device.hpp, mq_clk).
-int mq_last_stage_clocks(mq_index *idx, uint64_t *out16) try {
-    if (!idx || !out16) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    HIPCHK(hipEventSynchronize(c->ev1));
-    HIPCHK(hipMemcpy(out16, c->d_counter + 16, MQ_N_CLK * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_last_stage_clocks(mq_index *idx, uint64_t *out16) {
+    return guarded([&]() -> int {
+        if (!idx || !out16) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(c->ev1));
+        HIPCHK(hipMemcpy(out16, c->d_counter + 16, MQ_N_CLK * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        return MQ_OK;
+    });
 }
 
-int mq_last_map_ms(mq_index *idx, float *ms) try {
-    if (!idx || !ms) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    mq_ctx *c = idx->def_ctx;
-    if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
-    HIPCHK(hipEventSynchronize(c->ev1));
-    HIPCHK(hipEventElapsedTime(ms, c->ev0, c->ev1));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_last_map_ms(mq_index *idx, float *ms) {
+    return guarded([&]() -> int {
+        if (!idx || !ms) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx;
+        if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        HIPCHK(hipEventSynchronize(c->ev1));
+        HIPCHK(hipEventElapsedTime(ms, c->ev0, c->ev1));
+        return MQ_OK;
+    });
 }
 
 int mq_probe_rate(mq_index *idx, uint32_t blocks, uint32_t per_thread, uint32_t bitmap_log2, uint32_t table_too, float *ms,
-                  uint64_t *lookups, uint64_t *extra_steps) try {
-    if (!idx || !ms || !lookups || !extra_steps) return set_err(MQ_EINVAL, "bad arguments");
-    if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    int rc = use_device(idx);
-    if (rc) return rc;
-    unsigned long long *d_acc = nullptr;
-    uint32_t *bm = nullptr;
-    uint64_t bit_mask = 0;
-    HIPCHK(hipMalloc((void **)&d_acc, 16));
-    HIPCHK(hipMemset(d_acc, 0, 16));
-    if (bitmap_log2) {  // a stand-in bitmap with one bit in eight set
-        bit_mask = (1ull << bitmap_log2) - 1;
-        HIPCHK(hipMalloc((void **)&bm, (size_t)1 << (bitmap_log2 - 3)));
-        HIPCHK(hipMemset(bm, 0x10, (size_t)1 << (bitmap_log2 - 3)));
-    }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    per_thread = (per_thread + 3u) & ~3u;
-    hipLaunchKernelGGL(probe_rate_kernel, dim3(blocks), dim3(256), 0, 0, idx->table, idx->nslots - 1, per_thread, 1ull, d_acc, bm, bit_mask, table_too);  // warm-up
-    HIPCHK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(probe_rate_kernel, dim3(blocks), dim3(256), 0, 0, idx->table, idx->nslots - 1, per_thread, 0x1234567ull, d_acc, bm, bit_mask, table_too);
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(ms, e0, e1));
-    unsigned long long acc[2];
-    HIPCHK(hipMemcpy(acc, d_acc, 16, hipMemcpyDeviceToHost));
-    hipFree(d_acc);
-    hipFree(bm);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    *lookups = (uint64_t)blocks * 256ull * per_thread;
-    *extra_steps = acc[1] / 2;  // two launches accumulated
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                  uint64_t *lookups, uint64_t *extra_steps) {
+    return guarded([&]() -> int {
+        if (!idx || !ms || !lookups || !extra_steps) return set_err(MQ_EINVAL, "bad arguments");
+        if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        int rc = use_device(idx);
+        if (rc) return rc;
+        Buf<unsigned long long> d_acc;
+        Buf<uint8_t> bm_bytes;
+        ScopedEvent e0, e1;
+        uint64_t bit_mask = 0;
+        if ((rc = d_acc.alloc(2))) return rc;
+        HIPCHK(hipMemset(d_acc, 0, 16));
+        if (bitmap_log2) {  // a stand-in bitmap with one bit in eight set
+            bit_mask = (1ull << bitmap_log2) - 1;
+            if ((rc = bm_bytes.alloc((uint64_t)1 << (bitmap_log2 - 3)))) return rc;
+            HIPCHK(hipMemset(bm_bytes, 0x10, (size_t)1 << (bitmap_log2 - 3)));
+        }
+        const uint32_t *const bm = reinterpret_cast<const uint32_t *>(bm_bytes.p);
+        HIPCHK(hipEventCreate(&e0.h));
+        HIPCHK(hipEventCreate(&e1.h));
+        per_thread = (per_thread + 3u) & ~3u;
+        hipLaunchKernelGGL(probe_rate_kernel, dim3(blocks), dim3(256), 0, 0, idx->table, idx->nslots - 1, per_thread, 1ull, d_acc, bm, bit_mask, table_too);  // warm-up
+        HIPCHK(hipEventRecord(e0, 0));
+        hipLaunchKernelGGL(probe_rate_kernel, dim3(blocks), dim3(256), 0, 0, idx->table, idx->nslots - 1, per_thread, 0x1234567ull, d_acc, bm, bit_mask, table_too);
+        HIPCHK(hipEventRecord(e1, 0));
+        HIPCHK(hipEventSynchronize(e1));
+        HIPCHK(hipEventElapsedTime(ms, e0, e1));
+        unsigned long long acc[2];
+        HIPCHK(hipMemcpy(acc, d_acc, 16, hipMemcpyDeviceToHost));
+        *lookups = (uint64_t)blocks * 256ull * per_thread;
+        *extra_steps = acc[1] / 2;  // two launches accumulated
+        return MQ_OK;
+    });
 }
 
-int mq_ctx_last_map_ms(mq_ctx *ctx, float *ms) try {
-    if (!ctx || !ms) return set_err(MQ_EINVAL, "bad arguments");
-    if (!ctx->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
-    HIPCHK(hipEventSynchronize(ctx->ev1));
-    HIPCHK(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_last_map_ms(mq_ctx *ctx, float *ms) {
+    return guarded([&]() -> int {
+        if (!ctx || !ms) return set_err(MQ_EINVAL, "bad arguments");
+        if (!ctx->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        HIPCHK(hipEventSynchronize(ctx->ev1));
+        HIPCHK(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+        return MQ_OK;
+    });
 }
 
 }  // extern "C"

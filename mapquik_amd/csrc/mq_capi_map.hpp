@@ -1,5 +1,6 @@
-// mq_capi_map.hpp -- C ABI, mapping side: launch sequences, stream-slot contexts (mq_ctx_*), host-buffer and device-resident entry
-// points, device-parsed FASTA chunks, PAF formatting, page-locked host memory (part of the one translation unit mq_capi.hip).
+// mq_capi_map.hpp -- C ABI, mapping side: launch sequences (the kernel pair of each comes from MAP_KERNELS), stream-slot contexts
+// (mq_ctx_*), host-buffer and device-resident entry points, device-parsed FASTA chunks, PAF formatting, page-locked host memory (part of
+// the one translation unit mq_capi.hip).  Temporary device memory is a Buf: it goes when its function returns, by whichever way.
 #pragma once
 
 struct LaunchOpt {
@@ -54,26 +55,15 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     if (!idx->split) {
         if (n > WORK_ID_MASK) return set_err(MQ_EINVAL, "more than 2^30 - 1 reads in one batch");
         hipLaunchKernelGGL(order_reads_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, A);  // the launch order (and map_kernel's work descriptors)
-        uint32_t grid = std::min<uint32_t>(idx->grid_fused, (n + MAP_WAVES - 1) / MAP_WAVES);
+        uint32_t grid = fused_grid(idx, n);
         if (o.grid_override) grid = std::min(grid, o.grid_override);
         const dim3 blk(64 * MAP_WAVES);
-        if (idx->dp.variant) {  // a seeding variant other than the frozen reading: the instantiation built with the variants
-            if (o.instrumented) hipLaunchKernelGGL((map_kernel<64, true, true>), dim3(grid), blk, 0, st, A);
-            else if (idx->chain_chunk == 4) hipLaunchKernelGGL((map_kernel<4, false, true>), dim3(grid), blk, 0, st, A);
-            else hipLaunchKernelGGL((map_kernel<64, false, true>), dim3(grid), blk, 0, st, A);
-        } else if (o.instrumented) hipLaunchKernelGGL((map_kernel<64, true>), dim3(grid), blk, 0, st, A);
-        else if (idx->chain_chunk == 4) hipLaunchKernelGGL((map_kernel<4, false>), dim3(grid), blk, 0, st, A);
-        else hipLaunchKernelGGL((map_kernel<64, false>), dim3(grid), blk, 0, st, A);
+        // (a seeding variant other than the frozen reading takes the instantiation built with the variants)
+        const MapPair &kp = MAP_KERNELS[idx->dp.variant != 0][o.instrumented][idx->chain_chunk == 4];
+        hipLaunchKernelGGL(kp.map, dim3(grid), blk, 0, st, A);
         HIPCHK(hipGetLastError());
         // the reads the fast seeder declined (queue length on the device: map_kernel's grid, its waves leave at once when there are none)
-        const uint32_t gd = grid;
-        if (idx->dp.variant) {
-            if (o.instrumented) hipLaunchKernelGGL((map_declined_kernel<64, true, true>), dim3(gd), blk, 0, st, A);
-            else if (idx->chain_chunk == 4) hipLaunchKernelGGL((map_declined_kernel<4, false, true>), dim3(gd), blk, 0, st, A);
-            else hipLaunchKernelGGL((map_declined_kernel<64, false, true>), dim3(gd), blk, 0, st, A);
-        } else if (o.instrumented) hipLaunchKernelGGL((map_declined_kernel<64, true>), dim3(gd), blk, 0, st, A);
-        else if (idx->chain_chunk == 4) hipLaunchKernelGGL((map_declined_kernel<4, false>), dim3(gd), blk, 0, st, A);
-        else hipLaunchKernelGGL((map_declined_kernel<64, false>), dim3(gd), blk, 0, st, A);
+        hipLaunchKernelGGL(kp.declined, dim3(grid), blk, 0, st, A);
         HIPCHK(hipGetLastError());
     } else {
         const uint32_t gs = std::min<uint32_t>(idx->grid_seed, (n + SEED_WAVES - 1) / SEED_WAVES);
@@ -124,14 +114,14 @@ static int redo_overflow(mq_ctx *c, const uint8_t *bases, const uint64_t *offset
     const uint32_t rgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min(idx->grid_fused, idx->grid_map), (1ull << 30) / ((uint64_t)cap * sizeof(MatchRec) * waves)));
     int rc = ctx_ensure(c, (uint32_t)redo.size(), sub_total, 65536u);
     if (rc) return rc;
-    MatchRec *big = nullptr;
-    uint8_t *d_sb = nullptr;
-    uint64_t *d_so = nullptr;
-    mq_hit *d_sh = nullptr;
-    hipError_t e = hipMalloc((void **)&big, (size_t)rgrid * waves * cap * sizeof(MatchRec));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_sb, sub_total + 1);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_so, so.size() * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_sh, redo.size() * sizeof(mq_hit));
+    Buf<MatchRec> big;
+    Buf<uint8_t> d_sb;
+    Buf<uint64_t> d_so;
+    Buf<mq_hit> d_sh;
+    hipError_t e = big.try_alloc((uint64_t)rgrid * waves * cap);
+    if (e == hipSuccess) e = d_sb.try_alloc(sub_total + 1);
+    if (e == hipSuccess) e = d_so.try_alloc(so.size());
+    if (e == hipSuccess) e = d_sh.try_alloc(redo.size());
     if (e == hipSuccess && sub_total) e = hipMemcpyAsync(d_sb, sb.data(), sub_total, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_so, so.data(), so.size() * 8, hipMemcpyHostToDevice, c->stream);
     int rrc = MQ_OK;
@@ -146,15 +136,24 @@ static int redo_overflow(mq_ctx *c, const uint8_t *bases, const uint64_t *offset
     }
     if (e == hipSuccess && rrc == MQ_OK) e = hipMemcpyAsync(sh.data(), d_sh, redo.size() * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    else hipStreamSynchronize(c->stream);
-    hipFree(big);
-    hipFree(d_sb);
-    hipFree(d_so);
-    hipFree(d_sh);
+    else hipStreamSynchronize(c->stream);  // (the stream is idle before the buffers go, whichever way this returns)
     if (e != hipSuccess) return set_err(e == hipErrorOutOfMemory ? MQ_ENOMEM : MQ_EHIP, std::string("overflow retry: ") + hipGetErrorString(e));
     if (rrc) return rrc;
     for (size_t j = 0; j < redo.size(); ++j) out[redo[j]] = sh[j];
     return MQ_OK;
+}
+
+// What a batch of n reads in `total` bytes needs of a context on its way through the host-buffer entry points: the page-locked side,
+// scratch, device staging.
+static int ctx_ensure_staging(mq_ctx *c, uint32_t n, uint64_t total, bool with_lens) {
+    int rc;
+    if ((rc = c->h_off.ensure((uint64_t)n + 1))) return rc;
+    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((rc = ctx_ensure(c, n, total, list_f16(c->idx)))) return rc;
+    if ((rc = c->st_bases.ensure(total + 64))) return rc;
+    if ((rc = c->st_off.ensure((uint64_t)n + 1))) return rc;
+    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
+    return with_lens ? c->st_lens.ensure((uint64_t)n) : MQ_OK;
 }
 
 // host buffers -> device staging -> launch sequence -> page-locked hits, all asynchronous on the context's stream.
@@ -168,8 +167,7 @@ static int ctx_submit(mq_ctx *c, const uint8_t *bases, uint64_t buf_bytes, const
     if (n == 0) return MQ_OK;
     int rc = use_device(idx);
     if (rc) return rc;
-    if ((rc = grow_pinned(c->h_off, c->h_off_cap, (uint64_t)n + 1))) return rc;
-    if ((rc = grow_pinned(c->h_out, c->h_out_cap, (uint64_t)n))) return rc;
+    if ((rc = c->h_off.ensure((uint64_t)n + 1))) return rc;  // (ahead of the rest: the offsets are checked into it)
     uint64_t total, first;
     if (!lens) {
         first = offsets[0];
@@ -190,11 +188,7 @@ static int ctx_submit(mq_ctx *c, const uint8_t *bases, uint64_t buf_bytes, const
         }
     }
     c->h_off[n] = total;
-    if ((rc = ctx_ensure(c, n, total, list_f16(idx)))) return rc;
-    if ((rc = grow(c->st_bases, c->st_bases_cap, total + 64))) return rc;
-    if ((rc = grow(c->st_off, c->st_off_cap, (uint64_t)n + 1))) return rc;
-    if ((rc = grow(c->st_out, c->st_out_cap, (uint64_t)n))) return rc;
-    if (lens && (rc = grow(c->st_lens, c->st_lens_cap, (uint64_t)n))) return rc;
+    if ((rc = ctx_ensure_staging(c, n, total, lens != nullptr))) return rc;
     if (total) HIPCHK(hipMemcpyAsync(c->st_bases, bases + first, total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->st_off, c->h_off, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     LaunchOpt o;
@@ -255,14 +249,14 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
     if (rc) return rc;
     const uint32_t n_tiles = (uint32_t)((bytes + FX_TILE - 1) / FX_TILE);
     const uint32_t cap = fx_line_cap(bytes);
-    if ((rc = grow(c->st_bases, c->st_bases_cap, bytes + 64))) return rc;
-    if ((rc = grow(c->fx_tile_counts, c->fx_tile_counts_cap, (uint64_t)n_tiles + 1))) return rc;
-    if ((rc = grow(c->fx_tile_off, c->fx_tile_off_cap, (uint64_t)n_tiles + 1))) return rc;
-    if ((rc = grow(c->fx_nl, c->fx_nl_cap, cap))) return rc;
-    if ((rc = grow(c->st_off, c->st_off_cap, (uint64_t)cap / 2 + 1))) return rc;
-    if ((rc = grow(c->st_lens, c->st_lens_cap, (uint64_t)cap / 2 + 1))) return rc;
-    if (!c->fx_info) HIPCHK(hipMalloc((void **)&c->fx_info, 16));
-    if (!c->h_fx_info) HIPCHK(hipHostMalloc((void **)&c->h_fx_info, 16, hipHostMallocDefault));
+    if ((rc = c->st_bases.ensure(bytes + 64))) return rc;
+    if ((rc = c->fx_tile_counts.ensure((uint64_t)n_tiles + 1))) return rc;
+    if ((rc = c->fx_tile_off.ensure((uint64_t)n_tiles + 1))) return rc;
+    if ((rc = c->fx_nl.ensure(cap))) return rc;
+    if ((rc = c->st_off.ensure((uint64_t)cap / 2 + 1))) return rc;
+    if ((rc = c->st_lens.ensure((uint64_t)cap / 2 + 1))) return rc;
+    if (!c->fx_info && (rc = c->fx_info.alloc(4))) return rc;
+    if (!c->h_fx_info && (rc = c->h_fx_info.alloc(4))) return rc;
     hipStream_t st = c->stream;
     if (bytes) {
         // The bytes behind the last page boundary (< 4 KB) go through a page-locked buffer of the context: a caller that page-locks the
@@ -272,7 +266,7 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
         const uintptr_t cut = end_addr & ~(uintptr_t)4095;
         uint64_t main_len = cut > (uintptr_t)buf ? (uint64_t)(cut - (uintptr_t)buf) : 0;
         const uint64_t tail_len = bytes - main_len;
-        if (!c->h_fx_tail) HIPCHK(hipHostMalloc((void **)&c->h_fx_tail, 4096, hipHostMallocDefault));
+        if (!c->h_fx_tail && (rc = c->h_fx_tail.alloc(4096))) return rc;
         if (main_len) HIPCHK(hipMemcpyAsync(c->st_bases, buf, main_len, hipMemcpyHostToDevice, st));
         if (tail_len) {
             memcpy(c->h_fx_tail, buf + main_len, tail_len);
@@ -286,9 +280,9 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
     hipLaunchKernelGGL(list_newlines_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_nl, cap);
     const dim3 sgrid(std::max<uint32_t>(1, std::min<uint32_t>(cap / 2 / 256 + 1, (uint32_t)idx->n_cu * 4u)));
     if (format == MQ_FASTX_FASTQ)
-        hipLaunchKernelGGL(fastq_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off), c->st_lens, cap / 2);
+        hipLaunchKernelGGL(fastq_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
     else
-        hipLaunchKernelGGL(fasta_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off), c->st_lens, cap / 2);
+        hipLaunchKernelGGL(fasta_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, st));
     c->fx_pending = true;
@@ -314,9 +308,9 @@ static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_en
     *hits = nullptr;
     if (*flags & FX_IRREGULAR) return MQ_OK;  // not "header line, sequence line" all through: the caller parses this chunk on the host
     if (n == 0) return MQ_OK;
-    if ((rc = grow_pinned(c->h_out, c->h_out_cap, (uint64_t)n))) return rc;
-    if ((rc = grow_pinned(c->h_fx_nl, c->h_fx_nl_cap, (uint64_t)lines))) return rc;
-    if ((rc = grow(c->st_out, c->st_out_cap, (uint64_t)n))) return rc;
+    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((rc = c->h_fx_nl.ensure((uint64_t)lines))) return rc;
+    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
     if ((rc = ctx_ensure(c, n, c->fx_bytes, list_f16(idx)))) return rc;
     LaunchOpt o;
     o.d_lens = c->st_lens;
@@ -348,45 +342,35 @@ static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_en
 
 extern "C" {
 
-int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes) try {
-    if (!ctx || (bytes && !buf)) return set_err(MQ_EINVAL, "bad arguments");
-    return ctx_submit_fasta(ctx, buf, begin, bytes, MQ_FASTX_FASTA);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes) {
+    return guarded([&]() -> int {
+        if (!ctx || (bytes && !buf)) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_submit_fasta(ctx, buf, begin, bytes, MQ_FASTX_FASTA);
+    });
 }
 
-int mq_ctx_submit_fastx(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format) try {
-    if (!ctx || (bytes && !buf)) return set_err(MQ_EINVAL, "bad arguments");
-    return ctx_submit_fasta(ctx, buf, begin, bytes, format);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_submit_fastx(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format) {
+    return guarded([&]() -> int {
+        if (!ctx || (bytes && !buf)) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_submit_fasta(ctx, buf, begin, bytes, format);
+    });
 }
 
-int mq_ctx_wait_fasta(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags) try {
-    if (!ctx || !n_reads || !line_ends || !n_lines || !hits || !flags) return set_err(MQ_EINVAL, "bad arguments");
-    return ctx_wait_fasta(ctx, n_reads, line_ends, n_lines, hits, flags);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_wait_fasta(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags) {
+    return guarded([&]() -> int {
+        if (!ctx || !n_reads || !line_ends || !n_lines || !hits || !flags) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_wait_fasta(ctx, n_reads, line_ends, n_lines, hits, flags);
+    });
 }
 
-mq_ctx *mq_ctx_new(mq_index *idx) try {
-    if (!idx) {
-        set_err(MQ_EINVAL, "idx is NULL");
-        return nullptr;
-    }
-    return ctx_create(idx);
-} catch (const std::bad_alloc &) {
-    set_err(MQ_ENOMEM, "out of host memory");
-    return nullptr;
-} catch (const std::exception &e) {
-    set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
-    return nullptr;
+mq_ctx *mq_ctx_new(mq_index *idx) {
+    return guarded([&]() -> mq_ctx * {
+        if (!idx) {
+            set_err(MQ_EINVAL, "idx is NULL");
+            return nullptr;
+        }
+        return ctx_create(idx);
+    });
 }
 
 void mq_ctx_free(mq_ctx *ctx) {
@@ -395,213 +379,172 @@ void mq_ctx_free(mq_ctx *ctx) {
     ctx_release(ctx);
 }
 
-int mq_ctx_submit(mq_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) try {
-    if (!ctx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
-    return ctx_submit(ctx, bases, 0, offsets, nullptr, n, out);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_submit(mq_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) {
+    return guarded([&]() -> int {
+        if (!ctx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_submit(ctx, bases, 0, offsets, nullptr, n, out);
+    });
 }
 
 int mq_ctx_submit_spans(mq_ctx *ctx, const uint8_t *buf, uint64_t buf_bytes, const uint64_t *starts, const uint32_t *lens, uint32_t n,
-                        mq_hit *out) try {
-    if (!ctx || (n && (!buf || !starts || !lens || !out))) return set_err(MQ_EINVAL, "bad arguments");
-    return ctx_submit(ctx, buf, buf_bytes, starts, lens, n, out);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                        mq_hit *out) {
+    return guarded([&]() -> int {
+        if (!ctx || (n && (!buf || !starts || !lens || !out))) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_submit(ctx, buf, buf_bytes, starts, lens, n, out);
+    });
 }
 
-int mq_ctx_reserve(mq_ctx *ctx, uint32_t n_reads, uint64_t total_bytes) try {
-    if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
-    mq_ctx *c = ctx;
-    int rc = use_device(c->idx);
-    if (rc) return rc;
-    if ((rc = grow_pinned(c->h_off, c->h_off_cap, (uint64_t)n_reads + 1))) return rc;
-    if ((rc = grow_pinned(c->h_out, c->h_out_cap, (uint64_t)n_reads))) return rc;
-    if ((rc = ctx_ensure(c, n_reads, total_bytes, list_f16(c->idx)))) return rc;
-    if ((rc = grow(c->st_bases, c->st_bases_cap, total_bytes + 64))) return rc;
-    if ((rc = grow(c->st_off, c->st_off_cap, (uint64_t)n_reads + 1))) return rc;
-    if ((rc = grow(c->st_out, c->st_out_cap, (uint64_t)n_reads))) return rc;
-    return grow(c->st_lens, c->st_lens_cap, (uint64_t)n_reads);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_reserve(mq_ctx *ctx, uint32_t n_reads, uint64_t total_bytes) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        int rc = use_device(ctx->idx);
+        if (rc) return rc;
+        return ctx_ensure_staging(ctx, n_reads, total_bytes, true);
+    });
 }
 
-int mq_ctx_wait(mq_ctx *ctx) try {
-    if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
-    return ctx_wait(ctx);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_wait(mq_ctx *ctx) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        return ctx_wait(ctx);
+    });
 }
 
-int mq_ctx_map_batch(mq_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) try {
-    if (!ctx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
-    int rc = ctx_submit(ctx, bases, 0, offsets, nullptr, n, out);
-    if (rc) return rc;
-    return ctx_wait(ctx);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_ctx_map_batch(mq_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) {
+    return guarded([&]() -> int {
+        if (!ctx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
+        int rc = ctx_submit(ctx, bases, 0, offsets, nullptr, n, out);
+        if (rc) return rc;
+        return ctx_wait(ctx);
+    });
 }
 
 int mq_ctx_map_batch_device(mq_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases,
-                            mq_hit *d_out, void *stream) try {
-    if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
-    return ctx_map_device(ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                            mq_hit *d_out, void *stream) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        return ctx_map_device(ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
+    });
 }
 
 int mq_map_batch_device(mq_index *idx, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases,
-                        mq_hit *d_out, void *stream) try {
-    if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    return ctx_map_device(idx->def_ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                        mq_hit *d_out, void *stream) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_map_device(idx->def_ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
+    });
 }
 
-int mq_map_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) try {
-    if (!idx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
-    std::lock_guard<std::mutex> lk(idx->mu);
-    int rc = ctx_submit(idx->def_ctx, bases, 0, offsets, nullptr, n, out);
-    if (rc) return rc;
-    return ctx_wait(idx->def_ctx);
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_map_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) {
+    return guarded([&]() -> int {
+        if (!idx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        int rc = ctx_submit(idx->def_ctx, bases, 0, offsets, nullptr, n, out);
+        if (rc) return rc;
+        return ctx_wait(idx->def_ctx);
+    });
 }
 
 int mq_kminmers_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, const uint64_t *kmm_offsets,
-                      mq_kminmer *out, uint32_t *counts) try {
-    if (!idx || (n && (!offsets || !kmm_offsets || !counts))) return set_err(MQ_EINVAL, "bad arguments");
-    if (n == 0) return MQ_OK;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    int rc = use_device(idx);
-    if (rc) return rc;
-    const uint64_t total = offsets[n] - offsets[0];
-    const uint64_t ktotal = kmm_offsets[n] - kmm_offsets[0];
-    for (uint32_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= (1ull << 32)) return set_err(MQ_EINVAL, "bad offsets / sequence length must be < 2^32");
-    // parity/debug entry point: list regions sized for the worst case (one minimizer per base), so no sequence overflows
-    rc = ctx_ensure(idx->def_ctx, n, total, 65536u);
-    if (rc) return rc;
-    uint8_t *d_b = nullptr;
-    uint64_t *d_o = nullptr, *d_ko = nullptr;
-    mq_kminmer *d_k = nullptr;
-    uint32_t *d_c = nullptr;
-    mq_hit *d_h = nullptr;
-    uint64_t *d_zero_lens = nullptr;
-    auto cleanup = [&]() {
-        hipFree(d_b); hipFree(d_o); hipFree(d_ko); hipFree(d_k); hipFree(d_c); hipFree(d_h); hipFree(d_zero_lens);
-    };
-    std::vector<uint64_t> rel((size_t)n + 1), krel((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) {
-        rel[i] = offsets[i] - offsets[0];
-        krel[i] = kmm_offsets[i] - kmm_offsets[0];
-    }
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t x) { if (e == hipSuccess) e = x; return e == hipSuccess; };
-    ok(hipMalloc((void **)&d_b, total + 1));
-    ok(hipMalloc((void **)&d_o, ((size_t)n + 1) * 8));
-    ok(hipMalloc((void **)&d_ko, ((size_t)n + 1) * 8));
-    ok(hipMalloc((void **)&d_k, (ktotal + 1) * sizeof(mq_kminmer)));
-    ok(hipMalloc((void **)&d_c, (size_t)n * 4));
-    ok(hipMalloc((void **)&d_h, (size_t)n * sizeof(mq_hit)));
-    if (e == hipSuccess && total) ok(hipMemcpy(d_b, bases + offsets[0], total, hipMemcpyHostToDevice));
-    if (e == hipSuccess) ok(hipMemcpy(d_o, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    if (e == hipSuccess) ok(hipMemcpy(d_ko, krel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    if (e != hipSuccess) {
-        cleanup();
-        return set_err(MQ_EHIP, std::string("mq_kminmers_batch setup: ") + hipGetErrorString(e));
-    }
-    // before finalize there is no ref table: the 1-slot empty table never hits, so ref_lens is never read
-    {
-        LaunchOpt o;
-        o.d_dump = d_k;
-        o.d_dump_off = d_ko;
-        o.d_dump_counts = d_c;
-        o.f16 = 65536u;
-        rc = launch_map(idx->def_ctx, d_b, d_o, n, d_h, 0, o);
-    }
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    ok(hipMemcpy(counts, d_c, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (e == hipSuccess && ktotal && out) ok(hipMemcpy(out + kmm_offsets[0], d_k, ktotal * sizeof(mq_kminmer), hipMemcpyDeviceToHost));
-    cleanup();
-    if (e != hipSuccess) return set_err(MQ_EHIP, std::string("mq_kminmers_batch copy-out: ") + hipGetErrorString(e));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+                      mq_kminmer *out, uint32_t *counts) {
+    return guarded([&]() -> int {
+        if (!idx || (n && (!offsets || !kmm_offsets || !counts))) return set_err(MQ_EINVAL, "bad arguments");
+        if (n == 0) return MQ_OK;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        int rc = use_device(idx);
+        if (rc) return rc;
+        const uint64_t total = offsets[n] - offsets[0];
+        const uint64_t ktotal = kmm_offsets[n] - kmm_offsets[0];
+        for (uint32_t i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= (1ull << 32)) return set_err(MQ_EINVAL, "bad offsets / sequence length must be < 2^32");
+        // parity/debug entry point: list regions sized for the worst case (one minimizer per base), so no sequence overflows
+        rc = ctx_ensure(idx->def_ctx, n, total, 65536u);
+        if (rc) return rc;
+        Buf<uint8_t> d_b;
+        Buf<uint64_t> d_o, d_ko;
+        Buf<mq_kminmer> d_k;
+        Buf<uint32_t> d_c;
+        Buf<mq_hit> d_h;
+        std::vector<uint64_t> rel((size_t)n + 1), krel((size_t)n + 1);
+        for (uint32_t i = 0; i <= n; ++i) {
+            rel[i] = offsets[i] - offsets[0];
+            krel[i] = kmm_offsets[i] - kmm_offsets[0];
+        }
+        hipError_t e = hipSuccess;
+        auto ok = [&](hipError_t x) { if (e == hipSuccess) e = x; return e == hipSuccess; };
+        ok(d_b.try_alloc(total + 1));
+        ok(d_o.try_alloc((uint64_t)n + 1));
+        ok(d_ko.try_alloc((uint64_t)n + 1));
+        ok(d_k.try_alloc(ktotal + 1));
+        ok(d_c.try_alloc(n));
+        ok(d_h.try_alloc(n));
+        if (e == hipSuccess && total) ok(hipMemcpy(d_b, bases + offsets[0], total, hipMemcpyHostToDevice));
+        if (e == hipSuccess) ok(hipMemcpy(d_o, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        if (e == hipSuccess) ok(hipMemcpy(d_ko, krel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        if (e != hipSuccess) return set_err(MQ_EHIP, std::string("mq_kminmers_batch setup: ") + hipGetErrorString(e));
+        // before finalize there is no ref table: the 1-slot empty table never hits, so ref_lens is never read
+        {
+            LaunchOpt o;
+            o.d_dump = d_k;
+            o.d_dump_off = d_ko;
+            o.d_dump_counts = d_c;
+            o.f16 = 65536u;
+            rc = launch_map(idx->def_ctx, d_b, d_o, n, d_h, 0, o);
+        }
+        if (rc) return rc;
+        ok(hipMemcpy(counts, d_c, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (e == hipSuccess && ktotal && out) ok(hipMemcpy(out + kmm_offsets[0], d_k, ktotal * sizeof(mq_kminmer), hipMemcpyDeviceToHost));
+        if (e != hipSuccess) return set_err(MQ_EHIP, std::string("mq_kminmers_batch copy-out: ") + hipGetErrorString(e));
+        return MQ_OK;
+    });
 }
 
-int mq_index_lookup(mq_index *idx, const uint64_t *hashes, uint32_t n, uint8_t *found, mq_kminmer *entries, uint32_t *ref_ids) try {
-    if (!idx || (n && (!hashes || !found || !entries || !ref_ids))) return set_err(MQ_EINVAL, "bad arguments");
-    if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
-    if (n == 0) return MQ_OK;
-    std::lock_guard<std::mutex> lk(idx->mu);
-    int rc = use_device(idx);
-    if (rc) return rc;
-    uint64_t *d_k = nullptr;
-    uint8_t *d_f = nullptr;
-    mq_kminmer *d_e = nullptr;
-    uint32_t *d_r = nullptr;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t x) { if (e == hipSuccess) e = x; return e == hipSuccess; };
-    ok(hipMalloc((void **)&d_k, (size_t)n * 8));
-    ok(hipMalloc((void **)&d_f, (size_t)n));
-    ok(hipMalloc((void **)&d_e, (size_t)n * sizeof(mq_kminmer)));
-    ok(hipMalloc((void **)&d_r, (size_t)n * 4));
-    if (e == hipSuccess) ok(hipMemcpy(d_k, hashes, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, idx->table, idx->nslots - 1, d_k, n, d_f, d_e, d_r);
-        ok(hipGetLastError());
-    }
-    if (e == hipSuccess) ok(hipMemcpy(found, d_f, (size_t)n, hipMemcpyDeviceToHost));
-    if (e == hipSuccess) ok(hipMemcpy(entries, d_e, (size_t)n * sizeof(mq_kminmer), hipMemcpyDeviceToHost));
-    if (e == hipSuccess) ok(hipMemcpy(ref_ids, d_r, (size_t)n * 4, hipMemcpyDeviceToHost));
-    hipFree(d_k); hipFree(d_f); hipFree(d_e); hipFree(d_r);
-    if (e != hipSuccess) return set_err(MQ_EHIP, std::string("mq_index_lookup: ") + hipGetErrorString(e));
-    return MQ_OK;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_index_lookup(mq_index *idx, const uint64_t *hashes, uint32_t n, uint8_t *found, mq_kminmer *entries, uint32_t *ref_ids) {
+    return guarded([&]() -> int {
+        if (!idx || (n && (!hashes || !found || !entries || !ref_ids))) return set_err(MQ_EINVAL, "bad arguments");
+        if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
+        if (n == 0) return MQ_OK;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        int rc = use_device(idx);
+        if (rc) return rc;
+        Buf<uint64_t> d_k;
+        Buf<uint8_t> d_f;
+        Buf<mq_kminmer> d_e;
+        Buf<uint32_t> d_r;
+        hipError_t e = hipSuccess;
+        auto ok = [&](hipError_t x) { if (e == hipSuccess) e = x; return e == hipSuccess; };
+        ok(d_k.try_alloc(n));
+        ok(d_f.try_alloc(n));
+        ok(d_e.try_alloc(n));
+        ok(d_r.try_alloc(n));
+        if (e == hipSuccess) ok(hipMemcpy(d_k, hashes, (size_t)n * 8, hipMemcpyHostToDevice));
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, idx->table, idx->nslots - 1, d_k, n, d_f, d_e, d_r);
+            ok(hipGetLastError());
+        }
+        if (e == hipSuccess) ok(hipMemcpy(found, d_f, (size_t)n, hipMemcpyDeviceToHost));
+        if (e == hipSuccess) ok(hipMemcpy(entries, d_e, (size_t)n * sizeof(mq_kminmer), hipMemcpyDeviceToHost));
+        if (e == hipSuccess) ok(hipMemcpy(ref_ids, d_r, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (e != hipSuccess) return set_err(MQ_EHIP, std::string("mq_index_lookup: ") + hipGetErrorString(e));
+        return MQ_OK;
+    });
 }
 
-int mq_format_paf(const mq_index *idx, const char *q_id, uint64_t q_len, const mq_hit *hit, char *buf, size_t cap) try {
-    if (!idx || !q_id || !hit || !buf) return set_err(MQ_EINVAL, "bad arguments");
-    if (hit->status != MQ_HIT_MAPPED) return set_err(MQ_EINVAL, "hit is not mapped: the reference writes no line");
-    auto it = idx->refs.find(hit->ref_id);
-    if (it == idx->refs.end()) return set_err(MQ_EINVAL, "unknown ref_id in hit");
-    const unsigned long long r_len = it->second.second;
-    // src/mers.rs:181: column 11 repeats r_len, column 10 is the score
-    const unsigned long long qs = ((unsigned long long)hit->q_start_hi << 32) | hit->q_start, qe = ((unsigned long long)hit->q_end_hi << 32) | hit->q_end;
-    int w = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%s\t%s\t%llu\t%u\t%u\t%u\t%llu\t%u", q_id, (unsigned long long)q_len, qs, qe,
-                     hit->rc ? "-" : "+", it->second.first.c_str(), r_len, hit->r_start, hit->r_end, hit->score, r_len,
-                     hit->mapq);
-    return w;
-} catch (const std::bad_alloc &) {
-    return set_err(MQ_ENOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return set_err(MQ_EINVAL, std::string("unexpected exception: ") + e.what());
+int mq_format_paf(const mq_index *idx, const char *q_id, uint64_t q_len, const mq_hit *hit, char *buf, size_t cap) {
+    return guarded([&]() -> int {
+        if (!idx || !q_id || !hit || !buf) return set_err(MQ_EINVAL, "bad arguments");
+        if (hit->status != MQ_HIT_MAPPED) return set_err(MQ_EINVAL, "hit is not mapped: the reference writes no line");
+        auto it = idx->refs.find(hit->ref_id);
+        if (it == idx->refs.end()) return set_err(MQ_EINVAL, "unknown ref_id in hit");
+        const unsigned long long r_len = it->second.second;
+        // src/mers.rs:181: column 11 repeats r_len, column 10 is the score
+        const unsigned long long qs = ((unsigned long long)hit->q_start_hi << 32) | hit->q_start, qe = ((unsigned long long)hit->q_end_hi << 32) | hit->q_end;
+        int w = snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%s\t%s\t%llu\t%u\t%u\t%u\t%llu\t%u", q_id, (unsigned long long)q_len, qs, qe,
+                         hit->rc ? "-" : "+", it->second.first.c_str(), r_len, hit->r_start, hit->r_end, hit->score, r_len,
+                         hit->mapq);
+        return w;
+    });
 }
 
 // Page-locked host memory.  hipHostMalloc pins at ~4 GB/s on this platform (and hipHostFree costs another 0.14 s per GB), which

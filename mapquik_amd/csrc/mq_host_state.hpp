@@ -1,25 +1,10 @@
-// mq_host_state.hpp -- host-side state behind the C ABI (part of the one translation unit mq_capi.hip): error text, mq_ctx (a stream slot), mq_index,
-// launch geometry, scratch management.
+// mq_host_state.hpp -- host-side state behind the C ABI (part of the one translation unit mq_capi.hip): mq_ctx (a stream slot) and mq_index, whose
+// buffers are the owning types of mq_host_buf.hpp, the table of map kernels, launch geometry, scratch management.
 #pragma once
 
 // =================================================================== host side
 
 constexpr uint32_t MQ_MAX_REF_ID = 1u << 24;
-static thread_local std::string g_err;
-static int set_err(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-#define HIPCHK(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess) {                                                                                   \
-            char _b[512];                                                                                         \
-            snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-            return set_err(_e == hipErrorOutOfMemory ? MQ_ENOMEM : MQ_EHIP, _b);                                  \
-        }                                                                                                         \
-    } while (0)
-
 struct mq_index;
 
 // One stream slot: everything a map launch sequence writes (work counters, Match scratch, minimizer lists,
@@ -27,44 +12,39 @@ struct mq_index;
 // may be in flight together (the index itself is read-only once finalized); one context runs one sequence at a time.
 struct mq_ctx {
     mq_index *idx = nullptr;
-    hipStream_t stream = nullptr;   // the context's own stream (host-buffer entry points)
-    uint32_t *d_counter = nullptr;  // 64 words: SplitArgs::counters; [8..11] two 64-bit probe statistics of an instrumented launch
-    MatchRec *scratch = nullptr;    // per mapping wave: cap_matches records
-    size_t scratch_waves = 0;       // waves it has windows for
-    unsigned long long *mz_hash = nullptr;
-    uint32_t *mz_pos = nullptr;
-    uint32_t *mz_last = nullptr;    // seeding variant 16 only: every minimizer's second position (allocated with mz_pos, else nullptr)
-    uint64_t mz_cap = 0;            // list entries allocated
-    uint32_t *mz_count = nullptr;
-    uint64_t *mz_base = nullptr;
-    uint32_t *queue = nullptr;
-    uint4 *work = nullptr;          // map_kernel's work items (order_reads_kernel): WORK_FRONT_CAP + reads_cap descriptors
-    uint64_t reads_cap = 0;
-    uint64_t pool_base = 0, pool_cap = 0;  // of the last ctx_ensure: the pool behind the regular list regions
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // (members are destroyed last to first: the buffers, then the events, then the stream; ctx_release synchronises the stream before)
+    ScopedStream stream;            // the context's own stream (host-buffer entry points)
+    ScopedEvent ev0, ev1;
     bool ev_valid = false;
+    Buf<uint32_t> d_counter;        // 64 words: SplitArgs::counters; [8..11] two 64-bit probe statistics of an instrumented launch
+    Buf<MatchRec> scratch;          // per mapping wave: cap_matches records
+    size_t scratch_waves = 0;       // waves it has windows for
+    Buf<unsigned long long> mz_hash;
+    Buf<uint32_t> mz_pos;
+    Buf<uint32_t> mz_last;          // seeding variant 16 only: every minimizer's second position (allocated with mz_pos, else empty)
+    uint64_t mz_cap = 0;            // list entries allocated (the three lists are one group)
+    Buf<uint32_t> mz_count;
+    Buf<uint64_t> mz_base;
+    Buf<uint32_t> queue;
+    Buf<uint4> work;                // map_kernel's work items (order_reads_kernel): WORK_FRONT_CAP + reads_cap descriptors
+    uint64_t reads_cap = 0;         // reads the four per-read arrays above hold (one group)
+    uint64_t pool_base = 0, pool_cap = 0;  // of the last ctx_ensure: the pool behind the regular list regions
     // staging for the host-buffer entry points
-    uint8_t *st_bases = nullptr;
-    uint64_t st_bases_cap = 0;
-    uint64_t *st_off = nullptr;
-    uint64_t st_off_cap = 0;
-    mq_hit *st_out = nullptr;
-    uint64_t st_out_cap = 0;
-    uint32_t *st_lens = nullptr;
-    uint64_t st_lens_cap = 0;
-    uint64_t *h_off = nullptr;      // page-locked: relative offsets on their way to the device
-    uint64_t h_off_cap = 0;
-    mq_hit *h_out = nullptr;        // page-locked: hits on their way back
-    uint64_t h_out_cap = 0;
+    Buf<uint8_t> st_bases;
+    Buf<uint64_t> st_off;
+    Buf<mq_hit> st_out;
+    Buf<uint32_t> st_lens;
+    PinnedBuf<uint64_t> h_off;      // relative offsets on their way to the device
+    PinnedBuf<mq_hit> h_out;        // hits on their way back
     // device-parsed FASTA chunks (mq_ctx_submit_fasta / mq_ctx_wait_fasta): tile counts / offsets, the line ends, the scan's result words
-    uint32_t *fx_tile_counts = nullptr, *fx_tile_off = nullptr;
-    uint64_t fx_tile_counts_cap = 0, fx_tile_off_cap = 0;
-    uint32_t *fx_nl = nullptr, *h_fx_nl = nullptr;
-    uint64_t fx_nl_cap = 0, h_fx_nl_cap = 0;
-    uint32_t *fx_info = nullptr, *h_fx_info = nullptr;  // device / page-locked: lines, records, flags
-    uint8_t *h_fx_tail = nullptr;                       // page-locked, one page: the piece's bytes behind its last page boundary
+    Buf<uint32_t> fx_tile_counts, fx_tile_off;
+    Buf<uint32_t> fx_nl;
+    PinnedBuf<uint32_t> h_fx_nl;
+    Buf<uint32_t> fx_info;          // lines, records, flags
+    PinnedBuf<uint32_t> h_fx_info;
+    PinnedBuf<uint8_t> h_fx_tail;   // one page: the piece's bytes behind its last page boundary
     bool fx_pending = false;
-    uint32_t fx_lpr = 2;                                // lines per record of the piece in flight (FASTA 2, FASTQ 4)
+    uint32_t fx_lpr = 2;            // lines per record of the piece in flight (FASTA 2, FASTQ 4)
     const uint8_t *fx_buf = nullptr;
     uint32_t fx_begin = 0, fx_bytes = 0;
     // a submitted, not yet waited-for batch
@@ -77,8 +57,21 @@ struct mq_ctx {
 };
 
 struct KmmChunk {
-    RefKmm *d = nullptr;
-    uint64_t n = 0, cap = 0;  // k-min-mers of several references share a chunk (assemblies with 10^5 small contigs)
+    Buf<RefKmm> d;   // d.cap k-min-mers of room
+    uint64_t n = 0;  // k-min-mers of several references share a chunk (assemblies with 10^5 small contigs)
+};
+
+// grow-only scratch of mq_index_add_ref (freed by finalize): no allocation per reference once it has grown
+struct BuildScratch {
+    Buf<uint8_t> seq;
+    Buf<unsigned long long> seg_hash;  // per-segment minimizer lists
+    Buf<uint32_t> seg_pos;
+    Buf<unsigned long long> dense_hash;  // the reference's dense list
+    Buf<uint32_t> dense_pos;
+    Buf<uint32_t> seg_last, dense_last;  // seeding variant 16 only
+    Buf<uint32_t> counts, queue;
+    Buf<unsigned long long> seg_off;
+    Buf<unsigned long long> info;  // [0] total minimizers, [1] overflow flag, [2..3] seed_ref_kernel's work counters
 };
 
 struct mq_index {
@@ -94,22 +87,11 @@ struct mq_index {
     uint64_t n_kmm_total = 0;
     bool finalized = false;
     uint32_t table_factor = 0;  // mq_index_set_table_factor: slots per inserted k-min-mer (0: the default, 8)
-    Bucket *table = nullptr;  // nslots / 2 buckets + the extra bucket of the key 0
+    Buf<Bucket> table;  // nslots / 2 buckets + the extra bucket of the key 0
     uint64_t nslots = 0;
-    uint64_t *d_ref_lens = nullptr;
+    Buf<uint64_t> d_ref_lens;
     uint64_t n_unique = 0, n_keys = 0;
-    // grow-only scratch of mq_index_add_ref (freed by finalize): no allocation per reference once it has grown
-    uint8_t *bld_seq = nullptr;
-    uint64_t bld_seq_cap = 0;
-    unsigned long long *bld_seg_hash = nullptr, *bld_dense_hash = nullptr;  // per-segment minimizer lists, the reference's dense list
-    uint32_t *bld_seg_pos = nullptr, *bld_dense_pos = nullptr;
-    uint32_t *bld_seg_last = nullptr, *bld_dense_last = nullptr;  // seeding variant 16 only
-    uint64_t bld_seg_hash_cap = 0, bld_seg_pos_cap = 0, bld_dense_hash_cap = 0, bld_dense_pos_cap = 0, bld_seg_last_cap = 0, bld_dense_last_cap = 0;
-    uint32_t *bld_counts = nullptr, *bld_queue = nullptr;
-    uint64_t bld_counts_cap = 0, bld_queue_cap = 0;
-    unsigned long long *bld_seg_off = nullptr;
-    uint64_t bld_seg_off_cap = 0;
-    unsigned long long *bld_info = nullptr;  // device: [0] total minimizers, [1] overflow flag, [2..3] seed_ref_kernel's work counters
+    BuildScratch bld;
     int grid_ref = 0;                        // workgroups of seed_ref_kernel that stay resident
     // launch geometry (workgroups) and scratch sizes, fixed at the first map call
     uint32_t grid_fused = 0, grid_seed = 0, grid_map = 0;  // map_kernel; seed_reads_kernel, map_lists_kernel (split)
@@ -123,14 +105,14 @@ struct mq_index {
     // mq_index_stage_*: the reference file's bytes on their way to the device piece by piece (a buffer of the file's size, an upload
     // stream, one event per piece); a state of its own behind its own lock, so that pieces keep flowing while a record is being indexed
     std::mutex stg_mu;
-    uint8_t *stg_buf = nullptr;
+    Buf<uint8_t> stg_buf;
     uint64_t stg_bytes = 0;
     hipStream_t stg_stream = nullptr;
     std::vector<hipEvent_t> stg_events;  // ticket t = event t (tickets count from 0)
     uint64_t stg_issued = 0;             // pieces issued so far
     // mq_index_reserve: the table allocated and cleared ahead of time by a thread of its own (finalize adopts it when the size fits)
     std::thread rsv_thread;
-    Bucket *rsv_table = nullptr;
+    Buf<Bucket> rsv_table;
     uint64_t rsv_nslots = 0;
     int rsv_err = 0;                // hipError_t of the background allocation
     double table_alloc_ms = 0;      // what allocating + clearing the table that is in use took (hipMalloc + memset + synchronize), wherever it ran
@@ -224,13 +206,10 @@ static int use_device(const mq_index *idx) {
 static size_t table_bytes_of(uint64_t nslots) { return (size_t)(nslots / 2 + 1) * sizeof(Bucket); }
 
 static int alloc_table(mq_index *idx, uint64_t nslots) {
-    if (idx->table) {
-        HIPCHK(hipFree(idx->table));
-        idx->table = nullptr;
-    }
     if (nslots < 2) nslots = 2;  // whole buckets
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipMalloc((void **)&idx->table, table_bytes_of(nslots)));
+    int rc = idx->table.alloc(table_bytes_of(nslots) / sizeof(Bucket));
+    if (rc) return rc;
     HIPCHK(hipMemset(idx->table, 0, table_bytes_of(nslots)));
     HIPCHK(hipDeviceSynchronize());
     idx->table_alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -238,28 +217,18 @@ static int alloc_table(mq_index *idx, uint64_t nslots) {
     return MQ_OK;
 }
 
-template <class T>
-static int grow(T *&p, uint64_t &cap, uint64_t need) {
-    if (need <= cap) return MQ_OK;
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    uint64_t nc = need + need / 4 + 64;
-    HIPCHK(hipMalloc((void **)&p, nc * sizeof(T)));
-    cap = nc;
-    return MQ_OK;
+// Every instantiation of the fused launch sequence's two kernels, by [seeding variant != 0][instrumented][chain chunk 4]: launch_map picks
+// its pair here and the launch geometry is the minimum over the same entries.  (The instrumented launch is built for chunk 64 only.)
+using MapFn = void (*)(SplitArgs);
+struct MapPair {
+    MapFn map, declined;
+};
+template <int CH, bool TIMING, bool VAR>
+constexpr MapPair map_pair() {
+    return {map_kernel<CH, TIMING, VAR>, map_declined_kernel<CH, TIMING, VAR>};
 }
-template <class T>
-static int grow_pinned(T *&p, uint64_t &cap, uint64_t need) {
-    if (need <= cap) return MQ_OK;
-    if (p) HIPCHK(hipHostFree(p));
-    p = nullptr;
-    cap = 0;
-    uint64_t nc = need + need / 4 + 64;
-    HIPCHK(hipHostMalloc((void **)&p, nc * sizeof(T), hipHostMallocDefault));
-    cap = nc;
-    return MQ_OK;
-}
+static const MapPair MAP_KERNELS[2][2][2] = {{{map_pair<64, false, false>(), map_pair<4, false, false>()}, {map_pair<64, true, false>(), map_pair<64, true, false>()}},
+                                             {{map_pair<64, false, true>(), map_pair<4, false, true>()}, {map_pair<64, true, true>(), map_pair<64, true, true>()}}};
 
 // launch geometry: persistent waves, as many workgroups as stay resident
 static int ensure_geometry_once(mq_index *idx) {
@@ -271,24 +240,18 @@ static int ensure_geometry_once(mq_index *idx) {
         if (oe && atoi(oe) >= 1 && atoi(oe) < occ) occ = atoi(oe);
         return MQ_OK;
     };
-    int occ = 0, rc;
+    int occ = 0, occ_min = INT_MAX, rc;
     // the grid of a launch sequence = the workgroups that are RESIDENT together, for every instantiation launched on it: wave w's first two
     // work items are its own (items w and n_waves + w, among them the heavy reads that go first), so a workgroup that has to wait for a
-    // place would hold them back; the variants' instantiation and map_declined_kernel (more scratch) may fit fewer than map_kernel<64, false>
-    {
-        const void *fns[] = {(const void *)map_kernel<64, false, false>, (const void *)map_kernel<64, false, true>, (const void *)map_kernel<64, true, false>,
-                             (const void *)map_kernel<64, true, true>, (const void *)map_kernel<4, false, false>, (const void *)map_kernel<4, false, true>,
-                             (const void *)map_declined_kernel<64, false, false>, (const void *)map_declined_kernel<64, false, true>,
-                             (const void *)map_declined_kernel<64, true, false>, (const void *)map_declined_kernel<64, true, true>,
-                             (const void *)map_declined_kernel<4, false, false>, (const void *)map_declined_kernel<4, false, true>};
-        int occ_min = 8;
-        for (const void *fn : fns) {
-            if ((rc = occ_of(fn, 64 * MAP_WAVES, occ))) return rc;
-            occ_min = std::min(occ_min, occ);
-        }
-        occ = occ_min;
-    }
-    idx->grid_fused = (uint32_t)(occ * idx->n_cu);
+    // place would hold them back; the variants' instantiation and map_declined_kernel (more scratch) may fit fewer than the product's map_kernel
+    for (const auto &by_variant : MAP_KERNELS)
+        for (const auto &by_instrumented : by_variant)
+            for (const MapPair &kp : by_instrumented)
+                for (const MapFn fn : {kp.map, kp.declined}) {
+                    if ((rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return rc;
+                    occ_min = std::min(occ_min, occ);
+                }
+    idx->grid_fused = (uint32_t)(occ_min * idx->n_cu);
     if ((rc = occ_of((const void *)seed_reads_kernel<0>, 64 * SEED_WAVES, occ))) return rc;
     idx->grid_seed = (uint32_t)(occ * idx->n_cu);
     if ((rc = occ_of((const void *)map_lists_kernel<64, false>, 64 * ML_WAVES, occ))) return rc;
@@ -299,6 +262,9 @@ static int ensure_geometry_once(mq_index *idx) {
     if (idx->cap_matches < 1) idx->cap_matches = 1;
     return MQ_OK;
 }
+
+// workgroups of the fused launch sequence for n reads (ensure_geometry must have succeeded)
+static uint32_t fused_grid(const mq_index *idx, uint32_t n) { return std::min<uint32_t>(idx->grid_fused, (n + MAP_WAVES - 1) / MAP_WAVES); }
 
 static int ensure_geometry(mq_index *idx) {
     std::call_once(idx->geometry_once, [idx] { idx->geometry_rc = ensure_geometry_once(idx); });  // contexts of one index start concurrently
@@ -322,10 +288,10 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
     mq_index *idx = c->idx;
     int rc = ensure_geometry(idx);
     if (rc) return rc;
-    if (!c->d_counter) HIPCHK(hipMalloc((void **)&c->d_counter, 256));
+    if (!c->d_counter && (rc = c->d_counter.alloc(64))) return rc;
     if (!c->ev0) {
-        HIPCHK(hipEventCreate(&c->ev0));
-        HIPCHK(hipEventCreate(&c->ev1));
+        HIPCHK(hipEventCreate(&c->ev0.h));
+        HIPCHK(hipEventCreate(&c->ev1.h));
     }
     {
         // Match scratch: one window per mapping wave THIS batch can employ (a launch never has more workgroups than reads / waves per
@@ -335,28 +301,21 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
         const size_t wpw = (size_t)std::max(MAP_WAVES, ML_WAVES);
         const size_t want = std::min(max_waves, ((size_t)n + wpw - 1) / wpw * wpw + wpw);
         if (want > c->scratch_waves) {
-            if (c->scratch) HIPCHK(hipFree(c->scratch));
-            c->scratch = nullptr;
             c->scratch_waves = 0;
             const size_t nw = std::min(max_waves, want + want / 4);
-            HIPCHK(hipMalloc((void **)&c->scratch, nw * idx->cap_matches * sizeof(MatchRec)));
+            if ((rc = c->scratch.alloc(nw * idx->cap_matches))) return rc;
             c->scratch_waves = nw;
         }
     }
+    // a group shares one capacity: all of it goes before any of it comes back, and a failure leaves the group empty
     if (n > c->reads_cap) {
-        if (c->mz_count) HIPCHK(hipFree(c->mz_count));
-        if (c->mz_base) HIPCHK(hipFree(c->mz_base));
-        if (c->queue) HIPCHK(hipFree(c->queue));
-        if (c->work) HIPCHK(hipFree(c->work));
-        c->mz_count = c->queue = nullptr;
-        c->mz_base = nullptr;
-        c->work = nullptr;
         c->reads_cap = 0;
+        reset_all(c->mz_count, c->mz_base, c->queue, c->work);
         const uint64_t nc = (uint64_t)n + n / 4 + 64;
-        HIPCHK(hipMalloc((void **)&c->mz_count, nc * 4));
-        HIPCHK(hipMalloc((void **)&c->mz_base, nc * 8));
-        HIPCHK(hipMalloc((void **)&c->queue, nc * 4));
-        HIPCHK(hipMalloc((void **)&c->work, (nc + WORK_FRONT_CAP) * sizeof(uint4)));
+        if ((rc = c->mz_count.alloc(nc)) || (rc = c->mz_base.alloc(nc)) || (rc = c->queue.alloc(nc)) || (rc = c->work.alloc(nc + WORK_FRONT_CAP))) {
+            reset_all(c->mz_count, c->mz_base, c->queue, c->work);
+            return rc;
+        }
         c->reads_cap = nc;
     }
     // regular regions, then the pool for lists denser than their region (an eighth of the regular space, at least 1 M entries)
@@ -366,50 +325,22 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
     c->pool_base = regular;
     c->pool_cap = pool;
     if (need > c->mz_cap) {
-        if (c->mz_hash) HIPCHK(hipFree(c->mz_hash));
-        if (c->mz_pos) HIPCHK(hipFree(c->mz_pos));
-        if (c->mz_last) HIPCHK(hipFree(c->mz_last));
-        c->mz_hash = nullptr;
-        c->mz_pos = nullptr;
-        c->mz_last = nullptr;
         c->mz_cap = 0;
+        reset_all(c->mz_hash, c->mz_pos, c->mz_last);
         const uint64_t nc = need + need / 8;
-        HIPCHK(hipMalloc((void **)&c->mz_hash, nc * 8));
-        HIPCHK(hipMalloc((void **)&c->mz_pos, nc * 4));
-        if (idx->dp.variant & MQ_SEEDVAR_END_COMPRESSED) HIPCHK(hipMalloc((void **)&c->mz_last, nc * 4));
+        if ((rc = c->mz_hash.alloc(nc)) || (rc = c->mz_pos.alloc(nc)) || ((idx->dp.variant & MQ_SEEDVAR_END_COMPRESSED) && (rc = c->mz_last.alloc(nc)))) {
+            reset_all(c->mz_hash, c->mz_pos, c->mz_last);
+            return rc;
+        }
         c->mz_cap = nc;
     }
     return MQ_OK;
 }
 
+// (the caller has selected the index's device: the context's buffers, events and stream go with it)
 static void ctx_release(mq_ctx *c) {
     if (!c) return;
     if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->d_counter);
-    hipFree(c->scratch);
-    hipFree(c->mz_hash);
-    hipFree(c->mz_pos);
-    hipFree(c->mz_last);
-    hipFree(c->mz_count);
-    hipFree(c->mz_base);
-    hipFree(c->queue);
-    hipFree(c->work);
-    hipFree(c->st_bases);
-    hipFree(c->st_off);
-    hipFree(c->st_out);
-    hipFree(c->st_lens);
-    hipFree(c->fx_tile_counts);
-    hipFree(c->fx_tile_off);
-    hipFree(c->fx_nl);
-    hipFree(c->fx_info);
-    if (c->h_fx_nl) hipHostFree(c->h_fx_nl);
-    if (c->h_fx_info) hipHostFree(c->h_fx_info);
-    if (c->h_fx_tail) hipHostFree(c->h_fx_tail);
-    if (c->h_off) hipHostFree(c->h_off);
-    if (c->h_out) hipHostFree(c->h_out);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -420,9 +351,9 @@ static mq_ctx *ctx_create(mq_index *idx) {
         return nullptr;
     }
     c->idx = idx;
-    if (hipSetDevice(idx->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(idx->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess) {
         set_err(MQ_EHIP, "hipStreamCreate failed");
-        c->stream = nullptr;
+        c->stream.h = nullptr;
         ctx_release(c);
         return nullptr;
     }
@@ -436,33 +367,23 @@ static void free_stage(mq_index *idx) {
     idx->stg_events.clear();
     if (idx->stg_stream) hipStreamDestroy(idx->stg_stream);
     idx->stg_stream = nullptr;
-    hipFree(idx->stg_buf);
-    idx->stg_buf = nullptr;
+    idx->stg_buf.reset();
     idx->stg_bytes = 0;
     idx->stg_issued = 0;
 }
 
+// ref_map lengths (src/closures.rs:49), dense by ref id
+static uint32_t max_ref_id(const mq_index *idx) { return idx->refs.empty() ? 0 : idx->refs.rbegin()->first; }
+static int upload_ref_lens(mq_index *idx) {
+    std::vector<uint64_t> lens((size_t)max_ref_id(idx) + 1, 0);
+    for (auto &kv : idx->refs) lens[kv.first] = kv.second.second;
+    int rc = idx->d_ref_lens.alloc(lens.size());
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(idx->d_ref_lens, lens.data(), lens.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return MQ_OK;
+}
+
 static void free_build_scratch(mq_index *idx) {
     free_stage(idx);
-    hipFree(idx->bld_seq);
-    hipFree(idx->bld_seg_hash);
-    hipFree(idx->bld_seg_pos);
-    hipFree(idx->bld_dense_hash);
-    hipFree(idx->bld_dense_pos);
-    hipFree(idx->bld_seg_last);
-    hipFree(idx->bld_dense_last);
-    hipFree(idx->bld_counts);
-    hipFree(idx->bld_queue);
-    hipFree(idx->bld_seg_off);
-    hipFree(idx->bld_info);
-    idx->bld_seq = nullptr;
-    idx->bld_seg_hash = idx->bld_dense_hash = nullptr;
-    idx->bld_seg_pos = idx->bld_dense_pos = nullptr;
-    idx->bld_seg_last = idx->bld_dense_last = nullptr;
-    idx->bld_seg_last_cap = idx->bld_dense_last_cap = 0;
-    idx->bld_counts = idx->bld_queue = nullptr;
-    idx->bld_seg_off = nullptr;
-    idx->bld_info = nullptr;
-    idx->bld_seq_cap = idx->bld_seg_hash_cap = idx->bld_seg_pos_cap = idx->bld_dense_hash_cap = idx->bld_dense_pos_cap = 0;
-    idx->bld_counts_cap = idx->bld_queue_cap = idx->bld_seg_off_cap = 0;
+    idx->bld = BuildScratch();
 }
