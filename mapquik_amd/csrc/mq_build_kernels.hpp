@@ -307,13 +307,15 @@ __global__ void pack_slots_kernel(const Bucket *__restrict__ table, uint64_t n_b
     }
 }
 // mq_index_load: saved slots back into an empty table (keys are distinct, so every insertion claims its slot); flags[0] is set
-// when an entry cannot be what mq_index_save wrote (a reference id beyond the file's reference table, a key 0 outside its slot).
+// when an entry cannot be what mq_index_save wrote (a reference id beyond the file's reference table or in a hole of it -- ref_lens, one
+// length per id up to max_id, holds 0 there, and a reference of length 0 owns no k-min-mer --, a key 0 outside its slot).
 __global__ void unpack_slots_kernel(const SavedSlot *__restrict__ in, uint64_t n, Bucket *__restrict__ table, uint64_t mask, uint32_t max_id,
-                                    uint32_t *__restrict__ flags) {
+                                    const uint64_t *__restrict__ ref_lens, uint32_t *__restrict__ flags) {
     uint32_t n_claimed = 0, n_dead = 0;  // not used here: mq_index_load counts the finished table against the file's header
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const SavedSlot v = in[i];
-        if (v.count == 0 || (v.e.id_rc >> 1) > max_id || (v.is_key0 != 0) != (v.key == 0) || v.is_key0 > 1u) {
+        const uint32_t id = v.e.id_rc >> 1;
+        if (v.count == 0 || id > max_id || ref_lens[id] == 0 || (v.is_key0 != 0) != (v.key == 0) || v.is_key0 > 1u) {
             atomicOr(flags, 1u);
             continue;
         }

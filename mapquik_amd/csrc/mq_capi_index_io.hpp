@@ -130,6 +130,9 @@ mq_index *mq_index_load(const char *path, int device) {
         }
         const uint32_t max_id = max_ref_id(idx);
         if (ok && alloc_table(idx, hdr[1]) != MQ_OK) ok = false;
+        // the dense length array goes up BEFORE the scatter: a reference of length 0 cannot own a k-min-mer, so a zero in it marks an
+        // id the file's (possibly sparse) reference table does not have, and the scatter refuses an entry that names one
+        if (ok) ok = upload_ref_lens(idx) == MQ_OK;
         // file -> page-locked buffer -> device -> scatter kernel, by a few threads at once (each its own buffers and stream; the
         // kernels of different chunks insert into the same table with atomics): the file read, not the copy, is what takes time
         const size_t total = (size_t)hdr[3] * sizeof(SavedSlot);
@@ -165,7 +168,7 @@ mq_index *mq_index_load(const char *path, int device) {
                     good = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st) == hipSuccess;
                     const uint64_t ns = n / sizeof(SavedSlot);
                     hipLaunchKernelGGL(unpack_slots_kernel, dim3((uint32_t)std::min<uint64_t>((ns + 255) / 256, 1u << 16)), dim3(256), 0, st,
-                                       (const SavedSlot *)d.p, ns, idx->table, hdr[1] - 1, max_id, d_flags);
+                                       (const SavedSlot *)d.p, ns, idx->table, hdr[1] - 1, max_id, (const uint64_t *)idx->d_ref_lens.p, d_flags);
                     good = good && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
                 }
                 if (!good) bad.store(1);
@@ -205,7 +208,6 @@ mq_index *mq_index_load(const char *path, int device) {
                 why = "corrupt index file (key counts or reference ids disagree with its header): ";
             }
         }
-        if (ok) ok = upload_ref_lens(idx) == MQ_OK;
         d_flags.reset();
         if (!ok) {
             mq_index_free(idx);
