@@ -158,6 +158,16 @@ int mq_index_stage_begin(mq_index *idx, uint64_t total_bytes);
 int mq_index_stage_piece(mq_index *idx, uint64_t at, const uint8_t *src, uint64_t n, uint64_t *ticket);
 int mq_index_stage_done(mq_index *idx, uint64_t ticket, int wait);
 int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name, uint64_t at, uint64_t len, uint64_t after_ticket);
+/* mq_index_add_ref_staged for a record whose sequence is spread over lines: buffer[at, at + bytes) is everything between the
+ * header's line end and the next record's '>' (or the end of the file).  The lines are joined on the device -- the region is split at
+ * every '\n', one trailing '\r' is cut from each piece (the last one, which has no '\n', included), the pieces are concatenated; every
+ * other byte is kept as it is -- and the result is indexed as mq_index_add_ref_device would index it.  *seq_len (may be NULL) receives
+ * the joined length: the reference's length in mq_index_ref_info and in PAF columns 7 / 11.  Returns the k-min-mer count or <0. */
+int64_t mq_index_add_ref_staged_lines(mq_index *idx, uint32_t ref_id, const char *name, uint64_t at, uint64_t bytes,
+                                      uint64_t after_ticket, uint64_t *seq_len);
+/* Parity/debug: the joined bytes themselves, copied to host memory; returns the joined length (out may be NULL when cap == 0: the
+ * length alone), MQ_EINVAL when it exceeds cap (nothing is written then). */
+int64_t mq_index_staged_sequence(mq_index *idx, uint64_t at, uint64_t bytes, uint64_t after_ticket, uint8_t *out, uint64_t cap);
 
 /* DashMap::with_capacity (src/index.rs:83 sizes its map for 39,821,990 k-min-mers at Index::new): a hint that about
  * expected_kminmers k-min-mers will be inserted.  The table is allocated and cleared in the background while the references are

@@ -31,7 +31,7 @@ def hit_column(hits, name):
     return v
 
 # every symbol include/mapquik_hip.h (the seam) and include/mapquik_hip_diag.h (measurement / diagnostics) declare
-EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_params", "mq_index_set_map_params", "mq_index_stage_begin", "mq_index_stage_piece", "mq_index_stage_done", "mq_index_add_ref_staged", "mq_ctx_submit_fasta", "mq_ctx_wait_fasta", "mq_index_reserve", "mq_host_register", "mq_host_unregister",
+EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_params", "mq_index_set_map_params", "mq_index_stage_begin", "mq_index_stage_piece", "mq_index_stage_done", "mq_index_add_ref_staged", "mq_index_add_ref_staged_lines", "mq_index_staged_sequence", "mq_ctx_submit_fasta", "mq_ctx_wait_fasta", "mq_index_reserve", "mq_host_register", "mq_host_unregister",
            "mq_last_error", "mq_abi_version", "mq_device_count", "mq_params_default", "mq_index_new", "mq_index_free",
            "mq_index_add_ref", "mq_index_add_ref_device", "mq_index_finalize", "mq_index_get_stats", "mq_index_ref_info",
            "mq_map_batch", "mq_map_batch_device", "mq_map_reserve", "mq_kminmers_batch", "mq_index_lookup", "mq_format_paf",
@@ -137,6 +137,11 @@ def load_library(path=None):
         L.mq_index_stage_done.argtypes = [vp, u64, C.c_int]
         L.mq_index_add_ref_staged.restype = C.c_int64
         L.mq_index_add_ref_staged.argtypes = [vp, u32, C.c_char_p, u64, u64, u64]
+    if hasattr(L, "mq_index_add_ref_staged_lines"):
+        L.mq_index_add_ref_staged_lines.restype = C.c_int64
+        L.mq_index_add_ref_staged_lines.argtypes = [vp, u32, C.c_char_p, u64, u64, u64, C.POINTER(u64)]
+        L.mq_index_staged_sequence.restype = C.c_int64
+        L.mq_index_staged_sequence.argtypes = [vp, u64, u64, u64, vp, u64]
     L.mq_ctx_reserve.argtypes = [vp, u32, u64]
     L.mq_ctx_map_batch_device.argtypes = [vp, vp, vp, u32, u64, vp, vp]
     L.mq_ctx_last_map_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -319,6 +324,27 @@ class Index:
         if n < 0:
             raise _err(self._L, "mq_index_add_ref_staged")
         return n
+
+    def add_ref_staged_lines(self, ref_idx, name, at, nbytes, after_ticket=None):
+        """add_ref_staged for a line-wrapped record: the staging buffer's [at, at + nbytes) is everything behind the header line; its
+        lines are joined on the device.  Returns (k-min-mer count, joined length)."""
+        t = 0xFFFFFFFFFFFFFFFF if after_ticket is None else int(after_ticket)
+        ln = C.c_uint64()
+        n = self._L.mq_index_add_ref_staged_lines(self._h, ref_idx, name.encode(), int(at), int(nbytes), t, C.byref(ln))
+        if n < 0:
+            raise _err(self._L, "mq_index_add_ref_staged_lines")
+        return n, ln.value
+
+    def staged_sequence(self, at, nbytes, after_ticket=None):
+        """Parity / debug: the joined bytes of the staging buffer's [at, at + nbytes) as a uint8 array."""
+        t = 0xFFFFFFFFFFFFFFFF if after_ticket is None else int(after_ticket)
+        n = self._L.mq_index_staged_sequence(self._h, int(at), int(nbytes), t, None, 0)  # (no buffer: the checks, and the length alone)
+        if n < 0:
+            raise _err(self._L, "mq_index_staged_sequence")
+        out = np.empty(n, dtype=np.uint8)
+        if n and self._L.mq_index_staged_sequence(self._h, int(at), int(nbytes), t, _p(out), n) != n:
+            raise _err(self._L, "mq_index_staged_sequence")
+        return out
 
     def reserve_table(self, expected_kminmers):
         """DashMap::with_capacity (src/index.rs:83): the table for about this many k-min-mers is allocated and cleared in the background."""

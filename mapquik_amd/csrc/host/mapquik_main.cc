@@ -101,6 +101,7 @@ struct Opt {
     int gpus = 1;
     int seeding_variant = 0;  // MQ_SEEDVAR_* bits (include/mapquik_hip.h)
     bool fast_kh = false;     // MQ_FLAG_FAST_KH
+    bool ref_join_device = false;  // --ref-join device: a line-wrapped reference is streamed too, its lines joined on the device
     bool last_pass = true;  // no second pass follows this one
     int table_factor = 2;  // table slots per inserted k-min-mer: this driver is bound by its host side (mq_index_set_table_factor)
     std::string save_index, load_index;  // --save-index / --index: the on-disk index (the reference has none and re-indexes on every run)
@@ -119,7 +120,7 @@ static void usage() {
          "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with)\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with)\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -331,18 +332,22 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
                 if (r < 0) throw Error("mq_index_stage_done: " + last_error());
                 return r == 1;
             };
-            feeder::RefStreamer rs(o.reference, n_parse, hooks);
+            const bool join_dev = o.ref_join_device;  // a record = its header line + everything up to the next '>' at a line start
+            feeder::RefStreamer rs(o.reference, n_parse, hooks, join_dev);
             std::vector<std::string> lines;  // printed once the file's shape is known to be regular (else the loader below prints its own)
             res_streamer_used = true;
             const feeder::RefStreamer::Result res = rs.run([&](size_t k, const std::string &id, uint64_t at, uint64_t len) {
-                const int64_t cnt = mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
+                const auto tr0 = Clock::now();
+                const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
+                                             : mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
                 if (cnt < 0) throw Error("ref_extract: " + last_error());
+                if (g_timeline && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
                 lines.push_back("Indexed reference " + id + ": " + std::to_string(cnt) + " k-min-mers.");  // src/closures.rs:58
             });
             if (!res.irregular) {
                 for (const std::string &ln : lines) puts(ln.c_str());
                 ref_done = true;
-                tl("reference streamed: every record handed to ref_extract");
+                tl(join_dev ? "reference streamed: every record handed to ref_extract (lines joined on the device)" : "reference streamed: every record handed to ref_extract");
             } else {
                 // not one sequence line per record (a line-wrapped FASTA shows in its first block, before anything was indexed): an index
                 // that took records already is dropped, and the file goes through the loader below
@@ -818,6 +823,11 @@ int main(int argc, char **argv) {
         else if (a == "--table-factor") {
             o.table_factor = atoi(val());
             if (o.table_factor < 2 || o.table_factor > 64) { fprintf(stderr, "error: --table-factor wants 2..64\n"); return 2; }
+        }
+        else if (a == "--ref-join") {
+            const std::string v = val();
+            if (v != "device" && v != "host") { fprintf(stderr, "error: --ref-join wants device or host\n"); return 2; }
+            o.ref_join_device = v == "device";
         }
         else if (a == "--save-index") o.save_index = val();
         else if (a == "--index") o.load_index = val();

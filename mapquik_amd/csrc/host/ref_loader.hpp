@@ -237,6 +237,12 @@ class RefLoader {
 // header line only (pread of its few bytes) and never at a base: lower case and CR-LF are the kernels' / the spans' business.
 // Anything else -- sequences over several lines, blank lines, text before the first '>' -- ends the run as `irregular` and the caller
 // falls back to RefLoader (a line-wrapped FASTA shows in its first block, before anything was indexed).
+// join_lines (the driver's --ref-join device): a record is its header line plus every line up to the next line that starts with '>' (or
+// the file's end), and the callback gets that whole region: its lines are joined on the device (mq_index_add_ref_staged_lines).  The
+// block scan then looks for '>' at a line start and for the line end of that header only -- a wrapped file has 200,000 line ends per
+// block -- and the header is still the only text the host reads.  Text before the first '>' other than blank lines is `irregular`.
+// (Blank = '\n' and '\r' only, and the first '>' must follow a '\n' or open the file: "\r>a", or a '\r' and the '>' on either side of a
+// block border, is `irregular` too and goes to the loader.)
 class RefStreamer {
   public:
     struct Hooks {
@@ -252,7 +258,8 @@ class RefStreamer {
     };
     static constexpr uint64_t BLOCK = 16u << 20;
 
-    RefStreamer(const std::string &path, int n_threads, Hooks hooks) : path_(path), n_threads_(n_threads < 1 ? 1 : n_threads), hooks_(std::move(hooks)) {
+    RefStreamer(const std::string &path, int n_threads, Hooks hooks, bool join_lines = false)
+        : path_(path), n_threads_(n_threads < 1 ? 1 : n_threads), hooks_(std::move(hooks)), join_lines_(join_lines) {
         fd_ = open(path.c_str(), O_RDONLY);
         if (fd_ < 0) throw std::runtime_error("Error opening compressed file: " + path);  // get_reader's message (src/main.rs:62)
         struct stat st;
@@ -268,6 +275,7 @@ class RefStreamer {
     uint64_t file_bytes() const { return size_; }
 
     // fn(record number, id, offset of the sequence in the file = in the staging buffer, length), in file order, from a thread of its own
+    // (join_lines: offset and length of the region behind the header line, line ends and all)
     template <class F>
     Result run(F fn) {
         Result res;
@@ -315,7 +323,8 @@ class RefStreamer {
                         if (r <= 0) throw std::runtime_error("read error: " + path_);
                         got += (uint64_t)r;
                     }
-                    scan_block(sc, lo);
+                    if (join_lines_) scan_block_headers(sc, lo);
+                    else scan_block(sc, lo);
                     {
                         std::lock_guard<std::mutex> lk(mu);
                         scanned.push_back(std::move(sc));
@@ -392,6 +401,30 @@ class RefStreamer {
         };
         // a line [line_start, nl) ends (at its '\n', or at the file's end); cr: a '\r' in front of the line end.  Lines alternate: header
         // ('>' first), sequence (anything else first, or empty).  false: the file is not of that shape.
+        // a record goes to the indexer: header line [hs, he) without its line end, sequence (join_lines: region) [at, at + len)
+        auto hand_over = [&](uint64_t hs, uint64_t he, uint64_t at, uint64_t len) {
+            Rec r;
+            r.at = at;
+            r.len = len;
+            // seq_io's id(): the header up to its first space -- the only bytes of the file the host reads
+            const uint64_t hl = he - hs;
+            std::string h((size_t)hl, '\0');
+            uint64_t got = 0;
+            while (got < hl) {
+                const ssize_t q = pread(fd_, &h[(size_t)got], (size_t)(hl - got), (off_t)(hs + got));
+                if (q <= 0) throw std::runtime_error("read error: " + path_);
+                got += (uint64_t)q;
+            }
+            size_t ie = 1;
+            while (ie < h.size() && h[ie] != ' ') ++ie;
+            r.id = h.substr(1, ie - 1);
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                to_index.push_back(std::move(r));
+            }
+            ++res.records;
+            cv.notify_all();
+        };
         auto end_line = [&](uint64_t nl, bool cr) -> bool {
             const uint64_t ls = line_start, le = (cr && nl > ls) ? nl - 1 : nl;
             const bool starts_gt = ls < nl && cur_first == '>';
@@ -406,29 +439,40 @@ class RefStreamer {
             }
             if (starts_gt) return false;  // a header without its sequence line
             have_header = false;
-            Rec r;
-            r.at = ls;
-            r.len = le - ls;
-            if (r.len >= (1ull << 32)) throw std::runtime_error("sequence length must be < 2^32");
-            // seq_io's id(): the header up to its first space -- the only bytes of the file the host reads
-            const uint64_t hl = hdr_end - hdr_start;
-            std::string h((size_t)hl, '\0');
-            uint64_t got = 0;
-            while (got < hl) {
-                const ssize_t q = pread(fd_, &h[(size_t)got], (size_t)(hl - got), (off_t)(hdr_start + got));
-                if (q <= 0) throw std::runtime_error("read error: " + path_);
-                got += (uint64_t)q;
-            }
-            size_t ie = 1;
-            while (ie < h.size() && h[ie] != ' ') ++ie;
-            r.id = h.substr(1, ie - 1);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                to_index.push_back(std::move(r));
-            }
-            ++res.records;
-            cv.notify_all();
+            if (le - ls >= (1ull << 32)) throw std::runtime_error("sequence length must be < 2^32");
+            hand_over(hdr_start, hdr_end, ls, le - ls);
             return true;
+        };
+        // join_lines: the record in the making -- its header line [cur_hs, cur_he) ('\n' at cur_he; NONE: not seen yet, it lies in a later
+        // block), cur_cr: a '\r' in front of that line end
+        bool open = false, seen_header = false;
+        uint64_t cur_hs = 0, cur_he = NONE;
+        bool cur_cr = false;
+        auto close_record = [&](uint64_t region_end) {
+            const uint64_t he = cur_he == NONE ? size_ : cur_he;  // (a file that ends inside a header line)
+            const bool cr = cur_he == NONE ? (size_ > 0 && prev_last == '\r') : cur_cr;
+            const uint64_t at = std::min<uint64_t>(he + 1, region_end);
+            hand_over(cur_hs, (cr && he > cur_hs + 1) ? he - 1 : he, at, region_end - at);
+            open = false;
+        };
+        auto headers_of = [&](const Scan &s) -> bool {
+            const uint64_t lo = (uint64_t)s.block * BLOCK;
+            if (open && cur_he == NONE && s.first_nl != NONE) {  // the header that began in an earlier block ends here
+                cur_he = s.first_nl;
+                cur_cr = s.first_nl == lo ? prev_last == '\r' : s.first_nl_cr != 0;
+            }
+            bool first = true;
+            for (const Hdr &h : s.hdrs) {
+                if (h.pos == lo && lo > 0 && prev_last != '\n') continue;  // a '>' that opens the block but not a line
+                if (first && !seen_header && s.lead_blank < h.pos - lo) return false;  // text before the first '>'
+                first = false;
+                if (open) close_record(h.pos);
+                open = seen_header = true;
+                cur_hs = h.pos;
+                cur_he = h.nl;
+                cur_cr = h.cr != 0;
+            }
+            return !(first && !seen_header && s.lead_blank < s.n);
         };
         try {
             while (issued < n_blocks && !res.irregular) {
@@ -462,6 +506,13 @@ class RefStreamer {
                 for (auto it = held.find(next_in_order); it != held.end() && !res.irregular; it = held.find(next_in_order)) {
                     const Scan &s = it->second;
                     const uint64_t lo = (uint64_t)s.block * BLOCK;
+                    if (join_lines_) {
+                        if (!headers_of(s)) res.irregular = true;
+                        if (s.n) prev_last = s.last_byte;
+                        held.erase(it);
+                        ++next_in_order;
+                        continue;
+                    }
                     if (s.too_many) res.irregular = true;  // a block full of line ends: a line-wrapped FASTA (or very many tiny records): the host parser's case
                     if (cur_first < 0 && s.n) cur_first = s.first_byte;  // the line that opens this block
                     for (size_t k = 0; k < s.nl.size() && !res.irregular; ++k) {
@@ -475,7 +526,10 @@ class RefStreamer {
                     ++next_in_order;
                 }
             }
-            if (!res.irregular && !stop) {
+            if (!res.irregular && !stop && join_lines_) {
+                if (open) close_record(size_);
+                if (res.records == 0) res.irregular = true;  // (an empty or all-blank file: the host parser says what it is)
+            } else if (!res.irregular && !stop) {
                 if (line_start < size_ && !end_line(size_, false)) res.irregular = true;  // the file's last line has no '\n'
                 if (have_header) res.irregular = true;                                    // a header without its sequence line
                 if (res.records == 0) res.irregular = true;                               // (an empty file: the host parser says what it is)
@@ -509,6 +563,12 @@ class RefStreamer {
         uint8_t next_known;   // the byte behind it lies in this block ...
         uint8_t next;         // ... and is this one: the first byte of the next line
     };
+    static constexpr uint64_t NONE = ~(uint64_t)0;
+    struct Hdr {
+        uint64_t pos;  // file offset of a '>' at a line start (at a block's first byte: whether a line starts there is known later)
+        uint64_t nl;   // file offset of the '\n' that ends that line; NONE: it lies in a later block
+        uint8_t cr;    // a '\r' in front of it
+    };
     struct Scan {
         size_t block = 0;
         uint8_t *chunk = nullptr;
@@ -516,6 +576,11 @@ class RefStreamer {
         std::vector<NL> nl;
         bool too_many = false;
         uint8_t last_byte = 0, first_byte = 0;
+        // join_lines: the header lines that start in the block, the block's first '\n' (it ends a header that began earlier) and the
+        // number of blank bytes ('\n', '\r') the block opens with (all of the file in front of its first '>' must be)
+        std::vector<Hdr> hdrs;
+        uint64_t first_nl = NONE, lead_blank = 0;
+        uint8_t first_nl_cr = 0;
     };
     static constexpr size_t MAX_LINES_PER_BLOCK = 65536;  // single-line records of >= 512 bytes on average; beyond: the host parser's case
 
@@ -542,9 +607,41 @@ class RefStreamer {
         }
     }
 
+    void scan_block_headers(Scan &sc, uint64_t lo) const {
+        const uint8_t *c = sc.chunk;
+        const size_t n = (size_t)sc.n;
+        if (!n) return;
+        sc.first_byte = c[0];
+        sc.last_byte = c[n - 1];
+        size_t b = 0;
+        while (b < n && (c[b] == '\n' || c[b] == '\r')) ++b;
+        sc.lead_blank = b;
+        if (const uint8_t *q = (const uint8_t *)memchr(c, '\n', n)) {
+            sc.first_nl = lo + (uint64_t)(q - c);
+            sc.first_nl_cr = (q > c && q[-1] == '\r') ? 1 : 0;
+        }
+        for (size_t p = 0; p < n;) {
+            const uint8_t *q = (const uint8_t *)memchr(c + p, '>', n - p);
+            if (!q) break;
+            const size_t o = (size_t)(q - c);
+            if (o && c[o - 1] != '\n') {
+                p = o + 1;
+                continue;
+            }
+            const uint8_t *e = (const uint8_t *)memchr(q, '\n', n - o);
+            Hdr h;
+            h.pos = lo + o;
+            h.nl = e ? lo + (uint64_t)(e - c) : NONE;
+            h.cr = (e && e[-1] == '\r') ? 1 : 0;
+            sc.hdrs.push_back(h);
+            p = e ? (size_t)(e - c) + 1 : n;
+        }
+    }
+
     std::string path_;
     int n_threads_;
     Hooks hooks_;
+    bool join_lines_ = false;
     int fd_ = -1;
     uint64_t size_ = 0;
     std::vector<void *> all_chunks_;

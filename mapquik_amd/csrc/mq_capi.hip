@@ -25,6 +25,7 @@
 #include "mq_device.hpp"
 #include "mq_seed.hpp"
 #include "mq_fastx.hpp"
+#include "mq_join.hpp"
 
 using namespace mq;
 

@@ -304,6 +304,90 @@ int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name
     });
 }
 
+// ---- records whose sequence is spread over lines (every genome FASTA of an archive is wrapped at 60-80 columns): the region between
+// the header's line end and the next record's '>' is joined on the device (mq_join.hpp) into bld.seq -- not in place: tiles of one launch
+// would race, and the staging buffer still holds the header of the next record -- and indexed from there.
+
+// the state, range and ticket checks of mq_index_add_ref_staged, and the null stream made to wait for the pieces; *d_region: buffer + at
+static int staged_region(mq_index *idx, const char *who, uint64_t at, uint64_t bytes, uint64_t after_ticket, const uint8_t **d_region) {
+    std::lock_guard<std::mutex> lk(idx->stg_mu);
+    if (!idx->stg_buf) return set_err(MQ_ESTATE, std::string(who) + " before mq_index_stage_begin");
+    if (at > idx->stg_bytes || bytes > idx->stg_bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
+    if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
+    const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? idx->stg_issued : after_ticket + 1;
+    if (upto) HIPCHK(hipStreamWaitEvent(0, idx->stg_events[(size_t)upto - 1], 0));
+    *d_region = idx->stg_buf + at;
+    return MQ_OK;
+}
+
+// The lines of d_region[0, bytes) joined into bld.seq, on the null stream (behind the previous record's build kernels, which read
+// bld.seq); *joined: the joined length, read back once the last kernel is queued.  d_region lies `at` bytes into the staging buffer,
+// whose base is 16-byte aligned and which has 64 bytes of slack behind it.
+static int join_lines_locked(mq_index *idx, const uint8_t *d_region, uint64_t at, uint64_t bytes, uint64_t *joined) {
+    int rc;
+    *joined = 0;
+    if ((rc = idx->bld.seq.ensure(bytes + 64))) return rc;
+    if (!bytes) return MQ_OK;
+    const uint8_t *base = d_region - at;
+    const uint64_t begin = at, end = at + bytes;
+    const uint64_t tiles = (end - (begin & ~15ull) + FX_TILE - 1) / FX_TILE;
+    if (tiles >= (1ull << 32)) return set_err(MQ_EINVAL, "region too large");
+    const uint32_t n_tiles = (uint32_t)tiles;
+    if ((rc = idx->bld.join_counts.ensure(n_tiles))) return rc;
+    if ((rc = idx->bld.join_off.ensure(n_tiles))) return rc;
+    if (!idx->bld.join_total && (rc = idx->bld.join_total.alloc(1))) return rc;
+    const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((n_tiles + 3) / 4, (uint32_t)idx->n_cu * 8u));
+    hipLaunchKernelGGL(join_count_kernel, dim3(grid), dim3(256), 0, 0, base, begin, end, n_tiles, idx->bld.join_counts);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(join_scan_kernel, dim3(1), dim3(1024), 0, 0, idx->bld.join_counts, n_tiles, idx->bld.join_off, idx->bld.join_total);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(join_write_kernel, dim3(grid), dim3(256), 0, 0, base, begin, end, n_tiles, idx->bld.join_off, idx->bld.seq);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpy(&total, idx->bld.join_total, 8, hipMemcpyDeviceToHost));
+    *joined = total;
+    return MQ_OK;
+}
+
+int64_t mq_index_add_ref_staged_lines(mq_index *idx, uint32_t ref_id, const char *name, uint64_t at, uint64_t bytes, uint64_t after_ticket, uint64_t *seq_len) {
+    return guarded([&]() -> int64_t {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        const uint8_t *d_region = nullptr;
+        if ((rc = staged_region(idx, "mq_index_add_ref_staged_lines", at, bytes, after_ticket, &d_region))) return rc;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        // (what add_ref_device_locked would refuse is refused before the join: nothing is registered, nothing is overwritten)
+        if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
+        if (ref_id >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, "ref_id must be < 2^24 (reference lengths are kept in a dense device array)");
+        if (idx->refs.count(ref_id)) return set_err(MQ_EINVAL, "duplicate ref_id");
+        uint64_t joined = 0;
+        if ((rc = join_lines_locked(idx, d_region, at, bytes, &joined))) return rc;
+        if (joined >= (1ull << 32)) return set_err(MQ_EINVAL, "sequence length must be < 2^32");
+        if (seq_len) *seq_len = joined;
+        return add_ref_device_locked(idx, ref_id, name, idx->bld.seq, joined);
+    });
+}
+
+int64_t mq_index_staged_sequence(mq_index *idx, uint64_t at, uint64_t bytes, uint64_t after_ticket, uint8_t *out, uint64_t cap) {
+    return guarded([&]() -> int64_t {
+        if (!idx || (!out && cap)) return set_err(MQ_EINVAL, "bad arguments");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        const uint8_t *d_region = nullptr;
+        if ((rc = staged_region(idx, "mq_index_staged_sequence", at, bytes, after_ticket, &d_region))) return rc;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
+        uint64_t joined = 0;
+        if ((rc = join_lines_locked(idx, d_region, at, bytes, &joined))) return rc;
+        if (joined > (uint64_t)INT64_MAX) return set_err(MQ_EINVAL, "region too large");
+        if (!out) return (int64_t)joined;  // (cap == 0: the length alone)
+        if (joined > cap) return set_err(MQ_EINVAL, "mq_index_staged_sequence: the joined sequence is longer than cap");
+        if (joined) HIPCHK(hipMemcpy(out, idx->bld.seq, joined, hipMemcpyDeviceToHost));
+        return (int64_t)joined;
+    });
+}
+
 // Slots of the table per inserted k-min-mer (rounded up to a power of two of slots).  The default, 8 (load <= 1/8: 17 GB for a human
 // genome), is for a kernel fed from HBM: 1130 Gbases/s against 1114 / 1074 at 4 / 2.  A caller that feeds from files is bound by its
 // host side at a thirtieth of that and does better with 2: a quarter of the memory per replica, of the device-to-device copy per clone,

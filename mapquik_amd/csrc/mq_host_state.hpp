@@ -72,6 +72,9 @@ struct BuildScratch {
     Buf<uint32_t> counts, queue;
     Buf<unsigned long long> seg_off;
     Buf<unsigned long long> info;  // [0] total minimizers, [1] overflow flag, [2..3] seed_ref_kernel's work counters
+    // mq_index_add_ref_staged_lines: kept bytes per tile of the region, their exclusive scan, [0] the joined length (mq_join.hpp)
+    Buf<uint32_t> join_counts;
+    Buf<unsigned long long> join_off, join_total;
 };
 
 struct mq_index {
