@@ -519,11 +519,7 @@ class Feeder {
                     uint64_t sl = e2 - s;
                     if (sl && c->buf[s + sl - 1] == '\r') --sl;
                     if (sl >= (1ull << 32)) throw FeederError("sequence length must be < 2^32");
-                    uint64_t h1 = e1;
-                    if (h1 > w + 1 && c->buf[h1 - 1] == '\r') --h1;
-                    uint64_t ie = w + 1;
-                    while (ie < h1 && c->buf[ie] != ' ') ++ie;  // seq_io's id(): up to the first space
-                    c->ids.push_back({w + 1, (uint32_t)(ie - (w + 1))});
+                    c->ids.push_back({w + 1, (uint32_t)fasta_id(c->buf + w, e1 - w)});
                     c->starts.push_back(s);
                     c->lens.push_back((uint32_t)sl);
                     // '+' line: its end is in the surplus of the read more often than not; then a quality line as long as the sequence

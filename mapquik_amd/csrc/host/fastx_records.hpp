@@ -4,6 +4,7 @@
 #pragma once
 #include <dlfcn.h>
 #include <sys/mman.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdint>
@@ -73,6 +74,27 @@ struct FeederError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
 
+// ---------------------------------------------------------------- two chores of every reader of these files
+// exactly n bytes of the file at off into dst
+inline void pread_full(int fd, void *dst, uint64_t n, uint64_t off, const std::string &path) {
+    uint64_t got = 0;
+    while (got < n) {
+        const ssize_t r = pread(fd, (uint8_t *)dst + got, n - got, (off_t)(off + got));
+        if (r <= 0) throw std::runtime_error("read error: " + path);
+        got += (uint64_t)r;
+    }
+}
+
+// seq_io's id() of the header line [line, line + len) (its '>' or '@' first, its '\n' not part of it): the bytes behind the first one up
+// to the first SPACE (a TAB is part of the id).  CR-LF files: one trailing '\r' is not part of a line longer than its first byte
+// (cr_cut: the caller has taken it off already).  Returns the id's length; the id starts at line + 1.
+inline uint64_t fasta_id(const uint8_t *line, uint64_t len, bool cr_cut = false) {
+    if (!cr_cut && len > 1 && line[len - 1] == '\r') --len;
+    uint64_t e = 1;
+    while (e < len && line[e] != ' ') ++e;
+    return e - 1;
+}
+
 // ---------------------------------------------------------------- record boundaries
 constexpr uint64_t NEED_MORE = ~0ull;
 
@@ -130,16 +152,13 @@ inline void spans_from_line_ends(Chunk &c, const uint32_t *line_ends, uint32_t n
     c.ids.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t hs = i ? (uint64_t)line_ends[lpr * i - 1] + 1 : c.begin;
-        uint64_t he = line_ends[lpr * i];
+        const uint64_t he = line_ends[lpr * i];
         const uint64_t ss = he + 1;
         uint64_t se = line_ends[lpr * i + 1];
         if (se > ss && b[se - 1] == '\r') --se;
-        if (he > hs + 1 && b[he - 1] == '\r') --he;
-        uint64_t s = hs + 1, e = s;  // seq_io's id(): the header line up to its first SPACE
-        while (e < he && b[e] != ' ') ++e;
         c.starts[i] = ss;
         c.lens[i] = (uint32_t)(se - ss);
-        c.ids[i] = {s, (uint32_t)(e - s)};
+        c.ids[i] = {hs + 1, (uint32_t)fasta_id(b + hs, he - hs)};
     }
 }
 
@@ -152,12 +171,7 @@ inline void parse_chunk(Chunk &c, bool fastq) {
         const uint8_t *e = (const uint8_t *)memchr(b + from, '\n', end - from);
         return e ? (uint64_t)(e - b) : end;
     };
-    auto add_id = [&](uint64_t h0, uint64_t h1) {  // seq_io's id(): the header line up to its first SPACE (a TAB is part of the id)
-        if (h1 > h0 + 1 && b[h1 - 1] == '\r') --h1;  // CR-LF files: the CR is not part of the line
-        uint64_t s = h0 + 1, e = s;
-        while (e < h1 && b[e] != ' ') ++e;
-        c.ids.push_back({s, (uint32_t)(e - s)});
-    };
+    auto add_id = [&](uint64_t h0, uint64_t h1) { c.ids.push_back({h0 + 1, (uint32_t)fasta_id(b + h0, h1 - h0)}); };
     while (p < end) {
         if (b[p] == '\n' || b[p] == '\r') { ++p; continue; }
         if (fastq) {

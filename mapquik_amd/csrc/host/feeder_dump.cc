@@ -1,6 +1,10 @@
 // feeder_dump -- test tool for fastx_feeder.hpp (no GPU needed: chunk buffers come from malloc).
 // usage: feeder_dump <file> <fasta|fastq|ref> <chunk_bytes> <threads>   -> one line per read, in input order: id TAB length TAB sequence
 //        (ref: through the reference loader, ref_loader.hpp; FEEDER_DUMP_QUIET=1 prints only "records bases" -- for timing)
+//        feeder_dump <file> <refstream|refstream-lines> <block_bytes> <threads> -> the reference streamer (ref_loader.hpp: one sequence
+//        line per record | a record's lines joined later) with malloc'ed chunks and a link that is always done: one line per record,
+//        id TAB offset TAB length, or the one word "irregular".  block_bytes 0: every block size from 1 to the file's size + 1, each
+//        result behind a line "block <b>"
 //        feeder_dump <file.gz> inflate <segment_bytes> <threads>        -> the inflated bytes of all members (par_gzip.hpp alone);
 //        stderr: "rounds R max_chain C" (FEEDER_DUMP_QUIET=1: no bytes, "bytes seconds" on stdout)
 #include <cstdio>
@@ -44,6 +48,29 @@ int main(int argc, char **argv) {
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (getenv("FEEDER_DUMP_QUIET")) printf("%llu %.4f\n", (unsigned long long)total, dt);
             else fwrite(out.p, 1, total, stdout);
+            return 0;
+        }
+        if (std::string(argv[2]) == "refstream" || std::string(argv[2]) == "refstream-lines") {
+            const bool lines = std::string(argv[2]) == "refstream-lines";
+            struct stat st;
+            if (stat(argv[1], &st) != 0) throw std::runtime_error("cannot open");
+            const uint64_t one = strtoull(argv[3], nullptr, 10);
+            for (uint64_t b = one ? one : 1; b <= (one ? one : (uint64_t)st.st_size + 1); ++b) {
+                RefStreamer::Hooks hooks;
+                hooks.alloc = [](size_t n) { return malloc(n); };
+                hooks.release = [](void *q) { free(q); };
+                uint64_t tickets = 0;
+                hooks.piece = [&tickets](uint64_t, const uint8_t *, uint64_t) { return tickets++; };
+                hooks.done = [](uint64_t, bool) { return true; };
+                RefStreamer rs(argv[1], atoi(argv[4]), hooks, lines, b);
+                std::string out;
+                const RefStreamer::Result res = rs.run([&](size_t, const std::string &id, uint64_t at, uint64_t len) {
+                    out += id + "\t" + std::to_string(at) + "\t" + std::to_string(len) + "\n";
+                });
+                if (!one) printf("block %llu\n", (unsigned long long)b);
+                // (what was handed over before a file was found irregular depends on the threads' timing: not printed)
+                fputs(res.irregular ? "irregular\n" : out.c_str(), stdout);
+            }
             return 0;
         }
         if (std::string(argv[2]) == "ref") {

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -137,6 +138,206 @@ static void print_totals(Clock::time_point start) {
     printf("Maximum RSS: %sGB\n", strchr(fb, '.') || strchr(fb, 'e') ? fb : (std::string(fb) + ".0").c_str());  // src/main.rs:271
 }
 
+// ---------------------------------------------------------------- the reference phase: one function per route (run_pass decides which)
+// what the routes share
+struct RefPhase {
+    const Opt &o;
+    const Params &P;
+    std::unique_ptr<Index> &index;  // the index being built (run_pass replaces it when the streamer gives a file back late)
+    int n_parse;                    // host threads
+    const std::function<void()> &start_feed;  // starts the read feeder (once)
+    bool prefetch;                  // MQ_DRIVER_PREFETCH: the read feeder starts while the reference is still being indexed
+};
+
+// --index: the finalized table from a file written by --save-index (occupied slots only; validated against its header on load)
+static std::unique_ptr<ReadOnlyIndex> load_index_file(const Opt &o, const Params &P, int device) {
+    std::unique_ptr<ReadOnlyIndex> loaded(new ReadOnlyIndex(ReadOnlyIndex::load(o.load_index, device)));
+    mq_params fp;
+    if (mq_index_get_params(loaded->handle(), &fp) != MQ_OK) throw Error("mq_index_get_params: " + last_error());
+    const mq_params want = P.to_abi();
+    if (fp.k != want.k || fp.l != want.l || fp.density != want.density || fp.use_hpc != want.use_hpc ||
+        (fp.flags & (MQ_FLAG_SEED_VARIANT_MASK | MQ_FLAG_FAST_KH)) != (want.flags & (MQ_FLAG_SEED_VARIANT_MASK | MQ_FLAG_FAST_KH))) {
+        char msg[640];
+        snprintf(msg, sizeof(msg), "%s was built with -k %u -l %u -d %s%s --seeding-variant %u%s: run with the same seeding parameters (this run: -k %u -l %u -d %s%s --seeding-variant %u%s)",
+                 o.load_index.c_str(), fp.k, fp.l, rust_float(fp.density).c_str(), fp.use_hpc ? "" : " --nohpc", (fp.flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT,
+                 (fp.flags & MQ_FLAG_FAST_KH) ? " --fast-kh" : "",
+                 want.k, want.l, rust_float(want.density).c_str(), want.use_hpc ? "" : " --nohpc", (want.flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT,
+                 (want.flags & MQ_FLAG_FAST_KH) ? " --fast-kh" : "");
+        throw Error(msg);
+    }
+    // the chaining thresholds and the case folding are this run's (they act at mapping time only)
+    if (mq_index_set_map_params(loaded->handle(), want.c, want.s, want.g, (want.flags & MQ_FLAG_FOLD_CASE) ? 1 : 0) != MQ_OK) throw Error("mq_index_set_map_params: " + last_error());
+    mq_index_stats st;
+    mq_index_get_stats(loaded->handle(), &st);
+    printf("Loaded index %s: %llu references, %llu k-min-mers.\n", o.load_index.c_str(), (unsigned long long)st.n_refs, (unsigned long long)st.n_kminmers);
+    tl("index file loaded");
+    return loaded;
+}
+
+// an uncompressed FASTA of one sequence line per record (what assemblers and this repository's tools write): streamed to the
+// device block by block as it is read, records indexed while the blocks behind them are still on the link (RefStreamer);
+// the host reads the header lines only.  Any other shape (Result::irregular): nothing is printed, the caller sends the file elsewhere.
+static feeder::RefStreamer::Result stream_reference(const RefPhase &rp) {
+    feeder::RefStreamer::Hooks hooks;
+    hooks.alloc = [](size_t n) { return mq_host_alloc(n); };
+    hooks.release = [](void *q) { mq_host_free(q); };
+    mq_index *h = rp.index->handle();
+    hooks.piece = [h](uint64_t at, const uint8_t *src, uint64_t n) {
+        uint64_t t = 0;
+        if (mq_index_stage_piece(h, at, src, n, &t) != MQ_OK) throw Error("mq_index_stage_piece: " + last_error());
+        return t;
+    };
+    hooks.done = [h](uint64_t t, bool wait) {
+        const int r = mq_index_stage_done(h, t, wait ? 1 : 0);
+        if (r < 0) throw Error("mq_index_stage_done: " + last_error());
+        return r == 1;
+    };
+    const bool join_dev = rp.o.ref_join_device;  // a record = its header line + everything up to the next '>' at a line start
+    feeder::RefStreamer rs(rp.o.reference, rp.n_parse, hooks, join_dev);
+    std::vector<std::string> lines;  // printed once the file's shape is known to be regular (else the loader below prints its own)
+    const feeder::RefStreamer::Result res = rs.run([&](size_t k, const std::string &id, uint64_t at, uint64_t len) {
+        const auto tr0 = Clock::now();
+        const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
+                                     : mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
+        if (cnt < 0) throw Error("ref_extract: " + last_error());
+        if (g_timeline && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
+        lines.push_back("Indexed reference " + id + ": " + std::to_string(cnt) + " k-min-mers.");  // src/closures.rs:58
+    });
+    if (!res.irregular) {
+        for (const std::string &ln : lines) puts(ln.c_str());
+        tl(join_dev ? "reference streamed: every record handed to ref_extract (lines joined on the device)" : "reference streamed: every record handed to ref_extract");
+    }
+    return res;
+}
+
+// an uncompressed FASTA: the whole file read once by all threads (since before the HIP runtime came up), multi-line records
+// compacted in place by a pool, records handed over whole and in order (ref_loader.hpp).  The buffer is page-locked in one
+// call (huge pages: milliseconds), every record's bytes are queued for the device the moment the record is ready
+// (mq_index_stage_piece: the link runs at its full rate, 3.1 GB in 0.06 s) and a second thread indexes record after record
+// behind its piece (mq_index_add_ref_staged) -- copied record by record from pageable memory this was 0.24 s.
+// ref_host (MQ_DRIVER_REF_HOST): records copied from pageable memory one by one, as in earlier rounds.  stage_begin: the index is a new
+// one (the streamer's went away with its staging buffer) and gets a staging buffer here.
+static void load_reference_whole(const RefPhase &rp, feeder::RefLoader &rl, bool ref_host, bool stage_begin) {
+    rl.wait_read();
+    tl("reference file in host memory");
+    mq_index *h = rp.index->handle();
+    struct stat rst;
+    bool staged = !ref_host && stat(rp.o.reference.c_str(), &rst) == 0 && (uint64_t)rst.st_size == rl.file_bytes();
+    if (staged && stage_begin) {
+        if (mq_index_stage_begin(h, rl.file_bytes()) != MQ_OK) staged = false;
+    }
+    bool locked = false;
+    if (staged) {
+        locked = mq_host_register(rl.data(), (size_t)rl.mapped_bytes()) == MQ_OK;  // (not locked: the copies still work, at the pageable rate)
+        tl(locked ? "reference buffer page-locked" : "reference buffer could not be page-locked: pageable copies");
+    }
+    struct Job {
+        size_t idx;
+        std::string id;
+        uint64_t at, len, ticket;
+    };
+    std::mutex jmu;
+    std::condition_variable jcv;
+    std::deque<Job> jobs;
+    bool jobs_done = false;
+    std::string jerr;
+    std::vector<std::string> lines;
+    std::thread indexer;
+    if (staged)
+        indexer = std::thread([&]() {
+            for (;;) {
+                Job j;
+                {
+                    std::unique_lock<std::mutex> lk(jmu);
+                    jcv.wait(lk, [&] { return !jobs.empty() || jobs_done; });
+                    if (jobs.empty()) return;
+                    j = std::move(jobs.front());
+                    jobs.pop_front();
+                }
+                const int64_t cnt = mq_index_add_ref_staged(h, (uint32_t)j.idx, j.id.c_str(), j.at, j.len, j.ticket);  // index_mers, src/closures.rs:46-51
+                if (cnt < 0) {
+                    std::lock_guard<std::mutex> lk(jmu);
+                    if (jerr.empty()) jerr = "ref_extract: " + last_error();
+                    return;
+                }
+                printf("Indexed reference %s: %lld k-min-mers.\n", j.id.c_str(), (long long)cnt);  // src/closures.rs:58
+            }
+        });
+    size_t ref_idx = 0;
+    std::string ferr;
+    uint64_t last_ticket = 0;
+    bool any_ticket = false;
+    try {
+        rl.for_each([&](const feeder::RefLoader::Record &r, const uint8_t *seq) {
+            if (ref_idx == 0) tl("first reference record ready");
+            if (rp.prefetch) rp.start_feed();  // the whole file has been read by now: the host threads are free
+            if (staged) {
+                uint64_t t = 0;
+                if (mq_index_stage_piece(h, r.seq, seq, r.len, &t) != MQ_OK) throw Error("mq_index_stage_piece: " + last_error());
+                last_ticket = t;
+                any_ticket = true;
+                {
+                    std::lock_guard<std::mutex> lk(jmu);
+                    if (!jerr.empty()) throw Error(jerr);
+                    jobs.push_back(Job{ref_idx, r.id, r.seq, r.len, t});
+                }
+                jcv.notify_all();
+            } else {
+                const size_t cnt = mers::ref_extract(ref_idx, r.id, seq, r.len, rp.P, *rp.index);
+                printf("Indexed reference %s: %zu k-min-mers.\n", r.id.c_str(), cnt);  // src/closures.rs:58
+            }
+            ++ref_idx;
+        });
+    } catch (const std::exception &e) { ferr = e.what(); }
+    {
+        std::lock_guard<std::mutex> lk(jmu);
+        jobs_done = true;
+        if (!ferr.empty()) jobs.clear();
+    }
+    jcv.notify_all();
+    if (indexer.joinable()) indexer.join();
+    // the copies read the buffer until the last piece is done (a record too short to be seeded is "indexed" without waiting for its piece)
+    if (any_ticket) mq_index_stage_done(h, last_ticket, 1);
+    if (locked) mq_host_unregister(rl.data());
+    if (!ferr.empty()) throw Error(ferr);
+    if (!jerr.empty()) throw Error(jerr);
+    tl("every reference record indexed");
+    // (the buffer goes back to the system at the end of the run, beside the rest of the teardown: handing 3 GB back takes 0.14 s
+    // here and stalls whoever maps or allocates memory meanwhile -- index finalisation, stream-slot set-up)
+}
+
+// compressed (or FASTQ) reference: through the chunked feeder, pageable chunk buffers (every reference byte is copied to
+// the device exactly once)
+static void feed_reference_chunked(const RefPhase &rp, bool ref_fasta) {
+    using feeder::Chunk;
+    if (rp.prefetch) rp.start_feed();
+    feeder::Feeder rfeed(rp.o.reference, !ref_fasta, 1ull << 28, rp.n_parse, rp.n_parse + 4, [](size_t n) { return malloc(n); },
+                         [](void *q) { free(q); }, [](void *, size_t) { return 0; }, [](void *) { return 0; });
+    rfeed.start();
+    std::map<size_t, Chunk *> held;
+    size_t next = 0, ref_idx = 0;
+    std::string name;
+    auto flush = [&]() {
+        for (auto it = held.find(next); it != held.end(); it = held.find(next)) {
+            Chunk *c = it->second;
+            for (size_t i = 0; i < c->starts.size(); ++i) {
+                name.assign((const char *)c->buf + c->ids[i].off, c->ids[i].len);
+                const size_t cnt = mers::ref_extract(ref_idx, name, c->buf + c->starts[i], c->lens[i], rp.P, *rp.index);
+                printf("Indexed reference %s: %zu k-min-mers.\n", name.c_str(), cnt);  // src/closures.rs:58
+                ++ref_idx;
+            }
+            held.erase(it);
+            rfeed.recycle(c);
+            ++next;
+        }
+    };
+    while (Chunk *c = rfeed.next()) {
+        held[c->seq_no] = c;
+        flush();
+    }
+    flush();
+}
+
 // One run of the reference's flow (src/closures.rs:22-212): index the reference, map the reads, write <prefix>.paf in input
 // order.  second_fa != "": the reads left unmapped also go to that FASTA file (for the second pass).
 static int run_pass(const Opt &o, const Params &P, const std::string &reads_path, bool reads_fasta, bool ref_fasta, const std::string &prefix,
@@ -202,7 +403,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
         // the whole job on the bench's input.
         const bool prefetch = getenv("MQ_DRIVER_PREFETCH") != nullptr && getenv("MQ_DRIVER_NO_PREFETCH") == nullptr;
         bool feed_started = false;
-        auto start_feed = [&]() {
+        const std::function<void()> start_feed = [&]() {
             if (!feed_started) {
                 feed.start();
                 feed_started = true;
@@ -274,34 +475,10 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
             std::thread &t;
             ~ReaperGuard() { if (t.joinable()) t.join(); }
         } reaper_guard{ref_reaper};
-        bool ref_done = false;
-        bool res_streamer_used = false;  // the streamer ran (and gave the file back): the index's staging buffer holds its pieces
-        bool streamer_index_dropped = false;  // ... after records had been indexed: that index was replaced by a new one
         std::unique_ptr<ReadOnlyIndex> loaded;
         if (!o.load_index.empty()) {
-            // --index: the finalized table from a file written by --save-index (occupied slots only; validated against its header on load)
             building.clear();
-            loaded.reset(new ReadOnlyIndex(ReadOnlyIndex::load(o.load_index, dev_of(0))));
-            mq_params fp;
-            if (mq_index_get_params(loaded->handle(), &fp) != MQ_OK) throw Error("mq_index_get_params: " + last_error());
-            const mq_params want = P.to_abi();
-            if (fp.k != want.k || fp.l != want.l || fp.density != want.density || fp.use_hpc != want.use_hpc ||
-                (fp.flags & (MQ_FLAG_SEED_VARIANT_MASK | MQ_FLAG_FAST_KH)) != (want.flags & (MQ_FLAG_SEED_VARIANT_MASK | MQ_FLAG_FAST_KH))) {
-                char msg[640];
-                snprintf(msg, sizeof(msg), "%s was built with -k %u -l %u -d %s%s --seeding-variant %u%s: run with the same seeding parameters (this run: -k %u -l %u -d %s%s --seeding-variant %u%s)",
-                         o.load_index.c_str(), fp.k, fp.l, rust_float(fp.density).c_str(), fp.use_hpc ? "" : " --nohpc", (fp.flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT,
-                         (fp.flags & MQ_FLAG_FAST_KH) ? " --fast-kh" : "",
-                         want.k, want.l, rust_float(want.density).c_str(), want.use_hpc ? "" : " --nohpc", (want.flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT,
-                         (want.flags & MQ_FLAG_FAST_KH) ? " --fast-kh" : "");
-                throw Error(msg);
-            }
-            // the chaining thresholds and the case folding are this run's (they act at mapping time only)
-            if (mq_index_set_map_params(loaded->handle(), want.c, want.s, want.g, (want.flags & MQ_FLAG_FOLD_CASE) ? 1 : 0) != MQ_OK) throw Error("mq_index_set_map_params: " + last_error());
-            mq_index_stats st;
-            mq_index_get_stats(loaded->handle(), &st);
-            printf("Loaded index %s: %llu references, %llu k-min-mers.\n", o.load_index.c_str(), (unsigned long long)st.n_refs, (unsigned long long)st.n_kminmers);
-            ref_done = true;
-            tl("index file loaded");
+            loaded = load_index_file(o, P, dev_of(0));
         } else {
             if (stream_ref || (preload && !ref_host)) {
                 // the device's staging buffer of the reference FIRST: device allocations queue behind each other, and this one (the file's
@@ -313,180 +490,34 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
             }
             reserve_table();
             early_start();
-        }
-        if (!ref_done && stream_ref) {
-            // an uncompressed FASTA of one sequence line per record (what assemblers and this repository's tools write): streamed to the
-            // device block by block as it is read, records indexed while the blocks behind them are still on the link (RefStreamer);
-            // the host reads the header lines only.  Any other shape: the loader below.
-            feeder::RefStreamer::Hooks hooks;
-            hooks.alloc = [](size_t n) { return mq_host_alloc(n); };
-            hooks.release = [](void *q) { mq_host_free(q); };
-            mq_index *h = building[0]->handle();
-            hooks.piece = [h](uint64_t at, const uint8_t *src, uint64_t n) {
-                uint64_t t = 0;
-                if (mq_index_stage_piece(h, at, src, n, &t) != MQ_OK) throw Error("mq_index_stage_piece: " + last_error());
-                return t;
-            };
-            hooks.done = [h](uint64_t t, bool wait) {
-                const int r = mq_index_stage_done(h, t, wait ? 1 : 0);
-                if (r < 0) throw Error("mq_index_stage_done: " + last_error());
-                return r == 1;
-            };
-            const bool join_dev = o.ref_join_device;  // a record = its header line + everything up to the next '>' at a line start
-            feeder::RefStreamer rs(o.reference, n_parse, hooks, join_dev);
-            std::vector<std::string> lines;  // printed once the file's shape is known to be regular (else the loader below prints its own)
-            res_streamer_used = true;
-            const feeder::RefStreamer::Result res = rs.run([&](size_t k, const std::string &id, uint64_t at, uint64_t len) {
-                const auto tr0 = Clock::now();
-                const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
-                                             : mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
-                if (cnt < 0) throw Error("ref_extract: " + last_error());
-                if (g_timeline && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
-                lines.push_back("Indexed reference " + id + ": " + std::to_string(cnt) + " k-min-mers.");  // src/closures.rs:58
-            });
-            if (!res.irregular) {
-                for (const std::string &ln : lines) puts(ln.c_str());
-                ref_done = true;
-                tl(join_dev ? "reference streamed: every record handed to ref_extract (lines joined on the device)" : "reference streamed: every record handed to ref_extract");
-            } else {
-                // not one sequence line per record (a line-wrapped FASTA shows in its first block, before anything was indexed): an index
-                // that took records already is dropped, and the file goes through the loader below
-                if (res.handed > 0) {  // (an index that has seen nothing stays: its table is being allocated in the background already)
-                    early_join();      // the slots set up so far belong to the index that goes away
-                    for (auto &v : slots) for (auto &c : v) { mq_ctx_free(c); c = nullptr; }
-                    building[0].reset();
-                    building[0].reset(new Index(P, dev_of(0)));
-                    building[0]->table_factor((uint32_t)o.table_factor);
-                    streamer_index_dropped = true;
-                    reserve_table();
+            const RefPhase rp{o, P, building[0], n_parse, start_feed, prefetch};
+            feeder::RefStreamer::Result streamed;  // the streamer's, where it ran
+            bool index_replaced = false;           // ... and gave the file back after records had been indexed: that index was replaced by a new one
+            if (stream_ref) {
+                streamed = stream_reference(rp);
+                if (streamed.irregular) {
+                    // not one sequence line per record (a line-wrapped FASTA shows in its first block, before anything was indexed): an index
+                    // that took records already is dropped, and the file goes through the loader below
+                    if (streamed.handed > 0) {  // (an index that has seen nothing stays: its table is being allocated in the background already)
+                        early_join();      // the slots set up so far belong to the index that goes away
+                        for (auto &v : slots) for (auto &c : v) { mq_ctx_free(c); c = nullptr; }
+                        building[0].reset();
+                        building[0].reset(new Index(P, dev_of(0)));
+                        building[0]->table_factor((uint32_t)o.table_factor);
+                        index_replaced = true;
+                        reserve_table();
+                    }
+                    tl("reference is not one line per record: host loader");
                 }
-                tl("reference is not one line per record: host loader");
             }
-        }
-        if (ref_done) {
-        } else if (ref_plain && !(o.low_memory && res_streamer_used)) {  // (--low-memory: a file the streamer gave back goes through the chunked reader below, record by record)
-            // an uncompressed FASTA: the whole file read once by all threads (since before the HIP runtime came up), multi-line records
-            // compacted in place by a pool, records handed over whole and in order (ref_loader.hpp).  The buffer is page-locked in one
-            // call (huge pages: milliseconds), every record's bytes are queued for the device the moment the record is ready
-            // (mq_index_stage_piece: the link runs at its full rate, 3.1 GB in 0.06 s) and a second thread indexes record after record
-            // behind its piece (mq_index_add_ref_staged) -- copied record by record from pageable memory this was 0.24 s.
-            if (!preload) preload.reset(new feeder::RefLoader(o.reference, n_parse, false));  // (the streamer above sent the file here)
-            feeder::RefLoader &rl = *preload;
-            rl.wait_read();
-            tl("reference file in host memory");
-            mq_index *h = building[0]->handle();
-            struct stat rst;
-            bool staged = !ref_host && stat(o.reference.c_str(), &rst) == 0 && (uint64_t)rst.st_size == rl.file_bytes();
-            if (staged && streamer_index_dropped) {  // the streamer's index went away with its staging buffer: the new index gets one
-                if (mq_index_stage_begin(h, rl.file_bytes()) != MQ_OK) staged = false;
-            }
-            bool locked = false;
-            if (staged) {
-                locked = mq_host_register(rl.data(), (size_t)rl.mapped_bytes()) == MQ_OK;  // (not locked: the copies still work, at the pageable rate)
-                tl(locked ? "reference buffer page-locked" : "reference buffer could not be page-locked: pageable copies");
-            }
-            struct Job {
-                size_t idx;
-                std::string id;
-                uint64_t at, len, ticket;
-            };
-            std::mutex jmu;
-            std::condition_variable jcv;
-            std::deque<Job> jobs;
-            bool jobs_done = false;
-            std::string jerr;
-            std::vector<std::string> lines;
-            std::thread indexer;
-            if (staged)
-                indexer = std::thread([&]() {
-                    for (;;) {
-                        Job j;
-                        {
-                            std::unique_lock<std::mutex> lk(jmu);
-                            jcv.wait(lk, [&] { return !jobs.empty() || jobs_done; });
-                            if (jobs.empty()) return;
-                            j = std::move(jobs.front());
-                            jobs.pop_front();
-                        }
-                        const int64_t cnt = mq_index_add_ref_staged(h, (uint32_t)j.idx, j.id.c_str(), j.at, j.len, j.ticket);  // index_mers, src/closures.rs:46-51
-                        if (cnt < 0) {
-                            std::lock_guard<std::mutex> lk(jmu);
-                            if (jerr.empty()) jerr = "ref_extract: " + last_error();
-                            return;
-                        }
-                        printf("Indexed reference %s: %lld k-min-mers.\n", j.id.c_str(), (long long)cnt);  // src/closures.rs:58
-                    }
-                });
-            size_t ref_idx = 0;
-            std::string ferr;
-            uint64_t last_ticket = 0;
-            bool any_ticket = false;
-            try {
-                rl.for_each([&](const feeder::RefLoader::Record &r, const uint8_t *seq) {
-                    if (ref_idx == 0) tl("first reference record ready");
-                    if (prefetch) start_feed();  // the whole file has been read by now: the host threads are free
-                    if (staged) {
-                        uint64_t t = 0;
-                        if (mq_index_stage_piece(h, r.seq, seq, r.len, &t) != MQ_OK) throw Error("mq_index_stage_piece: " + last_error());
-                        last_ticket = t;
-                        any_ticket = true;
-                        {
-                            std::lock_guard<std::mutex> lk(jmu);
-                            if (!jerr.empty()) throw Error(jerr);
-                            jobs.push_back(Job{ref_idx, r.id, r.seq, r.len, t});
-                        }
-                        jcv.notify_all();
-                    } else {
-                        const size_t cnt = mers::ref_extract(ref_idx, r.id, seq, r.len, P, *building[0]);
-                        printf("Indexed reference %s: %zu k-min-mers.\n", r.id.c_str(), cnt);  // src/closures.rs:58
-                    }
-                    ++ref_idx;
-                });
-            } catch (const std::exception &e) { ferr = e.what(); }
-            {
-                std::lock_guard<std::mutex> lk(jmu);
-                jobs_done = true;
-                if (!ferr.empty()) jobs.clear();
-            }
-            jcv.notify_all();
-            if (indexer.joinable()) indexer.join();
-            // the copies read the buffer until the last piece is done (a record too short to be seeded is "indexed" without waiting for its piece)
-            if (any_ticket) mq_index_stage_done(h, last_ticket, 1);
-            if (locked) mq_host_unregister(rl.data());
-            if (!ferr.empty()) throw Error(ferr);
-            if (!jerr.empty()) throw Error(jerr);
-            tl("every reference record indexed");
-            // (the buffer goes back to the system at the end of the run, beside the rest of the teardown: handing 3 GB back takes 0.14 s
-            // here and stalls whoever maps or allocates memory meanwhile -- index finalisation, stream-slot set-up)
-        } else {
-            // compressed (or FASTQ) reference: through the chunked feeder, pageable chunk buffers (every reference byte is copied to
-            // the device exactly once)
-            if (prefetch) start_feed();
-            feeder::Feeder rfeed(o.reference, !ref_fasta, 1ull << 28, n_parse, n_parse + 4, [](size_t n) { return malloc(n); },
-                                 [](void *q) { free(q); }, [](void *, size_t) { return 0; }, [](void *) { return 0; });
-            rfeed.start();
-            std::map<size_t, Chunk *> held;
-            size_t next = 0, ref_idx = 0;
-            std::string name;
-            auto flush = [&]() {
-                for (auto it = held.find(next); it != held.end(); it = held.find(next)) {
-                    Chunk *c = it->second;
-                    for (size_t i = 0; i < c->starts.size(); ++i) {
-                        name.assign((const char *)c->buf + c->ids[i].off, c->ids[i].len);
-                        const size_t cnt = mers::ref_extract(ref_idx, name, c->buf + c->starts[i], c->lens[i], P, *building[0]);
-                        printf("Indexed reference %s: %zu k-min-mers.\n", name.c_str(), cnt);  // src/closures.rs:58
-                        ++ref_idx;
-                    }
-                    held.erase(it);
-                    rfeed.recycle(c);
-                    ++next;
+            if (!stream_ref || streamed.irregular) {
+                if (ref_plain && !(o.low_memory && stream_ref)) {  // (--low-memory: a file the streamer gave back goes through the chunked reader, record by record)
+                    if (!preload) preload.reset(new feeder::RefLoader(o.reference, n_parse, false));  // (the streamer above sent the file here)
+                    load_reference_whole(rp, *preload, ref_host, index_replaced);
+                } else {
+                    feed_reference_chunked(rp, ref_fasta);
                 }
-            };
-            while (Chunk *c = rfeed.next()) {
-                held[c->seq_no] = c;
-                flush();
             }
-            flush();
         }
         std::vector<std::unique_ptr<ReadOnlyIndex>> ro((size_t)o.gpus);
         tl("every reference record handed to ref_extract");

@@ -6,6 +6,11 @@
 // threads in parallel (pread of 16-MB blocks into one anonymous, huge-page-backed mapping of the file's size), record starts
 // are found by the same threads, multi-line records are compacted in place by a pool (one record per task) while the caller
 // already indexes the first ones.  Uncompressed FASTA only: compressed or FASTQ references go through the feeder.
+//
+// Three parts: RefLoader (the whole file in host memory); two record trackers, LineRecords and RegionRecords, that find the
+// records of a file from per-block notes and know every rule about a block border (plain classes: no threads, no file, no locks); and
+// RefStreamer, one block pipeline written over a tracker type, which never holds the file: blocks of a size given to its constructor
+// (16 MB by default) go to the device as they are read.
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -25,6 +30,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include "fastx_records.hpp"
 
 namespace mapquik {
 namespace feeder {
@@ -118,12 +125,7 @@ class RefLoader {
                     const size_t b = next.fetch_add(1);
                     if (b >= n_blocks) break;
                     const uint64_t lo = (uint64_t)b * BLOCK, hi = std::min<uint64_t>(lo + BLOCK, size_);
-                    uint64_t got = 0;
-                    while (lo + got < hi) {
-                        const ssize_t r = pread(fd_, buf_ + lo + got, hi - lo - got, (off_t)(lo + got));
-                        if (r <= 0) throw std::runtime_error("read error: " + path_);
-                        got += (uint64_t)r;
-                    }
+                    pread_full(fd_, buf_ + lo, hi - lo, lo, path_);
                     for (uint64_t p = lo; p < hi;) {
                         const uint8_t *q = (const uint8_t *)memchr(buf_ + p, '>', hi - p);
                         if (!q) break;
@@ -161,12 +163,9 @@ class RefLoader {
         Record &r = recs_[i];
         const uint64_t h0 = starts_[i], end = r.region_end;
         const uint8_t *e1 = (const uint8_t *)memchr(buf_ + h0, '\n', end - h0);
-        uint64_t h1 = e1 ? (uint64_t)(e1 - buf_) : end;
+        const uint64_t h1 = e1 ? (uint64_t)(e1 - buf_) : end;
         const uint64_t s = h1 < end ? h1 + 1 : end;
-        if (h1 > h0 + 1 && buf_[h1 - 1] == '\r') --h1;
-        uint64_t ie = h0 + 1;
-        while (ie < h1 && buf_[ie] != ' ') ++ie;
-        r.id.assign((const char *)buf_ + h0 + 1, ie - (h0 + 1));
+        r.id.assign((const char *)buf_ + h0 + 1, fasta_id(buf_ + h0, h1 - h0));
         uint64_t dst = s, q = s;
         while (q < end) {
             const uint8_t *e = (const uint8_t *)memchr(buf_ + q, '\n', end - q);
@@ -228,21 +227,228 @@ class RefLoader {
     std::string error_;
 };
 
-// RefStreamer -- the same file, never held in host memory: the common shape of a reference FASTA written by a tool (one header line, one
-// sequence line per record) goes to the device as it is read.  Reader threads pread 16-MB blocks into a small pool of page-locked
-// chunks and note where the line ends and the '>' at line starts are; the calling thread queues every block's copy into the index's
-// staging buffer the moment it is read (mq_index_stage_piece: the PCIe link runs beside the reads, 3.1 GB in ~0.08 s) and recycles a
-// chunk when its copy is done; a third thread hands every record to the index as soon as its last block is on its way
-// (mq_index_add_ref_staged: the build's kernels wait on the device for the pieces, not on the host).  The host looks at a
-// header line only (pread of its few bytes) and never at a base: lower case and CR-LF are the kernels' / the spans' business.
-// Anything else -- sequences over several lines, blank lines, text before the first '>' -- ends the run as `irregular` and the caller
-// falls back to RefLoader (a line-wrapped FASTA shows in its first block, before anything was indexed).
-// join_lines (the driver's --ref-join device): a record is its header line plus every line up to the next line that starts with '>' (or
-// the file's end), and the callback gets that whole region: its lines are joined on the device (mq_index_add_ref_staged_lines).  The
-// block scan then looks for '>' at a line start and for the line end of that header only -- a wrapped file has 200,000 line ends per
-// block -- and the header is still the only text the host reads.  Text before the first '>' other than blank lines is `irregular`.
+// ---------------------------------------------------------------- the reference streamed: two record trackers and one block pipeline
+// A record tracker turns the blocks of a file into its records without ever holding the file: scan() notes what a block says about
+// lines (any thread, any order), consume() takes these notes in block order, finish() closes the file; every record goes to the sink
+// as (hdr_start, hdr_end, at, len), file offsets: the header line [hdr_start, hdr_end) without its line end, and the bytes
+// [at, at + len) that belong to it.  false from consume() or finish(): the file is not of the tracker's shape (`irregular`).  No
+// threads, no file, no locks: every rule about a block border is here, and a test can put a border anywhere (RefStreamer's block size).
+using RecordSink = std::function<void(uint64_t hdr_start, uint64_t hdr_end, uint64_t at, uint64_t len)>;
+
+// One header line, one sequence line per record (what assemblers and this repository's tools write); [at, at + len) is the sequence line
+// without its line end.  Sequences over several lines, text before the first '>', a header without its sequence line: irregular.
+class LineRecords {
+  public:
+    struct NL {
+        uint64_t pos;         // file offset of a '\n'
+        uint8_t cr;           // a '\r' in front of it (inside the block)
+        uint8_t next_known;   // the byte behind it lies in this block ...
+        uint8_t next;         // ... and is this one: the first byte of the next line
+    };
+    struct Summary {
+        uint64_t lo = 0, n = 0;  // the block: file offset, bytes
+        std::vector<NL> nl;
+        bool too_many = false;
+        uint8_t first_byte = 0, last_byte = 0;
+    };
+    static constexpr size_t MAX_LINES_PER_BLOCK = 65536;  // single-line records of >= 512 bytes on average; beyond: the host parser's case
+
+    explicit LineRecords(RecordSink sink) : sink_(std::move(sink)) {}
+
+    static Summary scan(const uint8_t *chunk, uint64_t n, uint64_t lo) {
+        Summary sc;
+        sc.lo = lo;
+        sc.n = n;
+        const uint8_t *p = chunk, *end = chunk + n;
+        if (n) {
+            sc.first_byte = chunk[0];
+            sc.last_byte = chunk[n - 1];
+        }
+        while (p < end) {
+            const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+            if (!q) break;
+            if (sc.nl.size() >= MAX_LINES_PER_BLOCK) {
+                sc.too_many = true;
+                return sc;
+            }
+            NL e;
+            e.pos = lo + (uint64_t)(q - chunk);
+            e.cr = (q > chunk && q[-1] == '\r') ? 1 : 0;
+            e.next_known = q + 1 < end ? 1 : 0;
+            e.next = q + 1 < end ? q[1] : 0;
+            sc.nl.push_back(e);
+            p = q + 1;
+        }
+        return sc;
+    }
+
+    bool consume(const Summary &s) {
+        if (s.too_many) return false;  // a block full of line ends: a line-wrapped FASTA (or very many tiny records): the host parser's case
+        if (cur_first < 0 && s.n) cur_first = s.first_byte;  // the line that opens this block
+        for (const NL &e : s.nl) {
+            const bool cr = e.pos == s.lo ? (s.lo > 0 && prev_last == '\r') : e.cr != 0;
+            if (!end_line(e.pos, cr)) return false;
+            cur_first = e.next_known ? (int)e.next : -1;
+        }
+        if (s.n) prev_last = s.last_byte;
+        return true;
+    }
+
+    bool finish(uint64_t file_size) {
+        if (line_start < file_size && !end_line(file_size, false)) return false;  // the file's last line has no '\n'
+        return !have_header;                                                      // a header without its sequence line
+    }
+
+  private:
+    // a line [line_start, nl) ends (at its '\n', or at the file's end); cr: a '\r' in front of the line end.  Lines alternate: header
+    // ('>' first), sequence (anything else first, or empty).  false: the file is not of that shape.
+    bool end_line(uint64_t nl, bool cr) {
+        const uint64_t ls = line_start, le = (cr && nl > ls) ? nl - 1 : nl;
+        const bool starts_gt = ls < nl && cur_first == '>';
+        line_start = nl + 1;
+        if (!have_header) {
+            if (ls == le) return true;     // a blank line where a header may start (before the first record, between records, at the end): skipped, as seq_io does
+            if (!starts_gt) return false;  // text before the first '>', a sequence that goes on over several lines
+            have_header = true;
+            hdr_start = ls;
+            hdr_end = le;
+            return true;
+        }
+        if (starts_gt) return false;  // a header without its sequence line
+        have_header = false;
+        if (le - ls >= (1ull << 32)) throw std::runtime_error("sequence length must be < 2^32");
+        sink_(hdr_start, hdr_end, ls, le - ls);
+        return true;
+    }
+
+    RecordSink sink_;
+    // line bookkeeping over the whole file: the start of the current line, and for a record in the making its header line
+    uint64_t line_start = 0;
+    bool have_header = false;
+    uint64_t hdr_start = 0, hdr_end = 0;  // [hdr_start, hdr_end): the header line without its line end
+    int cur_first = -1;                   // first byte of the line being read; -1: not seen yet (it opens the next block)
+    uint8_t prev_last = 0;                // the last byte of the block consumed before
+};
+
+// A record is its header line plus every line up to the next line that starts with '>' (or the file's end); [at, at + len) is that whole
+// region behind the header line's '\n', line ends and all.  The block scan looks for '>' at a line start and for the line end of that
+// header only -- a wrapped file has 200,000 line ends per block.  Text before the first '>' other than blank lines is irregular.
 // (Blank = '\n' and '\r' only, and the first '>' must follow a '\n' or open the file: "\r>a", or a '\r' and the '>' on either side of a
-// block border, is `irregular` too and goes to the loader.)
+// block border, is irregular too.)
+class RegionRecords {
+  public:
+    static constexpr uint64_t NONE = ~(uint64_t)0;
+    struct Hdr {
+        uint64_t pos;  // file offset of a '>' at a line start (at a block's first byte: whether a line starts there is known later)
+        uint64_t nl;   // file offset of the '\n' that ends that line; NONE: it lies in a later block
+        uint8_t cr;    // a '\r' in front of it
+    };
+    // the header lines that start in the block, the block's first '\n' (it ends a header that began earlier) and the number of blank
+    // bytes ('\n', '\r') the block opens with (all of the file in front of its first '>' must be)
+    struct Summary {
+        uint64_t lo = 0, n = 0;  // the block: file offset, bytes
+        std::vector<Hdr> hdrs;
+        uint64_t first_nl = NONE, lead_blank = 0;
+        uint8_t first_nl_cr = 0, last_byte = 0;
+    };
+
+    explicit RegionRecords(RecordSink sink) : sink_(std::move(sink)) {}
+
+    static Summary scan(const uint8_t *c, uint64_t n64, uint64_t lo) {
+        Summary sc;
+        sc.lo = lo;
+        sc.n = n64;
+        const size_t n = (size_t)n64;
+        if (!n) return sc;
+        sc.last_byte = c[n - 1];
+        size_t b = 0;
+        while (b < n && (c[b] == '\n' || c[b] == '\r')) ++b;
+        sc.lead_blank = b;
+        if (const uint8_t *q = (const uint8_t *)memchr(c, '\n', n)) {
+            sc.first_nl = lo + (uint64_t)(q - c);
+            sc.first_nl_cr = (q > c && q[-1] == '\r') ? 1 : 0;
+        }
+        for (size_t p = 0; p < n;) {
+            const uint8_t *q = (const uint8_t *)memchr(c + p, '>', n - p);
+            if (!q) break;
+            const size_t o = (size_t)(q - c);
+            if (o && c[o - 1] != '\n') {
+                p = o + 1;
+                continue;
+            }
+            const uint8_t *e = (const uint8_t *)memchr(q, '\n', n - o);
+            Hdr h;
+            h.pos = lo + o;
+            h.nl = e ? lo + (uint64_t)(e - c) : NONE;
+            h.cr = (e && e[-1] == '\r') ? 1 : 0;
+            sc.hdrs.push_back(h);
+            p = e ? (size_t)(e - c) + 1 : n;
+        }
+        return sc;
+    }
+
+    bool consume(const Summary &s) {
+        const bool ok = headers_of(s);
+        if (s.n) prev_last = s.last_byte;
+        return ok;
+    }
+
+    bool finish(uint64_t file_size) {
+        if (open) close_record(file_size);
+        return true;  // (an empty or all-blank file has no record: the pipeline's business)
+    }
+
+  private:
+    bool headers_of(const Summary &s) {
+        const uint64_t lo = s.lo;
+        if (open && cur_he == NONE && s.first_nl != NONE) {  // the header that began in an earlier block ends here
+            cur_he = s.first_nl;
+            cur_cr = s.first_nl == lo ? prev_last == '\r' : s.first_nl_cr != 0;
+        }
+        bool first = true;
+        for (const Hdr &h : s.hdrs) {
+            if (h.pos == lo && lo > 0 && prev_last != '\n') continue;  // a '>' that opens the block but not a line
+            if (first && !seen_header && s.lead_blank < h.pos - lo) return false;  // text before the first '>'
+            first = false;
+            if (open) close_record(h.pos);
+            open = seen_header = true;
+            cur_hs = h.pos;
+            cur_he = h.nl;
+            cur_cr = h.cr != 0;
+        }
+        return !(first && !seen_header && s.lead_blank < s.n);
+    }
+    // (a record closed by the next header knows its header's line end: a '>' at a line start lies behind a '\n')
+    void close_record(uint64_t region_end) {
+        const uint64_t he = cur_he == NONE ? region_end : cur_he;  // (a file that ends inside a header line: region_end is the file's end)
+        const bool cr = cur_he == NONE ? prev_last == '\r' : cur_cr;
+        const uint64_t at = std::min<uint64_t>(he + 1, region_end);
+        sink_(cur_hs, (cr && he > cur_hs + 1) ? he - 1 : he, at, region_end - at);
+        open = false;
+    }
+
+    RecordSink sink_;
+    // the record in the making -- its header line [cur_hs, cur_he) ('\n' at cur_he; NONE: not seen yet, it lies in a later block),
+    // cur_cr: a '\r' in front of that line end
+    bool open = false, seen_header = false;
+    uint64_t cur_hs = 0, cur_he = NONE;
+    bool cur_cr = false;
+    uint8_t prev_last = 0;  // the last byte of the block consumed before
+};
+
+// RefStreamer -- the same file, never held in host memory: the common shape of a reference FASTA written by a tool (one header line, one
+// sequence line per record) goes to the device as it is read.  Reader threads pread blocks (16 MB unless the constructor is told
+// otherwise) into a small pool of page-locked chunks and note what the record tracker wants to know of each (Tracker::scan); the
+// calling thread queues every block's copy into the index's staging buffer the moment it is read (mq_index_stage_piece: the PCIe link
+// runs beside the reads, 3.1 GB in ~0.08 s), recycles a chunk when its copy is done, and feeds the notes to the tracker in block
+// order; a third thread hands every record to the index as soon as its last block is on its way (mq_index_add_ref_staged: the build's
+// kernels wait on the device for the pieces, not on the host).  The host looks at a header line only (pread of its few bytes) and
+// never at a base: lower case and CR-LF are the kernels' / the spans' business.
+// The tracker is LineRecords, and anything but "header line, sequence line" -- sequences over several lines, text before the first
+// '>' -- ends the run as `irregular`: the caller falls back to RefLoader (a line-wrapped FASTA shows in its first block, before
+// anything was indexed).  join_lines (the driver's --ref-join device): the tracker is RegionRecords, the callback gets the whole
+// region of a record and its lines are joined on the device (mq_index_add_ref_staged_lines).  The pipeline is the same for both and
+// knows nothing of lines.
 class RefStreamer {
   public:
     struct Hooks {
@@ -252,14 +458,16 @@ class RefStreamer {
         std::function<bool(uint64_t ticket, bool wait)> done;                         // mq_index_stage_done
     };
     struct Result {
-        bool irregular = false;  // not "header line, sequence line" all through
+        bool irregular = false;  // not of the tracker's shape all through
         size_t handed = 0;       // records handed to the callback before that was noticed
         size_t records = 0;
     };
     static constexpr uint64_t BLOCK = 16u << 20;
 
-    RefStreamer(const std::string &path, int n_threads, Hooks hooks, bool join_lines = false)
-        : path_(path), n_threads_(n_threads < 1 ? 1 : n_threads), hooks_(std::move(hooks)), join_lines_(join_lines) {
+    // block_bytes: the size of a block and of a chunk (tests put block borders where they want them)
+    RefStreamer(const std::string &path, int n_threads, Hooks hooks, bool join_lines = false, uint64_t block_bytes = BLOCK)
+        : path_(path), n_threads_(n_threads < 1 ? 1 : n_threads), hooks_(std::move(hooks)), join_lines_(join_lines),
+          block_(block_bytes < 1 ? 1 : block_bytes) {
         fd_ = open(path.c_str(), O_RDONLY);
         if (fd_ < 0) throw std::runtime_error("Error opening compressed file: " + path);  // get_reader's message (src/main.rs:62)
         struct stat st;
@@ -278,14 +486,26 @@ class RefStreamer {
     // (join_lines: offset and length of the region behind the header line, line ends and all)
     template <class F>
     Result run(F fn) {
+        return join_lines_ ? run_with<RegionRecords>(fn) : run_with<LineRecords>(fn);
+    }
+
+  private:
+    template <class Tracker, class F>
+    Result run_with(F &fn) {
+        struct Block {
+            size_t block = 0;
+            uint8_t *chunk = nullptr;
+            uint64_t n = 0;
+            typename Tracker::Summary notes;
+        };
         Result res;
-        const size_t n_blocks = (size_t)((size_ + BLOCK - 1) / BLOCK);
+        const size_t n_blocks = (size_t)((size_ + block_ - 1) / block_);
         const size_t pool_size = (size_t)n_threads_ + 4;
         std::mutex mu;
         std::condition_variable cv;
         std::vector<void *> pool;           // free chunks
         size_t allocated = 0;               // chunks made so far (each reader makes its own first one: the pinning runs in parallel)
-        std::deque<Scan> scanned;           // blocks read and scanned, any order
+        std::deque<Block> scanned;          // blocks read and scanned, any order
         std::atomic<size_t> next_block{0};
         bool stop = false;
         std::string err;
@@ -307,24 +527,18 @@ class RefStreamer {
                         }
                     }
                     if (!chunk) {
-                        chunk = hooks_.alloc((size_t)BLOCK);
+                        chunk = hooks_.alloc((size_t)block_);
                         if (!chunk) throw std::runtime_error("cannot allocate a page-locked block for the reference");
                         std::lock_guard<std::mutex> lk(mu);
                         all_chunks_.push_back(chunk);
                     }
-                    Scan sc;
+                    Block sc;
                     sc.block = b;
                     sc.chunk = (uint8_t *)chunk;
-                    const uint64_t lo = (uint64_t)b * BLOCK, hi = std::min<uint64_t>(lo + BLOCK, size_);
+                    const uint64_t lo = (uint64_t)b * block_, hi = std::min<uint64_t>(lo + block_, size_);
                     sc.n = hi - lo;
-                    uint64_t got = 0;
-                    while (got < sc.n) {
-                        const ssize_t r = pread(fd_, sc.chunk + got, sc.n - got, (off_t)(lo + got));
-                        if (r <= 0) throw std::runtime_error("read error: " + path_);
-                        got += (uint64_t)r;
-                    }
-                    if (join_lines_) scan_block_headers(sc, lo);
-                    else scan_block(sc, lo);
+                    pread_full(fd_, sc.chunk, sc.n, lo, path_);
+                    sc.notes = Tracker::scan(sc.chunk, sc.n, lo);
                     {
                         std::lock_guard<std::mutex> lk(mu);
                         scanned.push_back(std::move(sc));
@@ -375,15 +589,9 @@ class RefStreamer {
         std::vector<std::thread> readers;
         for (int t = 0; t < n_threads_; ++t) readers.emplace_back(reader);
 
-        std::deque<std::pair<uint64_t, void *>> inflight;  // (ticket, chunk) in issue order
-        std::map<size_t, Scan> held;                       // scanned blocks waiting for their turn in the line bookkeeping
+        std::deque<std::pair<uint64_t, void *>> inflight;        // (ticket, chunk) in issue order
+        std::map<size_t, typename Tracker::Summary> held;        // the notes of blocks waiting for their turn in the tracker
         size_t next_in_order = 0, issued = 0;
-        // line bookkeeping over the whole file: the start of the current line, and for a record in the making its header line
-        uint64_t line_start = 0;
-        bool have_header = false;
-        uint64_t hdr_start = 0, hdr_end = 0;  // [hdr_start, hdr_end): the header line without its line end
-        int cur_first = -1;                   // first byte of the line being read; -1: not seen yet (it opens the next block)
-        uint8_t prev_last = 0;                // the last byte of the block consumed before
         auto give_back = [&](void *chunk) {
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -399,84 +607,25 @@ class RefStreamer {
                 must = false;
             }
         };
-        // a line [line_start, nl) ends (at its '\n', or at the file's end); cr: a '\r' in front of the line end.  Lines alternate: header
-        // ('>' first), sequence (anything else first, or empty).  false: the file is not of that shape.
         // a record goes to the indexer: header line [hs, he) without its line end, sequence (join_lines: region) [at, at + len)
-        auto hand_over = [&](uint64_t hs, uint64_t he, uint64_t at, uint64_t len) {
+        Tracker tracker([&](uint64_t hs, uint64_t he, uint64_t at, uint64_t len) {
             Rec r;
             r.at = at;
             r.len = len;
             // seq_io's id(): the header up to its first space -- the only bytes of the file the host reads
-            const uint64_t hl = he - hs;
-            std::string h((size_t)hl, '\0');
-            uint64_t got = 0;
-            while (got < hl) {
-                const ssize_t q = pread(fd_, &h[(size_t)got], (size_t)(hl - got), (off_t)(hs + got));
-                if (q <= 0) throw std::runtime_error("read error: " + path_);
-                got += (uint64_t)q;
-            }
-            size_t ie = 1;
-            while (ie < h.size() && h[ie] != ' ') ++ie;
-            r.id = h.substr(1, ie - 1);
+            std::vector<uint8_t> h((size_t)(he - hs));
+            pread_full(fd_, h.data(), h.size(), hs, path_);
+            if (!h.empty()) r.id.assign((const char *)h.data() + 1, (size_t)fasta_id(h.data(), h.size(), true));
             {
                 std::lock_guard<std::mutex> lk(mu);
                 to_index.push_back(std::move(r));
             }
             ++res.records;
             cv.notify_all();
-        };
-        auto end_line = [&](uint64_t nl, bool cr) -> bool {
-            const uint64_t ls = line_start, le = (cr && nl > ls) ? nl - 1 : nl;
-            const bool starts_gt = ls < nl && cur_first == '>';
-            line_start = nl + 1;
-            if (!have_header) {
-                if (ls == le) return true;     // a blank line where a header may start (before the first record, between records, at the end): skipped, as seq_io does
-                if (!starts_gt) return false;  // text before the first '>', a sequence that goes on over several lines
-                have_header = true;
-                hdr_start = ls;
-                hdr_end = le;
-                return true;
-            }
-            if (starts_gt) return false;  // a header without its sequence line
-            have_header = false;
-            if (le - ls >= (1ull << 32)) throw std::runtime_error("sequence length must be < 2^32");
-            hand_over(hdr_start, hdr_end, ls, le - ls);
-            return true;
-        };
-        // join_lines: the record in the making -- its header line [cur_hs, cur_he) ('\n' at cur_he; NONE: not seen yet, it lies in a later
-        // block), cur_cr: a '\r' in front of that line end
-        bool open = false, seen_header = false;
-        uint64_t cur_hs = 0, cur_he = NONE;
-        bool cur_cr = false;
-        auto close_record = [&](uint64_t region_end) {
-            const uint64_t he = cur_he == NONE ? size_ : cur_he;  // (a file that ends inside a header line)
-            const bool cr = cur_he == NONE ? (size_ > 0 && prev_last == '\r') : cur_cr;
-            const uint64_t at = std::min<uint64_t>(he + 1, region_end);
-            hand_over(cur_hs, (cr && he > cur_hs + 1) ? he - 1 : he, at, region_end - at);
-            open = false;
-        };
-        auto headers_of = [&](const Scan &s) -> bool {
-            const uint64_t lo = (uint64_t)s.block * BLOCK;
-            if (open && cur_he == NONE && s.first_nl != NONE) {  // the header that began in an earlier block ends here
-                cur_he = s.first_nl;
-                cur_cr = s.first_nl == lo ? prev_last == '\r' : s.first_nl_cr != 0;
-            }
-            bool first = true;
-            for (const Hdr &h : s.hdrs) {
-                if (h.pos == lo && lo > 0 && prev_last != '\n') continue;  // a '>' that opens the block but not a line
-                if (first && !seen_header && s.lead_blank < h.pos - lo) return false;  // text before the first '>'
-                first = false;
-                if (open) close_record(h.pos);
-                open = seen_header = true;
-                cur_hs = h.pos;
-                cur_he = h.nl;
-                cur_cr = h.cr != 0;
-            }
-            return !(first && !seen_header && s.lead_blank < s.n);
-        };
+        });
         try {
             while (issued < n_blocks && !res.irregular) {
-                Scan sc;
+                Block sc;
                 {
                     std::unique_lock<std::mutex> lk(mu);
                     if (scanned.empty() && !stop) {
@@ -498,41 +647,19 @@ class RefStreamer {
                     sc = std::move(scanned.front());
                     scanned.pop_front();
                 }
-                inflight.emplace_back(hooks_.piece((uint64_t)sc.block * BLOCK, sc.chunk, sc.n), sc.chunk);
+                inflight.emplace_back(hooks_.piece((uint64_t)sc.block * block_, sc.chunk, sc.n), sc.chunk);
                 ++issued;
-                const size_t blk = sc.block;
-                sc.chunk = nullptr;  // (the bytes are the link's now; the bookkeeping below uses what the scan noted)
-                held.emplace(blk, std::move(sc));
+                // (the bytes are the link's now; the tracker uses what the scan noted)
+                held.emplace(sc.block, std::move(sc.notes));
                 for (auto it = held.find(next_in_order); it != held.end() && !res.irregular; it = held.find(next_in_order)) {
-                    const Scan &s = it->second;
-                    const uint64_t lo = (uint64_t)s.block * BLOCK;
-                    if (join_lines_) {
-                        if (!headers_of(s)) res.irregular = true;
-                        if (s.n) prev_last = s.last_byte;
-                        held.erase(it);
-                        ++next_in_order;
-                        continue;
-                    }
-                    if (s.too_many) res.irregular = true;  // a block full of line ends: a line-wrapped FASTA (or very many tiny records): the host parser's case
-                    if (cur_first < 0 && s.n) cur_first = s.first_byte;  // the line that opens this block
-                    for (size_t k = 0; k < s.nl.size() && !res.irregular; ++k) {
-                        const NL &e = s.nl[k];
-                        const bool cr = e.pos == lo ? (lo > 0 && prev_last == '\r') : e.cr != 0;
-                        if (!end_line(e.pos, cr)) res.irregular = true;
-                        cur_first = e.next_known ? (int)e.next : -1;
-                    }
-                    if (s.n) prev_last = s.last_byte;
+                    if (!tracker.consume(it->second)) res.irregular = true;
                     held.erase(it);
                     ++next_in_order;
                 }
             }
-            if (!res.irregular && !stop && join_lines_) {
-                if (open) close_record(size_);
+            if (!res.irregular && !stop) {
+                if (!tracker.finish(size_)) res.irregular = true;
                 if (res.records == 0) res.irregular = true;  // (an empty or all-blank file: the host parser says what it is)
-            } else if (!res.irregular && !stop) {
-                if (line_start < size_ && !end_line(size_, false)) res.irregular = true;  // the file's last line has no '\n'
-                if (have_header) res.irregular = true;                                    // a header without its sequence line
-                if (res.records == 0) res.irregular = true;                               // (an empty file: the host parser says what it is)
             }
         } catch (const std::exception &e) {
             std::lock_guard<std::mutex> lk(mu);
@@ -556,92 +683,11 @@ class RefStreamer {
         return res;
     }
 
-  private:
-    struct NL {
-        uint64_t pos;         // file offset of a '\n'
-        uint8_t cr;           // a '\r' in front of it (inside the block)
-        uint8_t next_known;   // the byte behind it lies in this block ...
-        uint8_t next;         // ... and is this one: the first byte of the next line
-    };
-    static constexpr uint64_t NONE = ~(uint64_t)0;
-    struct Hdr {
-        uint64_t pos;  // file offset of a '>' at a line start (at a block's first byte: whether a line starts there is known later)
-        uint64_t nl;   // file offset of the '\n' that ends that line; NONE: it lies in a later block
-        uint8_t cr;    // a '\r' in front of it
-    };
-    struct Scan {
-        size_t block = 0;
-        uint8_t *chunk = nullptr;
-        uint64_t n = 0;
-        std::vector<NL> nl;
-        bool too_many = false;
-        uint8_t last_byte = 0, first_byte = 0;
-        // join_lines: the header lines that start in the block, the block's first '\n' (it ends a header that began earlier) and the
-        // number of blank bytes ('\n', '\r') the block opens with (all of the file in front of its first '>' must be)
-        std::vector<Hdr> hdrs;
-        uint64_t first_nl = NONE, lead_blank = 0;
-        uint8_t first_nl_cr = 0;
-    };
-    static constexpr size_t MAX_LINES_PER_BLOCK = 65536;  // single-line records of >= 512 bytes on average; beyond: the host parser's case
-
-    void scan_block(Scan &sc, uint64_t lo) const {
-        const uint8_t *p = sc.chunk, *end = sc.chunk + sc.n;
-        if (sc.n) {
-            sc.first_byte = sc.chunk[0];
-            sc.last_byte = sc.chunk[sc.n - 1];
-        }
-        while (p < end) {
-            const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-            if (!q) break;
-            if (sc.nl.size() >= MAX_LINES_PER_BLOCK) {
-                sc.too_many = true;
-                return;
-            }
-            NL e;
-            e.pos = lo + (uint64_t)(q - sc.chunk);
-            e.cr = (q > sc.chunk && q[-1] == '\r') ? 1 : 0;
-            e.next_known = q + 1 < end ? 1 : 0;
-            e.next = q + 1 < end ? q[1] : 0;
-            sc.nl.push_back(e);
-            p = q + 1;
-        }
-    }
-
-    void scan_block_headers(Scan &sc, uint64_t lo) const {
-        const uint8_t *c = sc.chunk;
-        const size_t n = (size_t)sc.n;
-        if (!n) return;
-        sc.first_byte = c[0];
-        sc.last_byte = c[n - 1];
-        size_t b = 0;
-        while (b < n && (c[b] == '\n' || c[b] == '\r')) ++b;
-        sc.lead_blank = b;
-        if (const uint8_t *q = (const uint8_t *)memchr(c, '\n', n)) {
-            sc.first_nl = lo + (uint64_t)(q - c);
-            sc.first_nl_cr = (q > c && q[-1] == '\r') ? 1 : 0;
-        }
-        for (size_t p = 0; p < n;) {
-            const uint8_t *q = (const uint8_t *)memchr(c + p, '>', n - p);
-            if (!q) break;
-            const size_t o = (size_t)(q - c);
-            if (o && c[o - 1] != '\n') {
-                p = o + 1;
-                continue;
-            }
-            const uint8_t *e = (const uint8_t *)memchr(q, '\n', n - o);
-            Hdr h;
-            h.pos = lo + o;
-            h.nl = e ? lo + (uint64_t)(e - c) : NONE;
-            h.cr = (e && e[-1] == '\r') ? 1 : 0;
-            sc.hdrs.push_back(h);
-            p = e ? (size_t)(e - c) + 1 : n;
-        }
-    }
-
     std::string path_;
     int n_threads_;
     Hooks hooks_;
     bool join_lines_ = false;
+    uint64_t block_ = BLOCK;
     int fd_ = -1;
     uint64_t size_ = 0;
     std::vector<void *> all_chunks_;

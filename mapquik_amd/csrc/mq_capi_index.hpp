@@ -282,23 +282,28 @@ int mq_index_stage_done(mq_index *idx, uint64_t ticket, int wait) {
     });
 }
 
+// the state, range and ticket checks of the calls that read the staging buffer, and the null stream made to wait for the pieces;
+// *d_region: buffer + at
+static int staged_region(mq_index *idx, const char *who, uint64_t at, uint64_t bytes, uint64_t after_ticket, const uint8_t **d_region) {
+    std::lock_guard<std::mutex> lk(idx->stg_mu);
+    if (!idx->stg_buf) return set_err(MQ_ESTATE, std::string(who) + " before mq_index_stage_begin");
+    if (at > idx->stg_bytes || bytes > idx->stg_bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
+    if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
+    // the build's kernels run on the null stream: it waits (on the device, not here) for the piece named (pieces complete in issue
+    // order, so for every piece up to it), or for every piece issued so far
+    const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? idx->stg_issued : after_ticket + 1;
+    if (upto) HIPCHK(hipStreamWaitEvent(0, idx->stg_events[(size_t)upto - 1], 0));
+    *d_region = idx->stg_buf + at;
+    return MQ_OK;
+}
+
 int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name, uint64_t at, uint64_t len, uint64_t after_ticket) {
     return guarded([&]() -> int64_t {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         int rc = use_device(idx);
         if (rc) return rc;
         const uint8_t *d_seq = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(idx->stg_mu);
-            if (!idx->stg_buf) return set_err(MQ_ESTATE, "mq_index_add_ref_staged before mq_index_stage_begin");
-            if (at > idx->stg_bytes || len > idx->stg_bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
-            // the build's kernels run on the null stream: it waits (on the device, not here) for the piece named (pieces complete in issue
-            // order, so for every piece up to it), or for every piece issued so far
-            if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
-            const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? idx->stg_issued : after_ticket + 1;
-            if (upto) HIPCHK(hipStreamWaitEvent(0, idx->stg_events[(size_t)upto - 1], 0));
-            d_seq = idx->stg_buf + at;
-        }
+        if ((rc = staged_region(idx, "mq_index_add_ref_staged", at, len, after_ticket, &d_seq))) return rc;
         std::lock_guard<std::mutex> lk(idx->mu);
         return add_ref_device_locked(idx, ref_id, name, d_seq, len);
     });
@@ -307,18 +312,6 @@ int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name
 // ---- records whose sequence is spread over lines (every genome FASTA of an archive is wrapped at 60-80 columns): the region between
 // the header's line end and the next record's '>' is joined on the device (mq_join.hpp) into bld.seq -- not in place: tiles of one launch
 // would race, and the staging buffer still holds the header of the next record -- and indexed from there.
-
-// the state, range and ticket checks of mq_index_add_ref_staged, and the null stream made to wait for the pieces; *d_region: buffer + at
-static int staged_region(mq_index *idx, const char *who, uint64_t at, uint64_t bytes, uint64_t after_ticket, const uint8_t **d_region) {
-    std::lock_guard<std::mutex> lk(idx->stg_mu);
-    if (!idx->stg_buf) return set_err(MQ_ESTATE, std::string(who) + " before mq_index_stage_begin");
-    if (at > idx->stg_bytes || bytes > idx->stg_bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
-    if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
-    const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? idx->stg_issued : after_ticket + 1;
-    if (upto) HIPCHK(hipStreamWaitEvent(0, idx->stg_events[(size_t)upto - 1], 0));
-    *d_region = idx->stg_buf + at;
-    return MQ_OK;
-}
 
 // The lines of d_region[0, bytes) joined into bld.seq, on the null stream (behind the previous record's build kernels, which read
 // bld.seq); *joined: the joined length, read back once the last kernel is queued.  d_region lies `at` bytes into the staging buffer,
