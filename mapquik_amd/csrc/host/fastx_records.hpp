@@ -1,6 +1,6 @@
 // fastx_records.hpp -- what a FASTX chunk is and how records are found in it on the host: Chunk, record boundaries (FASTA '>', FASTQ
 // '@' / '+' / equal lengths), the in-place parser (parse_chunk), spans from line ends found on the device (spans_from_line_ends), and the
-// run-time bindings of liblz4 / libdeflate.  Included by fastx_feeder.hpp.
+// run-time bindings of liblz4 / libdeflate.  Included by the read feeder's parts (fastx_feeder.hpp) and by ref_loader.hpp.
 #pragma once
 #include <dlfcn.h>
 #include <sys/mman.h>
@@ -80,7 +80,7 @@ inline void pread_full(int fd, void *dst, uint64_t n, uint64_t off, const std::s
     uint64_t got = 0;
     while (got < n) {
         const ssize_t r = pread(fd, (uint8_t *)dst + got, n - got, (off_t)(off + got));
-        if (r <= 0) throw std::runtime_error("read error: " + path);
+        if (r <= 0) throw FeederError("read error: " + path);
         got += (uint64_t)r;
     }
 }
@@ -138,6 +138,18 @@ inline uint64_t next_record_start(const uint8_t *b, uint64_t from, uint64_t end,
         p = (uint64_t)(e - b) + 1;
     }
     return at_eof ? end : NEED_MORE;
+}
+
+// the last record start in b[from, end) that can be vouched for without bytes beyond `end` (candidates too close to the end to be
+// validated are not taken); NEED_MORE if there is none
+inline uint64_t last_sure_record_start(const uint8_t *b, uint64_t from, uint64_t end, bool fastq) {
+    uint64_t last = NEED_MORE;
+    for (;;) {
+        const uint64_t q = next_record_start(b, from, end, fastq, false);
+        if (q == NEED_MORE || q >= end) return last;
+        last = q;
+        from = q + 1;
+    }
 }
 
 // ---------------------------------------------------------------- spans of a chunk whose line ends were found elsewhere

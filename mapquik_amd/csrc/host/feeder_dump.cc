@@ -1,6 +1,8 @@
 // feeder_dump -- test tool for fastx_feeder.hpp (no GPU needed: chunk buffers come from malloc).
 // usage: feeder_dump <file> <fasta|fastq|ref> <chunk_bytes> <threads>   -> one line per read, in input order: id TAB length TAB sequence
-//        (ref: through the reference loader, ref_loader.hpp; FEEDER_DUMP_QUIET=1 prints only "records bases" -- for timing)
+//        (ref: through the reference loader, ref_loader.hpp; FEEDER_DUMP_QUIET=1 prints only "records bases" -- for timing;
+//        FEEDER_DUMP_CHUNKS=1: stderr gets "chunk <seq_no> <records>" per chunk, in seq_no order, and at the end "syscr <n>", the
+//        process's read system calls as /proc/self/io counts them)
 //        feeder_dump <file> <refstream|refstream-lines> <block_bytes> <threads> -> the reference streamer (ref_loader.hpp: one sequence
 //        line per record | a record's lines joined later) with malloc'ed chunks and a link that is always done: one line per record,
 //        id TAB offset TAB length, or the one word "irregular".  block_bytes 0: every block size from 1 to the file's size + 1, each
@@ -124,11 +126,12 @@ int main(int argc, char **argv) {
         };
         std::map<size_t, Chunk *> held;
         size_t next = 0;
-        const bool quiet = getenv("FEEDER_DUMP_QUIET") != nullptr;
+        const bool quiet = getenv("FEEDER_DUMP_QUIET") != nullptr, list_chunks = getenv("FEEDER_DUMP_CHUNKS") != nullptr;
         unsigned long long n_rec = 0, n_bases = 0;
         auto flush = [&]() {
             for (auto it = held.find(next); it != held.end(); it = held.find(next)) {
                 Chunk *c = it->second;
+                if (list_chunks) fprintf(stderr, "chunk %zu %zu\n", c->seq_no, c->starts.size());
                 for (size_t i = 0; i < c->starts.size(); ++i) {
                     if (quiet) {
                         ++n_rec;
@@ -157,6 +160,15 @@ int main(int argc, char **argv) {
             return 1;
         }
         if (quiet) printf("%llu %llu\n", n_rec, n_bases);
+        if (list_chunks) {
+            unsigned long long syscr = 0;
+            char line[128];
+            if (FILE *io = fopen("/proc/self/io", "r")) {
+                while (fgets(line, sizeof(line), io))
+                    if (sscanf(line, "syscr: %llu", &syscr) == 1) fprintf(stderr, "syscr %llu\n", syscr);
+                fclose(io);
+            }
+        }
     } catch (const std::exception &e) {
         fprintf(stderr, "feeder_dump: %s\n", e.what());
         return 1;

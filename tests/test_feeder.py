@@ -306,3 +306,64 @@ def test_feeder_fastq_quality_lines_of_another_length(tool, tmp_path, crlf):
     for chunk, th in ((64, 4), (700, 3), (5000, 1), (1 << 28, 2)):
         assert _dump(tool, raw, True, chunk, th) == want, ("lean", chunk, th)
         assert _dump(tool, raw, True, chunk, th, {"MQ_FEEDER_NO_LEAN_FASTQ": "1"}) == want, ("chunked", chunk, th)
+
+
+def _record_starts(data, fastq):
+    """Byte offset of every record's first byte, by a plain line walk (FASTQ: four lines per record; FASTA: every '>' line)."""
+    starts, p, line = [], 0, 0
+    while p < len(data):
+        if (line % 4 == 0) if fastq else data[p:p + 1] == b">":
+            starts.append(p)
+        p = data.index(b"\n", p) + 1
+        line += 1
+    return starts
+
+
+@pytest.mark.parametrize("kind", ["fasta", "fasta-mapped", "fastq-lean", "fastq-chunked", "bgzf-fasta", "bgzf-fastq"])
+def test_feeder_chunk_owns_the_records_that_start_in_it(tool, tmp_path, kind):
+    """The rule the raw, lean-FASTQ, mapped-view and BGZF readers share: chunk i holds exactly the records whose first byte lies in
+    [i*CH, (i+1)*CH) of the (logical) file.  feeder_dump FEEDER_DUMP_CHUNKS=1 lists the records of every chunk; the plain parser
+    knows where every record starts.  LF line ends and a final newline (the lean reader's cut keeps the last record of a CR-LF file
+    without one with its predecessor); quality lines that begin with '@' and '+'."""
+    import os
+    fastq = "fastq" in kind
+    rng = random.Random(61 + fastq)
+    recs, text = _make(300, fastq, False, False, rng)
+    data = text.encode()
+    starts = _record_starts(data, fastq)
+    assert len(starts) == len(recs) == 300
+    env = {"FEEDER_DUMP_CHUNKS": "1"}
+    if kind.startswith("bgzf"):
+        blocks, p = bytearray(), 0
+        while p < len(data):  # blocks of 1,000-3,000 payload bytes: records, chunk and block boundaries fall everywhere
+            n = rng.randint(1000, 3000)
+            blocks += _bgzf(data[p:p + n], block=n)[:-28]  # (without the writer's empty EOF block)
+            p += n
+        path = tmp_path / "c.fx.gz"
+        path.write_bytes(bytes(blocks) + _bgzf(b""))
+        env["FEEDER_DUMP_KIND"] = "1"
+    else:
+        path = tmp_path / "c.fx"
+        path.write_bytes(data)
+    if kind == "fasta-mapped":
+        env.update(FEEDER_DUMP_UNPARSED="1", MQ_FEEDER_MAPPED_FASTA="1")
+    if kind == "fastq-chunked":
+        env["MQ_FEEDER_NO_LEAN_FASTQ"] = "1"
+    want_recs = [[a, str(len(b)), b] for a, b in recs]
+    for chunk in (64, 1000, 5000):
+        n_chunks = (len(data) + chunk - 1) // chunk
+        want = [0] * n_chunks
+        for s in starts:
+            want[s // chunk] += 1
+        for th in (1, 4):
+            r = subprocess.run([tool, str(path), "fastq" if fastq else "fasta", str(chunk), str(th)], capture_output=True, text=True, timeout=60,
+                               env=dict(os.environ, **env))
+            assert r.returncode == 0, r.stderr
+            got = [tuple(int(x) for x in ln.split()[1:]) for ln in r.stderr.split("\n") if ln.startswith("chunk ")]
+            assert got == list(enumerate(want)), (kind, chunk, th)
+            out = [ln.split("\t") for ln in r.stdout.split("\n") if ln != ""]
+            assert [g if len(g) == 3 else g + [""] for g in out] == want_recs
+            if kind.startswith("bgzf"):
+                assert "kind=bgzf" in r.stderr
+            if kind == "fasta-mapped":
+                assert "mapped 1" in r.stderr
