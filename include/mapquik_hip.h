@@ -256,6 +256,21 @@ int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_
 #define MQ_FASTX_FASTQ 1u
 int mq_ctx_submit_fastx(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format);
 int mq_ctx_wait_fasta(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags);
+/* MQ_FASTX_FASTA_LINES: FASTA records whose sequences may run over several lines (what seqkit writes by default: 60, 70 or 80 columns).
+ * buf[begin, bytes) holds whole records, begin at a record's '>'.  A header start is a '>' at `begin` or directly behind a '\n' (a '>'
+ * anywhere else is an ordinary byte); record r is header line r plus everything up to the next header start; its sequence is every byte
+ * behind the header line that is not '\n' and not a '\r' whose next byte is '\n' or which is the piece's last byte.  The device finds
+ * the headers and joins the lines; mq_ctx_wait_fasta_lines (and only it: mq_ctx_wait_fasta answers MQ_ESTATE and leaves the piece
+ * pending, as mq_ctx_wait_fasta_lines does for a piece of another format) launches the map kernels on the joined reads and returns
+ * pointers into the context's page-locked memory, valid until its next submit:
+ *   hdr_begin[r], hdr_end[r]   header line r = buf[hdr_begin[r], hdr_end[r]) ('>' first; a '\r' in front of the '\n' is inside)
+ *   seq_lens[r]                the joined length of read r (PAF column 2)
+ *   hits[0 .. n_reads)         as mq_ctx_wait fills them (overflow reads redone, from a host copy of those reads' joined bytes alone)
+ * flags & MQ_FASTA_IRREGULAR (n_reads = 0, nothing mapped, the context stays usable): the piece does not start with '>', holds more
+ * records than the span arrays (bytes / 32 + 2048), or holds a record without a sequence byte.  An empty piece is regular: 0 records. */
+#define MQ_FASTX_FASTA_LINES 2u
+int mq_ctx_wait_fasta_lines(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **hdr_begin, const uint32_t **hdr_end, const uint32_t **seq_lens,
+                            const mq_hit **hits, uint32_t *flags);
 /* Pre-size the context's device staging, minimizer lists and scratch for batches of up to n_reads reads / total_bytes buffer
  * bytes, so that the first submit does not pay for the allocations. */
 int mq_ctx_reserve(mq_ctx *ctx, uint32_t n_reads, uint64_t total_bytes);

@@ -31,7 +31,7 @@ def hit_column(hits, name):
     return v
 
 # every symbol include/mapquik_hip.h (the seam) and include/mapquik_hip_diag.h (measurement / diagnostics) declare
-EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_params", "mq_index_set_map_params", "mq_index_stage_begin", "mq_index_stage_piece", "mq_index_stage_done", "mq_index_add_ref_staged", "mq_index_add_ref_staged_lines", "mq_index_staged_sequence", "mq_ctx_submit_fasta", "mq_ctx_wait_fasta", "mq_index_reserve", "mq_host_register", "mq_host_unregister",
+EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_params", "mq_index_set_map_params", "mq_index_stage_begin", "mq_index_stage_piece", "mq_index_stage_done", "mq_index_add_ref_staged", "mq_index_add_ref_staged_lines", "mq_index_staged_sequence", "mq_ctx_submit_fasta", "mq_ctx_wait_fasta", "mq_ctx_wait_fasta_lines", "mq_index_reserve", "mq_host_register", "mq_host_unregister",
            "mq_last_error", "mq_abi_version", "mq_device_count", "mq_params_default", "mq_index_new", "mq_index_free",
            "mq_index_add_ref", "mq_index_add_ref_device", "mq_index_finalize", "mq_index_get_stats", "mq_index_ref_info",
            "mq_map_batch", "mq_map_batch_device", "mq_map_reserve", "mq_kminmers_batch", "mq_index_lookup", "mq_format_paf",
@@ -128,6 +128,8 @@ def load_library(path=None):
         L.mq_ctx_wait_fasta.argtypes = [vp, C.POINTER(u32), C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(u32)]
     if hasattr(L, "mq_ctx_submit_fastx"):
         L.mq_ctx_submit_fastx.argtypes = [vp, vp, u64, u64, u32]
+    if hasattr(L, "mq_ctx_wait_fasta_lines"):
+        L.mq_ctx_wait_fasta_lines.argtypes = [vp, C.POINTER(u32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
     if hasattr(L, "mq_index_stage_begin"):  # ABI 4
         L.mq_index_set_table_factor.argtypes = [vp, u32]
         L.mq_index_get_params.argtypes = [vp, C.POINTER(Params)]
@@ -557,12 +559,15 @@ class Context:
             raise _err(self._L, "mq_ctx_submit_spans")
         self._keep = (buf, starts, out, lens)
 
-    def submit_fasta(self, buf, begin=0, fastq=False):
+    def submit_fasta(self, buf, begin=0, fastq=False, lines=False):
         """Queue a piece of an uncompressed FASTA (or, fastq=True, four-line FASTQ) file that holds whole records (buf[begin:]): the
-        records are found on the device."""
+        records are found on the device.  lines=True (MQ_FASTX_FASTA_LINES): FASTA records whose sequences may run over several lines,
+        joined on the device; such a piece is finished with wait_fasta_lines()."""
+        if fastq and lines:
+            raise ValueError("fastq and lines exclude each other: only FASTA records are joined on the device")
         buf = _seq(buf)
-        if fastq:
-            if self._L.mq_ctx_submit_fastx(self._h, _p(buf), int(begin), buf.size, 1) != 0:
+        if fastq or lines:
+            if self._L.mq_ctx_submit_fastx(self._h, _p(buf), int(begin), buf.size, 1 if fastq else 2) != 0:
                 raise _err(self._L, "mq_ctx_submit_fastx")
         elif self._L.mq_ctx_submit_fasta(self._h, _p(buf), int(begin), buf.size) != 0:
             raise _err(self._L, "mq_ctx_submit_fasta")
@@ -580,6 +585,21 @@ class Context:
         hits = np.frombuffer(C.string_at(hp.value, n.value * hit_dtype.itemsize), dtype=hit_dtype).copy()
         lines = np.frombuffer(C.string_at(le.value, nl.value * 4), dtype=np.uint32).copy()
         return hits, lines, fl.value
+
+    def wait_fasta_lines(self):
+        """(hits, hdr_begin, hdr_end, seq_lens, flags) of the piece submitted with submit_fasta(lines=True): header r is
+        buf[hdr_begin[r]:hdr_end[r]], seq_lens[r] the joined length of read r.  flags & 1 (MQ_FASTA_IRREGULAR) or no record: empty arrays."""
+        n, fl = C.c_uint32(), C.c_uint32()
+        hb, he, sl, hp = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self._L.mq_ctx_wait_fasta_lines(self._h, C.byref(n), C.byref(hb), C.byref(he), C.byref(sl), C.byref(hp), C.byref(fl)) != 0:
+            raise _err(self._L, "mq_ctx_wait_fasta_lines")  # (MQ_ESTATE: the piece in flight, if any, is still pending)
+        self._keep = None
+        if fl.value & 1 or n.value == 0:
+            e = np.zeros(0, dtype=np.uint32)
+            return np.zeros(0, dtype=hit_dtype), e, e.copy(), e.copy(), fl.value
+        hits = np.frombuffer(C.string_at(hp.value, n.value * hit_dtype.itemsize), dtype=hit_dtype).copy()
+        u = [np.frombuffer(C.string_at(q.value, n.value * 4), dtype=np.uint32).copy() for q in (hb, he, sl)]
+        return hits, u[0], u[1], u[2], fl.value
 
     def wait(self):
         if self._L.mq_ctx_wait(self._h) != 0:

@@ -1,5 +1,5 @@
 // fastx_records.hpp -- what a FASTX chunk is and how records are found in it on the host: Chunk, record boundaries (FASTA '>', FASTQ
-// '@' / '+' / equal lengths), the in-place parser (parse_chunk), spans from line ends found on the device (spans_from_line_ends), and the
+// '@' / '+' / equal lengths), the in-place parser (parse_chunk), spans from line ends or header lines found on the device (spans_from_line_ends, spans_from_headers), and the
 // run-time bindings of liblz4 / libdeflate.  Included by the read feeder's parts (fastx_feeder.hpp) and by ref_loader.hpp.
 #pragma once
 #include <dlfcn.h>
@@ -12,6 +12,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/mapquik_hip.h"
@@ -32,6 +33,10 @@ struct Chunk {
     std::vector<uint64_t> starts;
     std::vector<uint32_t> lens;
     std::vector<IdSpan> ids;
+    // set by spans_from_headers (records found and their lines joined on the device, mq_ctx_wait_fasta_lines): everything of record i
+    // behind its header line, buf[regions[i].first, regions[i].second); starts stays empty, and whoever needs a read's bytes joins its
+    // region (append_joined_region)
+    std::vector<std::pair<uint64_t, uint64_t>> regions;
     std::vector<mq_hit> hits;
     std::string paf, unmapped, unmapped_fa;  // formatted output of this chunk
     // set by the whole-member gzip reader: the chunk's bytes still sit in a member's inflate buffer (kept alive by ext_hold);
@@ -63,6 +68,7 @@ struct Chunk {
         starts.clear();
         lens.clear();
         ids.clear();
+        regions.clear();
         hits.clear();
         paf.clear();
         unmapped.clear();
@@ -171,6 +177,32 @@ inline void spans_from_line_ends(Chunk &c, const uint32_t *line_ends, uint32_t n
         c.starts[i] = ss;
         c.lens[i] = (uint32_t)(se - ss);
         c.ids[i] = {hs + 1, (uint32_t)fasta_id(b + hs, he - hs)};
+    }
+}
+
+// ---------------------------------------------------------------- a chunk whose records were found and joined on the device
+// hdr_begin / hdr_end / seq_lens of mq_ctx_wait_fasta_lines (header line i = c.buf[hdr_begin[i], hdr_end[i]), seq_lens[i] the joined length):
+// the ids and lens parse_chunk gives for such a chunk, and every record's region; c.starts stays empty (the joined bytes are on the device).
+inline void spans_from_headers(Chunk &c, const uint32_t *hdr_begin, const uint32_t *hdr_end, const uint32_t *seq_lens, uint32_t n) {
+    const uint8_t *b = c.buf;
+    c.starts.clear();
+    c.lens.assign(seq_lens, seq_lens + n);
+    c.ids.resize(n);
+    c.regions.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t hs = hdr_begin[i], he = hdr_end[i];
+        c.ids[i] = {hs + 1, (uint32_t)fasta_id(b + hs, he - hs)};
+        c.regions[i] = {std::min<uint64_t>(he + 1, c.bytes), i + 1 < n ? (uint64_t)hdr_begin[i + 1] : c.bytes};
+    }
+}
+// The sequence of the region c.buf[from, to) appended to out, by the device's byte rule: a byte goes when it is '\n', or when it is
+// '\r' and the next byte is '\n' or there is none in the chunk.
+inline void append_joined_region(const Chunk &c, uint64_t from, uint64_t to, std::string &out) {
+    const uint8_t *b = c.buf;
+    for (uint64_t p = from; p < to; ++p) {
+        if (b[p] == '\n') continue;
+        if (b[p] == '\r' && (p + 1 == c.bytes || b[p + 1] == '\n')) continue;
+        out.push_back((char)b[p]);
     }
 }
 

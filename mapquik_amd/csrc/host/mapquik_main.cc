@@ -103,6 +103,7 @@ struct Opt {
     int seeding_variant = 0;  // MQ_SEEDVAR_* bits (include/mapquik_hip.h)
     bool fast_kh = false;     // MQ_FLAG_FAST_KH
     bool ref_join_device = false;  // --ref-join device: a line-wrapped reference is streamed too, its lines joined on the device
+    bool reads_join_device = false;  // --reads-join device: a line-wrapped reads FASTA goes to the device unparsed too, its records found and joined there
     bool last_pass = true;  // no second pass follows this one
     int table_factor = 2;  // table slots per inserted k-min-mer: this driver is bound by its host side (mq_index_set_table_factor)
     std::string save_index, load_index;  // --save-index / --index: the on-disk index (the reference has none and re-indexes on every run)
@@ -121,7 +122,7 @@ static void usage() {
          "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with)\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with)\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -394,7 +395,10 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
             on_device = fq && strcmp(fq, "device") == 0;
         }
         feed.leave_unparsed(on_device);  // (acts on uncompressed input only, FASTA or FASTQ)
-        const uint32_t fx_format = reads_fasta ? MQ_FASTX_FASTA : MQ_FASTX_FASTQ, fx_lpr = reads_fasta ? 2u : 4u;
+        // --reads-join device: FASTA chunks as MQ_FASTX_FASTA_LINES -- sequences over several lines (60, 70, 80 columns) are joined on the
+        // device instead of coming back irregular for a host thread to compact
+        const bool fx_wrapped = reads_fasta && o.reads_join_device;
+        const uint32_t fx_format = !reads_fasta ? MQ_FASTX_FASTQ : fx_wrapped ? MQ_FASTX_FASTA_LINES : MQ_FASTX_FASTA, fx_lpr = reads_fasta ? 2u : 4u;
         feed.premap();  // MQ_FEEDER_MAPPED_FASTA=1 only (experiment): the file is mapped, not read, while the reference is indexed
         // The read feeder starts when the index is ready.  MQ_DRIVER_PREFETCH=1 starts it while the reference is still being indexed
         // (it then allocates its page-locked chunk buffers and parses the first chunks early): that was the default while pinning
@@ -593,6 +597,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
         };
         const bool drv_timing = getenv("MQ_DRIVER_TIMING") != nullptr;  // diagnostic: where the map phase's threads spend their time (stderr)
         std::atomic<long long> t_submit_us{0}, t_finish_us{0}, t_fetch_us{0}, t_format_us{0}, t_write_us{0};
+        std::atomic<unsigned long long> n_unparsed{0}, n_irregular{0};  // chunks submitted unparsed / handed back by the device for the host's parser
         auto us_since = [](Clock::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - a).count(); };
         const char *fail_at_env = getenv("MQ_DRIVER_FAIL_AT");  // test hook: the worker that takes this chunk number reports a failure
         const long fail_at = fail_at_env ? atol(fail_at_env) : -1;
@@ -607,14 +612,17 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
                     if (!inflight[sl]) return;
                     const auto tf0 = Clock::now();
                     Chunk *fc = inflight[sl];
-                    if (fc->unparsed) {  // records found on the device: hits and line ends come back together
+                    if (fc->unparsed) {  // records found on the device: hits and line ends (or header spans) come back together
                         uint32_t n = 0, n_lines = 0, flags = 0;
-                        const uint32_t *line_ends = nullptr;
+                        const uint32_t *line_ends = nullptr, *hdr_begin = nullptr, *hdr_end = nullptr, *seq_lens = nullptr;
                         const mq_hit *hits = nullptr;
-                        if (mq_ctx_wait_fasta(ctx[sl], &n, &line_ends, &n_lines, &hits, &flags) != MQ_OK) {
-                            fail(std::string("mq_ctx_wait_fasta: ") + last_error());
+                        ++n_unparsed;
+                        if (fx_wrapped ? mq_ctx_wait_fasta_lines(ctx[sl], &n, &hdr_begin, &hdr_end, &seq_lens, &hits, &flags) != MQ_OK
+                                       : mq_ctx_wait_fasta(ctx[sl], &n, &line_ends, &n_lines, &hits, &flags) != MQ_OK) {
+                            fail(std::string(fx_wrapped ? "mq_ctx_wait_fasta_lines: " : "mq_ctx_wait_fasta: ") + last_error());
                         } else if (flags & MQ_FASTA_IRREGULAR) {
                             // sequences over several lines, blank lines, ...: this chunk the old way (parsed here, spans to the device)
+                            ++n_irregular;
                             try {
                                 fc->materialize();  // a view of the mapped file: the parser compacts sequence lines in place
                                 feeder::parse_chunk(*fc, !reads_fasta);
@@ -624,6 +632,9 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
                                      mq_ctx_wait(ctx[sl]) != MQ_OK))
                                     fail(std::string("mq_ctx_submit_spans: ") + last_error());
                             } catch (const std::exception &e) { fail(e.what()); }
+                        } else if (fx_wrapped) {
+                            feeder::spans_from_headers(*fc, hdr_begin, hdr_end, seq_lens, n);
+                            fc->hits.assign(hits, hits + n);
                         } else {
                             feeder::spans_from_line_ends(*fc, line_ends, n_lines, fx_lpr);
                             fc->hits.assign(hits, hits + n);
@@ -721,8 +732,8 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
                     }
                     const auto tm0 = Clock::now();
                     try {
-                    c->paf.reserve(c->starts.size() * 96);
-                    for (size_t i = 0; i < c->starts.size(); ++i) {
+                    c->paf.reserve(c->lens.size() * 96);
+                    for (size_t i = 0; i < c->lens.size(); ++i) {
                         const mq_hit &h = c->hits[i];
                         if (h.status == MQ_HIT_MAPPED) {
                             pw.append(c->paf, (const char *)c->buf + c->ids[i].off, c->ids[i].len, c->lens[i], h);  // src/mers.rs:181
@@ -735,7 +746,8 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
                                 c->unmapped_fa.push_back('>');
                                 c->unmapped_fa += id;
                                 c->unmapped_fa.push_back('\n');
-                                c->unmapped_fa.append((const char *)c->buf + c->starts[i], c->lens[i]);
+                                if (!c->regions.empty()) feeder::append_joined_region(*c, c->regions[i].first, c->regions[i].second, c->unmapped_fa);  // (joined on the device: no starts)
+                                else c->unmapped_fa.append((const char *)c->buf + c->starts[i], c->lens[i]);
                                 c->unmapped_fa.push_back('\n');
                             }
                         } else {
@@ -795,6 +807,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
             fprintf(stderr, "map phase %.3f s; summed over threads: submit %.3f s, finish (wait + spans) %.3f s, waiting for a chunk %.3f s (%d submitters), "
                             "format %.3f s (%d formatters), write + recycle %.3f s\n", secs(t0), t_submit_us / 1e6, t_finish_us / 1e6, t_fetch_us / 1e6, o.gpus * n_sub,
                     t_format_us / 1e6, n_format, t_write_us / 1e6);
+        if (drv_timing) fprintf(stderr, "unparsed chunks %llu irregular %llu\n", (unsigned long long)n_unparsed.load(), (unsigned long long)n_irregular.load());
         printf("Mapped query sequences in %s.\n", rust_duration(secs(t0)).c_str());  // src/closures.rs:211
         tl("PAF written");
         if (o.last_pass && getenv("MQ_DRIVER_FAST_EXIT") != nullptr) {
@@ -859,6 +872,11 @@ int main(int argc, char **argv) {
             const std::string v = val();
             if (v != "device" && v != "host") { fprintf(stderr, "error: --ref-join wants device or host\n"); return 2; }
             o.ref_join_device = v == "device";
+        }
+        else if (a == "--reads-join") {
+            const std::string v = val();
+            if (v != "device" && v != "host") { fprintf(stderr, "error: --reads-join wants device or host\n"); return 2; }
+            o.reads_join_device = v == "device";
         }
         else if (a == "--save-index") o.save_index = val();
         else if (a == "--index") o.load_index = val();

@@ -26,6 +26,7 @@
 #include "mq_seed.hpp"
 #include "mq_fastx.hpp"
 #include "mq_join.hpp"
+#include "mq_fastx_lines.hpp"
 
 using namespace mq;
 

@@ -238,21 +238,36 @@ static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
 // back.  The copy of the NEXT chunk (another context, another stream) runs meanwhile: the link stays busy.
 static uint32_t fx_line_cap(uint64_t bytes) { return (uint32_t)std::min<uint64_t>(bytes / 16 + 4096, 1u << 28); }
 
+// MQ_FASTX_FASTA_LINES only: the joined bytes (at most the piece's own) and the header spans of a piece of `bytes` bytes.  A context that
+// never sees the format never has them: mq_ctx_reserve sizes them only once a LINES piece has been submitted on the context.
+static int ctx_ensure_lines(mq_ctx *c, uint64_t bytes) {
+    const uint64_t cap = fx_line_cap(bytes) / 2;
+    int rc;
+    if ((rc = c->fl_joined.ensure(bytes + 64))) return rc;
+    if ((rc = c->fl_hb.ensure(cap + 1))) return rc;
+    return c->fl_he.ensure(cap + 1);
+}
+
 static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format) {
     mq_index *idx = c->idx;
     if (c->pending || c->fx_pending) return set_err(MQ_ESTATE, "context has a submitted batch: call mq_ctx_wait first");
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
     if (bytes >= (1ull << 32) || begin > bytes) return set_err(MQ_EINVAL, "a chunk must be smaller than 4 GB");
-    if (format != MQ_FASTX_FASTA && format != MQ_FASTX_FASTQ) return set_err(MQ_EINVAL, "format must be MQ_FASTX_FASTA or MQ_FASTX_FASTQ");
+    if (format != MQ_FASTX_FASTA && format != MQ_FASTX_FASTQ && format != MQ_FASTX_FASTA_LINES)
+        return set_err(MQ_EINVAL, "format must be MQ_FASTX_FASTA, MQ_FASTX_FASTQ or MQ_FASTX_FASTA_LINES");
+    const bool wrapped = format == MQ_FASTX_FASTA_LINES;      // records found and their lines joined by mq_fastx_lines.hpp
     const uint32_t lpr = format == MQ_FASTX_FASTQ ? 4u : 2u;  // lines per record
     int rc = use_device(idx);
     if (rc) return rc;
     const uint32_t n_tiles = (uint32_t)((bytes + FX_TILE - 1) / FX_TILE);
     const uint32_t cap = fx_line_cap(bytes);
     if ((rc = c->st_bases.ensure(bytes + 64))) return rc;
-    if ((rc = c->fx_tile_counts.ensure((uint64_t)n_tiles + 1))) return rc;
-    if ((rc = c->fx_tile_off.ensure((uint64_t)n_tiles + 1))) return rc;
-    if ((rc = c->fx_nl.ensure(cap))) return rc;
+    if ((rc = c->fx_tile_counts.ensure(((uint64_t)n_tiles + 1) * (wrapped ? 4u : 1u)))) return rc;
+    if ((rc = c->fx_tile_off.ensure(((uint64_t)n_tiles + 1) * (wrapped ? 3u : 1u)))) return rc;
+    if (wrapped) {
+        c->fl_used = true;
+        if ((rc = ctx_ensure_lines(c, bytes))) return rc;
+    } else if ((rc = c->fx_nl.ensure(cap))) return rc;
     if ((rc = c->st_off.ensure((uint64_t)cap / 2 + 1))) return rc;
     if ((rc = c->st_lens.ensure((uint64_t)cap / 2 + 1))) return rc;
     if (!c->fx_info && (rc = c->fx_info.alloc(4))) return rc;
@@ -275,6 +290,22 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
     }
     const uint32_t b = (uint32_t)begin, e = (uint32_t)bytes;
     const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((n_tiles + 3) / 4, (uint32_t)idx->n_cu * 8u));
+    if (wrapped) {
+        unsigned long long *offs = reinterpret_cast<unsigned long long *>(c->st_off.p);
+        hipLaunchKernelGGL(fl_count_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
+        hipLaunchKernelGGL(fl_scan_kernel, dim3(1), dim3(1024), 0, st, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, offs, c->fl_he, cap / 2, c->fx_info);
+        hipLaunchKernelGGL(fl_write_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_info, c->fl_joined, c->fl_hb, c->fl_he, offs, cap / 2);
+        const dim3 cgrid(std::max<uint32_t>(1, std::min<uint32_t>(cap / 2 / 256 + 1, (uint32_t)idx->n_cu * 4u)));
+        hipLaunchKernelGGL(fl_check_kernel, cgrid, dim3(256), 0, st, offs, c->st_lens, c->fx_info);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, st));
+        c->fx_pending = true;
+        c->fx_lines = true;
+        c->fx_buf = buf;
+        c->fx_begin = b;
+        c->fx_bytes = e;
+        return MQ_OK;
+    }
     hipLaunchKernelGGL(count_newlines_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
     hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, st, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, c->fx_nl, cap, c->fx_info, lpr);
     hipLaunchKernelGGL(list_newlines_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_nl, cap);
@@ -286,6 +317,7 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, st));
     c->fx_pending = true;
+    c->fx_lines = false;
     c->fx_lpr = lpr;
     c->fx_buf = buf;
     c->fx_begin = b;
@@ -295,6 +327,7 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
 
 static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags) {
     if (!c->fx_pending) return set_err(MQ_ESTATE, "no FASTA chunk submitted on this context");
+    if (c->fx_lines) return set_err(MQ_ESTATE, "the submitted piece is MQ_FASTX_FASTA_LINES: call mq_ctx_wait_fasta_lines");
     c->fx_pending = false;
     mq_index *idx = c->idx;
     int rc = use_device(idx);
@@ -340,6 +373,64 @@ static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_en
     return MQ_OK;
 }
 
+// MQ_FASTX_FASTA_LINES: the result words, the map kernels on (joined bytes, offsets) -- the device form, no lengths -- and hits, header
+// spans and joined lengths back.
+static int ctx_wait_fasta_lines(mq_ctx *c, uint32_t *n_reads, const uint32_t **hdr_begin, const uint32_t **hdr_end, const uint32_t **seq_lens,
+                                const mq_hit **hits, uint32_t *flags) {
+    if (!c->fx_pending || !c->fx_lines) return set_err(MQ_ESTATE, "no MQ_FASTX_FASTA_LINES piece submitted on this context");
+    c->fx_pending = false;
+    c->fx_lines = false;
+    mq_index *idx = c->idx;
+    int rc = use_device(idx);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint32_t n = c->h_fx_info[0], joined = c->h_fx_info[1];
+    *flags = c->h_fx_info[2];
+    *n_reads = 0;
+    *hdr_begin = *hdr_end = *seq_lens = nullptr;
+    *hits = nullptr;
+    if (*flags & FX_IRREGULAR) return MQ_OK;  // the caller parses this piece on the host
+    if (n == 0) return MQ_OK;
+    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((rc = c->h_fl_hb.ensure((uint64_t)n))) return rc;
+    if ((rc = c->h_fl_he.ensure((uint64_t)n))) return rc;
+    if ((rc = c->h_fl_lens.ensure((uint64_t)n))) return rc;
+    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
+    if ((rc = ctx_ensure(c, n, joined, list_f16(idx)))) return rc;
+    if (getenv("MQ_FX_POISON_HITS")) HIPCHK(hipMemsetAsync(c->st_out, 0xFF, (size_t)n * sizeof(mq_hit), c->stream));  // test hook: a record no wave writes shows
+    if ((rc = launch_map(c, c->fl_joined, c->st_off, n, c->st_out, c->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(c->h_out, c->st_out, (size_t)n * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fl_hb, c->fl_hb, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fl_he, c->fl_he, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fl_lens, c->st_lens, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> redo;
+    for (uint32_t i = 0; i < n; ++i)
+        if (c->h_out[i].status == MQ_HIT_OVERFLOW) redo.push_back(i);
+    if (!redo.empty()) {  // again with room, from a host copy of THOSE reads' joined bytes (the rest of the piece stays on the device)
+        std::vector<uint64_t> at(redo.size()), so(redo.size() + 1, 0);
+        for (size_t j = 0; j < redo.size(); ++j) {
+            HIPCHK(hipMemcpyAsync(&at[j], c->st_off.p + redo[j], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+            so[j + 1] = so[j] + c->h_fl_lens[redo[j]];
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<uint8_t> sb(so.back() ? so.back() : 1);
+        for (size_t j = 0; j < redo.size(); ++j)
+            if (so[j + 1] > so[j]) HIPCHK(hipMemcpyAsync(sb.data() + so[j], c->fl_joined.p + at[j], (size_t)(so[j + 1] - so[j]), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<mq_hit> sh(redo.size());
+        for (mq_hit &h : sh) h.status = MQ_HIT_OVERFLOW;
+        if ((rc = redo_overflow(c, sb.data(), so.data(), nullptr, (uint32_t)redo.size(), sh.data()))) return rc;
+        for (size_t j = 0; j < redo.size(); ++j) c->h_out[redo[j]] = sh[j];
+    }
+    *n_reads = n;
+    *hdr_begin = c->h_fl_hb;
+    *hdr_end = c->h_fl_he;
+    *seq_lens = c->h_fl_lens;
+    *hits = c->h_out;
+    return MQ_OK;
+}
+
 extern "C" {
 
 int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes) {
@@ -360,6 +451,14 @@ int mq_ctx_wait_fasta(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **line_ends
     return guarded([&]() -> int {
         if (!ctx || !n_reads || !line_ends || !n_lines || !hits || !flags) return set_err(MQ_EINVAL, "bad arguments");
         return ctx_wait_fasta(ctx, n_reads, line_ends, n_lines, hits, flags);
+    });
+}
+
+int mq_ctx_wait_fasta_lines(mq_ctx *ctx, uint32_t *n_reads, const uint32_t **hdr_begin, const uint32_t **hdr_end, const uint32_t **seq_lens,
+                            const mq_hit **hits, uint32_t *flags) {
+    return guarded([&]() -> int {
+        if (!ctx || !n_reads || !hdr_begin || !hdr_end || !seq_lens || !hits || !flags) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_wait_fasta_lines(ctx, n_reads, hdr_begin, hdr_end, seq_lens, hits, flags);
     });
 }
 
@@ -399,7 +498,8 @@ int mq_ctx_reserve(mq_ctx *ctx, uint32_t n_reads, uint64_t total_bytes) {
         if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
         int rc = use_device(ctx->idx);
         if (rc) return rc;
-        return ctx_ensure_staging(ctx, n_reads, total_bytes, true);
+        if ((rc = ctx_ensure_staging(ctx, n_reads, total_bytes, true))) return rc;
+        return ctx->fl_used ? ctx_ensure_lines(ctx, total_bytes) : MQ_OK;  // (a context that never saw a LINES piece does not pay for its buffers)
     });
 }
 

@@ -43,6 +43,13 @@ struct mq_ctx {
     Buf<uint32_t> fx_info;          // lines, records, flags
     PinnedBuf<uint32_t> h_fx_info;
     PinnedBuf<uint8_t> h_fx_tail;   // one page: the piece's bytes behind its last page boundary
+    // MQ_FASTX_FASTA_LINES (mq_fastx_lines.hpp): the joined sequence bytes, header spans and their mirrors; the joined lengths come back
+    // from st_lens, the offsets of the joined reads live in st_off
+    Buf<uint8_t> fl_joined;
+    Buf<uint32_t> fl_hb, fl_he;
+    PinnedBuf<uint32_t> h_fl_hb, h_fl_he, h_fl_lens;
+    bool fl_used = false;           // a LINES piece has been submitted on this context: mq_ctx_reserve sizes the buffers above too
+    bool fx_lines = false;          // the piece in flight is a LINES piece (mq_ctx_wait_fasta_lines finishes it)
     bool fx_pending = false;
     uint32_t fx_lpr = 2;            // lines per record of the piece in flight (FASTA 2, FASTQ 4)
     const uint8_t *fx_buf = nullptr;
