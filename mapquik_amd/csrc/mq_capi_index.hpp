@@ -329,7 +329,7 @@ static int join_lines_locked(mq_index *idx, const uint8_t *d_region, uint64_t at
     if ((rc = idx->bld.join_counts.ensure(n_tiles))) return rc;
     if ((rc = idx->bld.join_off.ensure(n_tiles))) return rc;
     if (!idx->bld.join_total && (rc = idx->bld.join_total.alloc(1))) return rc;
-    const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((n_tiles + 3) / 4, (uint32_t)idx->n_cu * 8u));
+    const uint32_t grid = fx_grid(idx, n_tiles);
     hipLaunchKernelGGL(join_count_kernel, dim3(grid), dim3(256), 0, 0, base, begin, end, n_tiles, idx->bld.join_counts);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(join_scan_kernel, dim3(1), dim3(1024), 0, 0, idx->bld.join_counts, n_tiles, idx->bld.join_off, idx->bld.join_total);

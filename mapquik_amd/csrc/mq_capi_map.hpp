@@ -92,23 +92,20 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
 }
 
 // Reads that came back MQ_HIT_OVERFLOW (more Match runs than the per-wave scratch holds, or a minimizer list denser than its
-// region): map those again on the GPU with worst-case scratch and list regions on a small grid.  Never a CPU path.
-static int redo_overflow(mq_ctx *c, const uint8_t *bases, const uint64_t *offsets, const uint32_t *lens, uint32_t n, mq_hit *out) {
-    mq_index *idx = c->idx;
+// region) are mapped again on the GPU with worst-case scratch and list regions on a small grid.  Never a CPU path.
+static std::vector<uint32_t> overflow_reads(const mq_hit *out, uint32_t n) {
     std::vector<uint32_t> redo;
     for (uint32_t i = 0; i < n; ++i)
         if (out[i].status == MQ_HIT_OVERFLOW) redo.push_back(i);
-    if (redo.empty()) return MQ_OK;
+    return redo;
+}
+
+// The relaunch: read j of the redo list is sb[so[j], so[j + 1]); its hit goes to out[redo[j]]
+static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std::vector<uint8_t> &sb, const std::vector<uint64_t> &so, mq_hit *out) {
+    mq_index *idx = c->idx;
     uint64_t sub_max = 0;
-    std::vector<uint64_t> so(redo.size() + 1, 0);
-    for (size_t j = 0; j < redo.size(); ++j) {
-        const uint64_t L = lens ? (uint64_t)lens[redo[j]] : offsets[redo[j] + 1] - offsets[redo[j]];
-        so[j + 1] = so[j] + L;
-        sub_max = std::max(sub_max, L);
-    }
+    for (size_t j = 0; j < redo.size(); ++j) sub_max = std::max(sub_max, so[j + 1] - so[j]);
     const uint64_t sub_total = so.back();
-    std::vector<uint8_t> sb(sub_total ? sub_total : 1);
-    for (size_t j = 0; j < redo.size(); ++j) memcpy(sb.data() + so[j], bases + offsets[redo[j]], (size_t)(so[j + 1] - so[j]));
     const uint32_t cap = (uint32_t)std::max<uint64_t>(sub_max, 1);  // a read cannot have more runs than bases
     const uint32_t waves = std::max(MAP_WAVES, ML_WAVES);
     const uint32_t rgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min(idx->grid_fused, idx->grid_map), (1ull << 30) / ((uint64_t)cap * sizeof(MatchRec) * waves)));
@@ -143,6 +140,36 @@ static int redo_overflow(mq_ctx *c, const uint8_t *bases, const uint64_t *offset
     return MQ_OK;
 }
 
+// ... of a batch in host arrays (lens == nullptr: read i ends at offsets[i + 1])
+static int redo_overflow(mq_ctx *c, const uint8_t *bases, const uint64_t *offsets, const uint32_t *lens, uint32_t n, mq_hit *out) {
+    const std::vector<uint32_t> redo = overflow_reads(out, n);
+    if (redo.empty()) return MQ_OK;
+    std::vector<uint64_t> so(redo.size() + 1, 0);
+    for (size_t j = 0; j < redo.size(); ++j) so[j + 1] = so[j] + (lens ? (uint64_t)lens[redo[j]] : offsets[redo[j] + 1] - offsets[redo[j]]);
+    std::vector<uint8_t> sb(so.back() ? so.back() : 1);
+    for (size_t j = 0; j < redo.size(); ++j) memcpy(sb.data() + so[j], bases + offsets[redo[j]], (size_t)(so[j + 1] - so[j]));
+    return redo_relaunch(c, redo, sb, so, out);
+}
+
+// ... of a piece whose records the device found: THOSE reads' offsets, lengths (d_lens == nullptr: up to d_offsets[r + 1]) and bytes come back from the arrays the launch read
+static int redo_overflow_device(mq_ctx *c, const uint8_t *d_bytes, const uint64_t *d_offsets, const uint32_t *d_lens, uint32_t n, mq_hit *out) {
+    const std::vector<uint32_t> redo = overflow_reads(out, n);
+    if (redo.empty()) return MQ_OK;
+    std::vector<uint64_t> at(2 * redo.size()), so(redo.size() + 1, 0);  // at[2 j], at[2 j + 1]: where read j begins and (device form) ends
+    std::vector<uint32_t> len(redo.size());
+    for (size_t j = 0; j < redo.size(); ++j) {
+        HIPCHK(hipMemcpyAsync(&at[2 * j], d_offsets + redo[j], (d_lens ? 1 : 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        if (d_lens) HIPCHK(hipMemcpyAsync(&len[j], d_lens + redo[j], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < redo.size(); ++j) so[j + 1] = so[j] + (d_lens ? (uint64_t)len[j] : at[2 * j + 1] - at[2 * j]);
+    std::vector<uint8_t> sb(so.back() ? so.back() : 1);
+    for (size_t j = 0; j < redo.size(); ++j)
+        if (so[j + 1] > so[j]) HIPCHK(hipMemcpyAsync(sb.data() + so[j], d_bytes + at[2 * j], (size_t)(so[j + 1] - so[j]), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return redo_relaunch(c, redo, sb, so, out);
+}
+
 // What a batch of n reads in `total` bytes needs of a context on its way through the host-buffer entry points: the page-locked side,
 // scratch, device staging.
 static int ctx_ensure_staging(mq_ctx *c, uint32_t n, uint64_t total, bool with_lens) {
@@ -156,17 +183,23 @@ static int ctx_ensure_staging(mq_ctx *c, uint32_t n, uint64_t total, bool with_l
     return with_lens ? c->st_lens.ensure((uint64_t)n) : MQ_OK;
 }
 
+// One context runs one thing at a time: a batch or a piece that has been submitted is waited for before the next
+static int ctx_require_idle(const mq_ctx *c) {
+    if (c->pending || c->fx_kind != FxKind::None) return set_err(MQ_ESTATE, "context has a submitted batch: call mq_ctx_wait / mq_ctx_wait_fasta first");
+    return MQ_OK;
+}
+
 // host buffers -> device staging -> launch sequence -> page-locked hits, all asynchronous on the context's stream.
 // lens == nullptr: offsets has n + 1 entries and read i is bases[offsets[i], offsets[i+1]).  lens != nullptr (spans form): the
 // whole buffer bases[0, buf_bytes) goes to the device and read i is bases[offsets[i], offsets[i] + lens[i]) (n offsets).
 static int ctx_submit(mq_ctx *c, const uint8_t *bases, uint64_t buf_bytes, const uint64_t *offsets, const uint32_t *lens, uint32_t n,
                       mq_hit *out) {
     mq_index *idx = c->idx;
-    if (c->pending || c->fx_pending) return set_err(MQ_ESTATE, "context has a submitted batch: call mq_ctx_wait / mq_ctx_wait_fasta first");
+    int rc = ctx_require_idle(c);
+    if (rc) return rc;
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
     if (n == 0) return MQ_OK;
-    int rc = use_device(idx);
-    if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
     if ((rc = c->h_off.ensure((uint64_t)n + 1))) return rc;  // (ahead of the rest: the offsets are checked into it)
     uint64_t total, first;
     if (!lens) {
@@ -223,20 +256,22 @@ static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     mq_index *idx = c->idx;
     if (n && (!d_offsets || !d_out)) return set_err(MQ_EINVAL, "bad arguments");
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
-    if (c->pending || c->fx_pending) return set_err(MQ_ESTATE, "context has a submitted batch: call mq_ctx_wait / mq_ctx_wait_fasta first");
-    int rc = use_device(idx);
+    int rc = ctx_require_idle(c);
     if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
     if ((rc = ctx_ensure(c, n, total_bases, list_f16(idx)))) return rc;
     LaunchOpt o;
     o.instrumented = instrumented;
     return launch_map(c, d_bases, d_offsets, n, d_out, st, o);
 }
 
-// ---- device-parsed FASTA chunks: the raw bytes go to the device, the scan kernels of mq_fastx.hpp find the records, map_kernel takes
-// the spans from device memory.  Two steps, so that the host learns the number of records without standing in the stream's way:
-// submit = copy + scan + the scan's result words back (all asynchronous); wait = read them, launch the map kernels, hits and line ends
-// back.  The copy of the NEXT chunk (another context, another stream) runs meanwhile: the link stays busy.
+// ---- device-parsed FASTX pieces: the raw bytes go to the device, a record scanner (mq_fastx.hpp, mq_fastx_lines.hpp) finds the records,
+// map_kernel takes them from device memory.  Two steps, so that the host learns the number of records without standing in the stream's
+// way: submit = copy + scan + the scan's result words back (all asynchronous); wait = read them, launch the map kernels, hits and side
+// arrays back.  The copy of the NEXT piece (another context, another stream) runs meanwhile: the link stays busy.
 static uint32_t fx_line_cap(uint64_t bytes) { return (uint32_t)std::min<uint64_t>(bytes / 16 + 4096, 1u << 28); }
+// grid of the kernels that take a record per thread (at most fx_line_cap / 2 records)
+static dim3 fx_record_grid(const mq_index *idx, uint32_t span_cap) { return dim3(std::max<uint32_t>(1, std::min<uint32_t>(span_cap / 256 + 1, (uint32_t)idx->n_cu * 4u))); }
 
 // MQ_FASTX_FASTA_LINES only: the joined bytes (at most the piece's own) and the header spans of a piece of `bytes` bytes.  A context that
 // never sees the format never has them: mq_ctx_reserve sizes them only once a LINES piece has been submitted on the context.
@@ -248,124 +283,117 @@ static int ctx_ensure_lines(mq_ctx *c, uint64_t bytes) {
     return c->fl_he.ensure(cap + 1);
 }
 
+// buf[0, bytes) to st_bases (which holds it), asynchronously.  The bytes behind the last page boundary (< 4 KB) go through a page-locked
+// buffer of the context: a caller that page-locks the whole pages of its pieces (the feeder, on a mapped file: mq_host_register) gets
+// an asynchronous copy for all the rest, and the last partial page -- which may belong to a range somebody else locks and releases --
+// is never the source of a DMA.
+static int fx_stage_piece(mq_ctx *c, const uint8_t *buf, uint64_t bytes) {
+    int rc;
+    if (!bytes) return MQ_OK;
+    const uintptr_t cut = ((uintptr_t)buf + bytes) & ~(uintptr_t)4095;
+    const uint64_t main_len = cut > (uintptr_t)buf ? (uint64_t)(cut - (uintptr_t)buf) : 0, tail_len = bytes - main_len;
+    if (!c->h_fx_tail && (rc = c->h_fx_tail.alloc(4096))) return rc;
+    if (main_len) HIPCHK(hipMemcpyAsync(c->st_bases, buf, main_len, hipMemcpyHostToDevice, c->stream));
+    if (tail_len) {
+        memcpy(c->h_fx_tail, buf + main_len, tail_len);
+        HIPCHK(hipMemcpyAsync(c->st_bases + main_len, c->h_fx_tail, tail_len, hipMemcpyHostToDevice, c->stream));
+    }
+    return MQ_OK;
+}
+
+// Records of one sequence line in st_bases[b, e) (FASTA: 2 lines, FASTQ: 4): line ends to fx_nl, spans to st_off / st_lens, result words to fx_info
+static void fx_find_records(mq_ctx *c, FxKind kind, uint32_t b, uint32_t e, uint32_t n_tiles) {
+    const uint32_t cap = fx_line_cap(e), grid = fx_grid(c->idx, n_tiles);
+    hipLaunchKernelGGL(count_newlines_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, c->fx_nl, cap, c->fx_info, kind == FxKind::Fastq ? 4u : 2u);
+    hipLaunchKernelGGL(list_newlines_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_nl, cap);
+    const auto spans_kernel = kind == FxKind::Fastq ? fastq_spans_kernel : fasta_spans_kernel;
+    hipLaunchKernelGGL(spans_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
+}
+
+// MQ_FASTX_FASTA_LINES: joined sequences to fl_joined, header spans to fl_hb / fl_he, their offsets / lengths to st_off / st_lens, result words to fx_info
+static void fx_join_records(mq_ctx *c, uint32_t b, uint32_t e, uint32_t n_tiles) {
+    const uint32_t cap = fx_line_cap(e), grid = fx_grid(c->idx, n_tiles);
+    unsigned long long *offs = reinterpret_cast<unsigned long long *>(c->st_off.p);
+    hipLaunchKernelGGL(fl_count_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
+    hipLaunchKernelGGL(fl_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, offs, c->fl_he, cap / 2, c->fx_info);
+    hipLaunchKernelGGL(fl_write_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_info, c->fl_joined, c->fl_hb, c->fl_he, offs, cap / 2);
+    hipLaunchKernelGGL(fl_check_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, offs, c->st_lens, c->fx_info);
+}
+
 static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format) {
     mq_index *idx = c->idx;
-    if (c->pending || c->fx_pending) return set_err(MQ_ESTATE, "context has a submitted batch: call mq_ctx_wait first");
+    int rc = ctx_require_idle(c);
+    if (rc) return rc;
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
     if (bytes >= (1ull << 32) || begin > bytes) return set_err(MQ_EINVAL, "a chunk must be smaller than 4 GB");
-    if (format != MQ_FASTX_FASTA && format != MQ_FASTX_FASTQ && format != MQ_FASTX_FASTA_LINES)
-        return set_err(MQ_EINVAL, "format must be MQ_FASTX_FASTA, MQ_FASTX_FASTQ or MQ_FASTX_FASTA_LINES");
-    const bool wrapped = format == MQ_FASTX_FASTA_LINES;      // records found and their lines joined by mq_fastx_lines.hpp
-    const uint32_t lpr = format == MQ_FASTX_FASTQ ? 4u : 2u;  // lines per record
-    int rc = use_device(idx);
-    if (rc) return rc;
-    const uint32_t n_tiles = (uint32_t)((bytes + FX_TILE - 1) / FX_TILE);
-    const uint32_t cap = fx_line_cap(bytes);
+    const FxKind kind = format == MQ_FASTX_FASTA ? FxKind::Fasta : format == MQ_FASTX_FASTQ ? FxKind::Fastq : format == MQ_FASTX_FASTA_LINES ? FxKind::FastaLines : FxKind::None;
+    if (kind == FxKind::None) return set_err(MQ_EINVAL, "format must be MQ_FASTX_FASTA, MQ_FASTX_FASTQ or MQ_FASTX_FASTA_LINES");
+    if ((rc = use_device(idx))) return rc;
+    const bool wrapped = kind == FxKind::FastaLines;  // (four counts and three offsets per tile, no line-end list); every ensure runs before anything is queued
+    const uint32_t b = (uint32_t)begin, e = (uint32_t)bytes, n_tiles = (uint32_t)((bytes + FX_TILE - 1) / FX_TILE), cap = fx_line_cap(bytes);
     if ((rc = c->st_bases.ensure(bytes + 64))) return rc;
     if ((rc = c->fx_tile_counts.ensure(((uint64_t)n_tiles + 1) * (wrapped ? 4u : 1u)))) return rc;
     if ((rc = c->fx_tile_off.ensure(((uint64_t)n_tiles + 1) * (wrapped ? 3u : 1u)))) return rc;
-    if (wrapped) {
-        c->fl_used = true;
-        if ((rc = ctx_ensure_lines(c, bytes))) return rc;
-    } else if ((rc = c->fx_nl.ensure(cap))) return rc;
+    if (wrapped) c->fl_used = true;
+    if ((rc = wrapped ? ctx_ensure_lines(c, bytes) : c->fx_nl.ensure(cap))) return rc;
     if ((rc = c->st_off.ensure((uint64_t)cap / 2 + 1))) return rc;
     if ((rc = c->st_lens.ensure((uint64_t)cap / 2 + 1))) return rc;
-    if (!c->fx_info && (rc = c->fx_info.alloc(4))) return rc;
-    if (!c->h_fx_info && (rc = c->h_fx_info.alloc(4))) return rc;
-    hipStream_t st = c->stream;
-    if (bytes) {
-        // The bytes behind the last page boundary (< 4 KB) go through a page-locked buffer of the context: a caller that page-locks the
-        // whole pages of its pieces (the feeder, on a mapped file: mq_host_register) gets an asynchronous copy for all the rest, and the
-        // last partial page -- which may belong to a range somebody else locks and releases -- is never the source of a DMA.
-        const uintptr_t end_addr = (uintptr_t)buf + bytes;
-        const uintptr_t cut = end_addr & ~(uintptr_t)4095;
-        uint64_t main_len = cut > (uintptr_t)buf ? (uint64_t)(cut - (uintptr_t)buf) : 0;
-        const uint64_t tail_len = bytes - main_len;
-        if (!c->h_fx_tail && (rc = c->h_fx_tail.alloc(4096))) return rc;
-        if (main_len) HIPCHK(hipMemcpyAsync(c->st_bases, buf, main_len, hipMemcpyHostToDevice, st));
-        if (tail_len) {
-            memcpy(c->h_fx_tail, buf + main_len, tail_len);
-            HIPCHK(hipMemcpyAsync(c->st_bases + main_len, c->h_fx_tail, tail_len, hipMemcpyHostToDevice, st));
-        }
-    }
-    const uint32_t b = (uint32_t)begin, e = (uint32_t)bytes;
-    const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>((n_tiles + 3) / 4, (uint32_t)idx->n_cu * 8u));
-    if (wrapped) {
-        unsigned long long *offs = reinterpret_cast<unsigned long long *>(c->st_off.p);
-        hipLaunchKernelGGL(fl_count_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
-        hipLaunchKernelGGL(fl_scan_kernel, dim3(1), dim3(1024), 0, st, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, offs, c->fl_he, cap / 2, c->fx_info);
-        hipLaunchKernelGGL(fl_write_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_info, c->fl_joined, c->fl_hb, c->fl_he, offs, cap / 2);
-        const dim3 cgrid(std::max<uint32_t>(1, std::min<uint32_t>(cap / 2 / 256 + 1, (uint32_t)idx->n_cu * 4u)));
-        hipLaunchKernelGGL(fl_check_kernel, cgrid, dim3(256), 0, st, offs, c->st_lens, c->fx_info);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, st));
-        c->fx_pending = true;
-        c->fx_lines = true;
-        c->fx_buf = buf;
-        c->fx_begin = b;
-        c->fx_bytes = e;
-        return MQ_OK;
-    }
-    hipLaunchKernelGGL(count_newlines_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, st, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, c->fx_nl, cap, c->fx_info, lpr);
-    hipLaunchKernelGGL(list_newlines_kernel, dim3(grid), dim3(256), 0, st, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_nl, cap);
-    const dim3 sgrid(std::max<uint32_t>(1, std::min<uint32_t>(cap / 2 / 256 + 1, (uint32_t)idx->n_cu * 4u)));
-    if (format == MQ_FASTX_FASTQ)
-        hipLaunchKernelGGL(fastq_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
-    else
-        hipLaunchKernelGGL(fasta_spans_kernel, sgrid, dim3(256), 0, st, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
+    if ((!c->fx_info && (rc = c->fx_info.alloc(4))) || (!c->h_fx_info && (rc = c->h_fx_info.alloc(4)))) return rc;
+    if ((rc = fx_stage_piece(c, buf, bytes))) return rc;
+    if (wrapped) fx_join_records(c, b, e, n_tiles);
+    else fx_find_records(c, kind, b, e, n_tiles);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, st));
-    c->fx_pending = true;
-    c->fx_lines = false;
-    c->fx_lpr = lpr;
-    c->fx_buf = buf;
-    c->fx_begin = b;
+    HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, c->stream));
+    c->fx_kind = kind;  // (the one place a piece becomes pending)
     c->fx_bytes = e;
     return MQ_OK;
 }
 
-static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags) {
-    if (!c->fx_pending) return set_err(MQ_ESTATE, "no FASTA chunk submitted on this context");
-    if (c->fx_lines) return set_err(MQ_ESTATE, "the submitted piece is MQ_FASTX_FASTA_LINES: call mq_ctx_wait_fasta_lines");
-    c->fx_pending = false;
-    mq_index *idx = c->idx;
-    int rc = use_device(idx);
+// The piece in flight is finished: its result words are in h_fx_info when this returns MQ_OK
+static int fx_take_info(mq_ctx *c) {
+    c->fx_kind = FxKind::None;
+    int rc = use_device(c->idx);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
+    return MQ_OK;
+}
+
+// The map kernels on the n records a scanner found (read r: d_lens[r] bytes at d_bytes + d_offsets[r]; d_lens == nullptr: up to d_offsets[r + 1]),
+// the hits back in h_out, side_copies() -- the caller's own arrays, queued behind the hit copy -- and overflowing reads redone
+template <typename F>
+static int fx_map_found(mq_ctx *c, const uint8_t *d_bytes, const uint64_t *d_offsets, const uint32_t *d_lens, uint32_t n, uint64_t total_bytes, F side_copies) {
+    int rc;
+    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
+    if ((rc = ctx_ensure(c, n, total_bytes, list_f16(c->idx)))) return rc;
+    if (getenv("MQ_FX_POISON_HITS")) HIPCHK(hipMemsetAsync(c->st_out, 0xFF, (size_t)n * sizeof(mq_hit), c->stream));  // test hook: a record no wave writes shows
+    LaunchOpt o;
+    o.d_lens = d_lens;
+    if ((rc = launch_map(c, d_bytes, d_offsets, n, c->st_out, c->stream, o))) return rc;
+    HIPCHK(hipMemcpyAsync(c->h_out, c->st_out, (size_t)n * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = side_copies())) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return redo_overflow_device(c, d_bytes, d_offsets, d_lens, n, c->h_out);
+}
+
+static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_ends, uint32_t *n_lines, const mq_hit **hits, uint32_t *flags) {
+    if (c->fx_kind == FxKind::None) return set_err(MQ_ESTATE, "no FASTA chunk submitted on this context");
+    if (c->fx_kind == FxKind::FastaLines) return set_err(MQ_ESTATE, "the submitted piece is MQ_FASTX_FASTA_LINES: call mq_ctx_wait_fasta_lines");
+    int rc = fx_take_info(c);
+    if (rc) return rc;
     const uint32_t lines = c->h_fx_info[0], n = c->h_fx_info[1];
     *flags = c->h_fx_info[2];
-    *n_reads = 0;
-    *n_lines = 0;
+    *n_reads = *n_lines = 0;
     *line_ends = nullptr;
     *hits = nullptr;
-    if (*flags & FX_IRREGULAR) return MQ_OK;  // not "header line, sequence line" all through: the caller parses this chunk on the host
-    if (n == 0) return MQ_OK;
-    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((*flags & FX_IRREGULAR) || n == 0) return MQ_OK;  // irregular (not "header line, sequence line" all through): the caller parses this chunk on the host
     if ((rc = c->h_fx_nl.ensure((uint64_t)lines))) return rc;
-    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
-    if ((rc = ctx_ensure(c, n, c->fx_bytes, list_f16(idx)))) return rc;
-    LaunchOpt o;
-    o.d_lens = c->st_lens;
-    if ((rc = launch_map(c, c->st_bases, c->st_off, n, c->st_out, c->stream, o))) return rc;
-    HIPCHK(hipMemcpyAsync(c->h_out, c->st_out, (size_t)n * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fx_nl, c->fx_nl, (size_t)lines * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    bool over = false;
-    for (uint32_t i = 0; i < n && !over; ++i) over = c->h_out[i].status == MQ_HIT_OVERFLOW;
-    if (over) {  // the rare reads with more Match runs / denser lists than the scratch holds: again with room, from the host's copy of the chunk
-        std::vector<uint64_t> offs(n);
-        std::vector<uint32_t> lens(n);
-        const uint32_t lpr = c->fx_lpr;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t ss = c->h_fx_nl[lpr * i] + 1;
-            uint32_t e = c->h_fx_nl[lpr * i + 1];
-            if (e > ss && c->fx_buf[e - 1] == '\r') --e;
-            offs[i] = ss;
-            lens[i] = e - ss;
-        }
-        if ((rc = redo_overflow(c, c->fx_buf, offs.data(), lens.data(), n, c->h_out))) return rc;
-    }
+    rc = fx_map_found(c, c->st_bases, c->st_off, c->st_lens, n, c->fx_bytes, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(c->h_fx_nl, c->fx_nl, (size_t)lines * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        return MQ_OK;
+    });
+    if (rc) return rc;
     *n_reads = n;
     *n_lines = lines;
     *line_ends = c->h_fx_nl;
@@ -373,56 +401,28 @@ static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_en
     return MQ_OK;
 }
 
-// MQ_FASTX_FASTA_LINES: the result words, the map kernels on (joined bytes, offsets) -- the device form, no lengths -- and hits, header
-// spans and joined lengths back.
+// MQ_FASTX_FASTA_LINES: the map kernels on (joined bytes, offsets) -- the device form, no lengths; hits, header spans, joined lengths back
 static int ctx_wait_fasta_lines(mq_ctx *c, uint32_t *n_reads, const uint32_t **hdr_begin, const uint32_t **hdr_end, const uint32_t **seq_lens,
                                 const mq_hit **hits, uint32_t *flags) {
-    if (!c->fx_pending || !c->fx_lines) return set_err(MQ_ESTATE, "no MQ_FASTX_FASTA_LINES piece submitted on this context");
-    c->fx_pending = false;
-    c->fx_lines = false;
-    mq_index *idx = c->idx;
-    int rc = use_device(idx);
+    if (c->fx_kind != FxKind::FastaLines) return set_err(MQ_ESTATE, "no MQ_FASTX_FASTA_LINES piece submitted on this context");
+    int rc = fx_take_info(c);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
     const uint32_t n = c->h_fx_info[0], joined = c->h_fx_info[1];
     *flags = c->h_fx_info[2];
     *n_reads = 0;
     *hdr_begin = *hdr_end = *seq_lens = nullptr;
     *hits = nullptr;
-    if (*flags & FX_IRREGULAR) return MQ_OK;  // the caller parses this piece on the host
-    if (n == 0) return MQ_OK;
-    if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
+    if ((*flags & FX_IRREGULAR) || n == 0) return MQ_OK;  // irregular: the caller parses this piece on the host
     if ((rc = c->h_fl_hb.ensure((uint64_t)n))) return rc;
     if ((rc = c->h_fl_he.ensure((uint64_t)n))) return rc;
     if ((rc = c->h_fl_lens.ensure((uint64_t)n))) return rc;
-    if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
-    if ((rc = ctx_ensure(c, n, joined, list_f16(idx)))) return rc;
-    if (getenv("MQ_FX_POISON_HITS")) HIPCHK(hipMemsetAsync(c->st_out, 0xFF, (size_t)n * sizeof(mq_hit), c->stream));  // test hook: a record no wave writes shows
-    if ((rc = launch_map(c, c->fl_joined, c->st_off, n, c->st_out, c->stream))) return rc;
-    HIPCHK(hipMemcpyAsync(c->h_out, c->st_out, (size_t)n * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fl_hb, c->fl_hb, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fl_he, c->fl_he, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fl_lens, c->st_lens, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    std::vector<uint32_t> redo;
-    for (uint32_t i = 0; i < n; ++i)
-        if (c->h_out[i].status == MQ_HIT_OVERFLOW) redo.push_back(i);
-    if (!redo.empty()) {  // again with room, from a host copy of THOSE reads' joined bytes (the rest of the piece stays on the device)
-        std::vector<uint64_t> at(redo.size()), so(redo.size() + 1, 0);
-        for (size_t j = 0; j < redo.size(); ++j) {
-            HIPCHK(hipMemcpyAsync(&at[j], c->st_off.p + redo[j], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-            so[j + 1] = so[j] + c->h_fl_lens[redo[j]];
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<uint8_t> sb(so.back() ? so.back() : 1);
-        for (size_t j = 0; j < redo.size(); ++j)
-            if (so[j + 1] > so[j]) HIPCHK(hipMemcpyAsync(sb.data() + so[j], c->fl_joined.p + at[j], (size_t)(so[j + 1] - so[j]), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        std::vector<mq_hit> sh(redo.size());
-        for (mq_hit &h : sh) h.status = MQ_HIT_OVERFLOW;
-        if ((rc = redo_overflow(c, sb.data(), so.data(), nullptr, (uint32_t)redo.size(), sh.data()))) return rc;
-        for (size_t j = 0; j < redo.size(); ++j) c->h_out[redo[j]] = sh[j];
-    }
+    rc = fx_map_found(c, c->fl_joined, c->st_off, nullptr, n, joined, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(c->h_fl_hb, c->fl_hb, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_fl_he, c->fl_he, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_fl_lens, c->st_lens, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        return MQ_OK;
+    });
+    if (rc) return rc;
     *n_reads = n;
     *hdr_begin = c->h_fl_hb;
     *hdr_end = c->h_fl_he;

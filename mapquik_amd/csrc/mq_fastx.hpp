@@ -16,18 +16,56 @@ namespace mq {
 constexpr uint32_t FX_TILE = 16384;  // bytes per wave and pass: 16 iterations of 64 lanes x 16 bytes
 constexpr uint32_t FX_IRREGULAR = 1u;
 
-// per byte of a dword: 0x80 where the byte equals '\n' (exact: no borrow between bytes)
-__device__ __forceinline__ uint32_t nl_mask32(uint32_t w) {
-    const uint32_t x = w ^ 0x0A0A0A0Au;
+// ---- what every record scanner is made of (mq_join.hpp and mq_fastx_lines.hpp take these from here)
+
+// per byte of a dword: 0x80 where the byte equals C (exact: no borrow between bytes)
+template <uint8_t C>
+__device__ __forceinline__ uint32_t eq_mask32(uint32_t w) {
+    const uint32_t x = w ^ (0x01010101u * C);
     return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
 }
+__device__ __forceinline__ uint32_t pack_mask4(uint32_t m) { return ((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u); }
+// bit b of the result: byte b of the 16 bytes equals C
+template <uint8_t C>
+__device__ __forceinline__ uint32_t eq_bits16(const uint4 v) {
+    return pack_mask4(eq_mask32<C>(v.x)) | (pack_mask4(eq_mask32<C>(v.y)) << 4) | (pack_mask4(eq_mask32<C>(v.z)) << 8) | (pack_mask4(eq_mask32<C>(v.w)) << 12);
+}
+// bit b of the result: position p0 + b lies in front of x (P: uint32_t, or uint64_t in the join kernels; nothing here wraps, wherever p0 lies)
+template <typename P>
+__device__ __forceinline__ uint32_t below16(P p0, P x) {
+    const P d = (x > p0 ? x : p0) - p0;
+    return (1u << (d < 16u ? (uint32_t)d : 16u)) - 1u;
+}
+// bit b of the result: position p0 + b lies in [begin, end)
+template <typename P>
+__device__ __forceinline__ uint32_t in_range16(P p0, P begin, P end) { return below16(p0, end) & ~below16(p0, begin); }
 // bit b of the result: byte b of the 16 bytes is '\n' and its position p0 + b lies in [begin, end)
-__device__ __forceinline__ uint32_t nl_bits16(const uint4 v, uint32_t p0, uint32_t begin, uint32_t end) {
-    auto pack = [](uint32_t m) { return ((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u); };
-    uint32_t bits = pack(nl_mask32(v.x)) | (pack(nl_mask32(v.y)) << 4) | (pack(nl_mask32(v.z)) << 8) | (pack(nl_mask32(v.w)) << 12);
-    if (p0 < begin) bits &= begin - p0 >= 16u ? 0u : (0xFFFFu << (begin - p0));
-    if (p0 + 16u > end) bits &= p0 >= end ? 0u : (0xFFFFu >> (p0 + 16u - end));
-    return bits;
+__device__ __forceinline__ uint32_t nl_bits16(const uint4 v, uint32_t p0, uint32_t begin, uint32_t end) { return eq_bits16<'\n'>(v) & in_range16(p0, begin, end); }
+
+// The tiles [lo, hi) of this thread of a 1,024-thread workgroup that scans n_tiles tile counts: equal runs, in thread order
+__device__ __forceinline__ void tile_span(uint32_t n_tiles, uint32_t &lo, uint32_t &hi) {
+    const uint32_t per = (n_tiles + 1023u) / 1024u;
+    lo = threadIdx.x * per < n_tiles ? threadIdx.x * per : n_tiles;
+    hi = lo + per < n_tiles ? lo + per : n_tiles;
+}
+// Exclusive scan of `mine` over the 1,024 threads of the workgroup, in thread order: returns op over the threads below (T() for thread 0) and
+// leaves the inclusive values in part[], the total in part[1023].  op(below, own) is associative with T() as its identity.
+struct ScanSum {
+    template <typename T>
+    __device__ T operator()(T below, T own) const { return below + own; }
+};
+template <typename T, typename Op = ScanSum>
+__device__ __forceinline__ T block_excl_scan_1024(T *part, T mine, Op op = Op()) {
+    const uint32_t t = threadIdx.x;
+    part[t] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        const T v = t >= d ? part[t - d] : T();
+        __syncthreads();
+        part[t] = op(v, part[t]);
+        __syncthreads();
+    }
+    return t ? part[t - 1] : T();
 }
 
 // buf: 16-byte aligned, readable up to the next multiple of 16 behind `end`
@@ -52,19 +90,11 @@ __global__ __launch_bounds__(1024) void scan_tiles_kernel(const uint8_t *__restr
                                                           uint32_t n_tiles, uint32_t *__restrict__ tile_off, uint32_t *__restrict__ nl_pos, uint32_t nl_cap,
                                                           uint32_t *__restrict__ info, uint32_t lines_per_record) {
     __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (n_tiles + 1023u) / 1024u;
-    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
-    uint32_t sum = 0;
+    const uint32_t t = threadIdx.x;
+    uint32_t lo, hi, sum = 0;
+    tile_span(n_tiles, lo, hi);
     for (uint32_t i = lo; i < hi; ++i) sum += tile_counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint32_t v = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
+    uint32_t run = block_excl_scan_1024(part, sum);
     for (uint32_t i = lo; i < hi; ++i) {
         tile_off[i] = run;
         run += tile_counts[i];

@@ -20,11 +20,6 @@
 
 namespace mq {
 
-__device__ __forceinline__ uint32_t gt_mask32(uint32_t w) {  // 0x80 where the byte equals '>' (nl_mask32's construction)
-    const uint32_t x = w ^ 0x3E3E3E3Eu;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-
 // What a lane knows of its 16 bytes at p0 (16-bit masks, bit b = byte p0 + b) before the state reaches it
 struct FlLane {
     uint4 v;        // the bytes (zero when p0 >= end: nothing is loaded there)
@@ -38,15 +33,13 @@ struct FlLane {
 __device__ __forceinline__ FlLane fl_lane16(const uint8_t *__restrict__ buf, uint32_t p0, uint32_t begin, uint32_t end, uint32_t lane) {
     FlLane L;
     L.v = make_uint4(0, 0, 0, 0);
-    uint32_t nl = 0, cr = 0, gt = 0, valid = 0;
+    const uint32_t valid = in_range16(p0, begin, end);
+    uint32_t nl = 0, cr = 0, gt = 0;
     if (p0 < end) {
         L.v = *reinterpret_cast<const uint4 *>(buf + p0);
-        nl = pack_mask4(nl_mask32(L.v.x)) | (pack_mask4(nl_mask32(L.v.y)) << 4) | (pack_mask4(nl_mask32(L.v.z)) << 8) | (pack_mask4(nl_mask32(L.v.w)) << 12);
-        cr = pack_mask4(cr_mask32(L.v.x)) | (pack_mask4(cr_mask32(L.v.y)) << 4) | (pack_mask4(cr_mask32(L.v.z)) << 8) | (pack_mask4(cr_mask32(L.v.w)) << 12);
-        gt = pack_mask4(gt_mask32(L.v.x)) | (pack_mask4(gt_mask32(L.v.y)) << 4) | (pack_mask4(gt_mask32(L.v.z)) << 8) | (pack_mask4(gt_mask32(L.v.w)) << 12);
-        valid = 0xFFFFu;
-        if (p0 < begin) valid &= begin - p0 >= 16u ? 0u : (0xFFFFu << (begin - p0));
-        if (p0 + 16u > end) valid &= 0xFFFFu >> (p0 + 16u - end);
+        nl = eq_bits16<'\n'>(L.v);
+        cr = eq_bits16<'\r'>(L.v);
+        gt = eq_bits16<'>'>(L.v);
     }
     // line starts: behind a '\n', and the piece's first byte
     uint32_t prev_nl = (uint32_t)__shfl_up((int)(nl >> 15), 1, 64);
@@ -136,55 +129,43 @@ __global__ __launch_bounds__(256) void fl_count_kernel(const uint8_t *__restrict
 __global__ __launch_bounds__(1024) void fl_scan_kernel(const uint8_t *__restrict__ buf, uint32_t begin, uint32_t end, const uint32_t *__restrict__ tile_counts,
                                                        uint32_t n_tiles, uint32_t *__restrict__ tile_off, unsigned long long *__restrict__ offsets,
                                                        uint32_t *__restrict__ hdr_end, uint32_t span_cap, uint32_t *__restrict__ info) {
-    __shared__ uint32_t eff[1024], part_k[1024], part_h[1024];
-    const uint32_t t = threadIdx.x, per = (n_tiles + 1023u) / 1024u;
-    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    __shared__ uint32_t eff[1024];
+    __shared__ uint2 part[1024];  // x: kept bytes, y: header starts
+    const uint32_t t = threadIdx.x;
+    uint32_t lo, hi;
+    tile_span(n_tiles, lo, hi);
     // the state: last event wins, over this thread's tiles, then over the threads
     uint32_t mine = FL_EV_NONE;
     for (uint32_t i = lo; i < hi; ++i) {
         const uint32_t e = tile_counts[4u * i + 3u];
         if (e) mine = e;
     }
-    eff[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint32_t v = t >= d ? eff[t - d] : FL_EV_NONE;
-        __syncthreads();
-        if (!eff[t]) eff[t] = v;
-        __syncthreads();
-    }
-    const uint32_t st_in = t ? (eff[t - 1] & 1u) : 0u;  // (FL_EV_NONE: no event in front of this thread's tiles -- outside a header line, as the piece begins)
+    // (FL_EV_NONE: no event in front of this thread's tiles -- outside a header line, as the piece begins)
+    const uint32_t st_in = block_excl_scan_1024(eff, mine, [](uint32_t below, uint32_t own) { return own ? own : below; }) & 1u;
     // kept bytes and header starts of this thread's tiles, now that the state entering each is known
-    uint32_t st = st_in, sum_k = 0, sum_h = 0;
+    const auto add = [](uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); };
+    const auto counted = [&](uint32_t i, uint32_t st) {  // tile i entered in state st
+        return make_uint2(tile_counts[4u * i] + (st ? 0u : tile_counts[4u * i + 1u]), tile_counts[4u * i + 2u]);
+    };
+    uint32_t st = st_in;
+    uint2 sum = make_uint2(0u, 0u);
     for (uint32_t i = lo; i < hi; ++i) {
-        sum_k += tile_counts[4u * i] + (st ? 0u : tile_counts[4u * i + 1u]);
-        sum_h += tile_counts[4u * i + 2u];
+        sum = add(sum, counted(i, st));
         const uint32_t e = tile_counts[4u * i + 3u];
         if (e) st = e & 1u;
     }
-    part_k[t] = sum_k;
-    part_h[t] = sum_h;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint32_t vk = t >= d ? part_k[t - d] : 0u, vh = t >= d ? part_h[t - d] : 0u;
-        __syncthreads();
-        part_k[t] += vk;
-        part_h[t] += vh;
-        __syncthreads();
-    }
-    uint32_t run_k = part_k[t] - sum_k, run_h = part_h[t] - sum_h;
+    uint2 run = block_excl_scan_1024(part, sum, add);
     st = st_in;
     for (uint32_t i = lo; i < hi; ++i) {
-        tile_off[3u * i] = run_k;
-        tile_off[3u * i + 1u] = run_h;
+        tile_off[3u * i] = run.x;
+        tile_off[3u * i + 1u] = run.y;
         tile_off[3u * i + 2u] = st;
-        run_k += tile_counts[4u * i] + (st ? 0u : tile_counts[4u * i + 1u]);
-        run_h += tile_counts[4u * i + 2u];
+        run = add(run, counted(i, st));
         const uint32_t e = tile_counts[4u * i + 3u];
         if (e) st = e & 1u;
     }
     if (t == 1023u) {
-        const uint32_t n = part_h[1023], joined = part_k[1023];
+        const uint32_t n = part[1023].y, joined = part[1023].x;
         const bool bad = (end > begin && buf[begin] != '>') || n > span_cap;
         if (!bad) {
             offsets[n] = joined;

@@ -7,6 +7,9 @@
 constexpr uint32_t MQ_MAX_REF_ID = 1u << 24;
 struct mq_index;
 
+// A piece of a FASTX file whose records the device finds (mq_ctx_submit_fastx): none in flight, or its format
+enum class FxKind { None, Fasta, Fastq, FastaLines };
+
 // One stream slot: everything a map launch sequence writes (work counters, Match scratch, minimizer lists,
 // events) plus the staging buffers of the host-buffer entry points.  Launch sequences of DIFFERENT contexts of one index
 // may be in flight together (the index itself is read-only once finalized); one context runs one sequence at a time.
@@ -49,11 +52,8 @@ struct mq_ctx {
     Buf<uint32_t> fl_hb, fl_he;
     PinnedBuf<uint32_t> h_fl_hb, h_fl_he, h_fl_lens;
     bool fl_used = false;           // a LINES piece has been submitted on this context: mq_ctx_reserve sizes the buffers above too
-    bool fx_lines = false;          // the piece in flight is a LINES piece (mq_ctx_wait_fasta_lines finishes it)
-    bool fx_pending = false;
-    uint32_t fx_lpr = 2;            // lines per record of the piece in flight (FASTA 2, FASTQ 4)
-    const uint8_t *fx_buf = nullptr;
-    uint32_t fx_begin = 0, fx_bytes = 0;
+    FxKind fx_kind = FxKind::None;  // the piece in flight (mq_ctx_wait_fasta finishes Fasta / Fastq, mq_ctx_wait_fasta_lines FastaLines)
+    uint32_t fx_bytes = 0;          // ... and its size
     // a submitted, not yet waited-for batch
     bool pending = false;
     const uint8_t *p_bases = nullptr;
@@ -275,6 +275,9 @@ static int ensure_geometry_once(mq_index *idx) {
 
 // workgroups of the fused launch sequence for n reads (ensure_geometry must have succeeded)
 static uint32_t fused_grid(const mq_index *idx, uint32_t n) { return std::min<uint32_t>(idx->grid_fused, (n + MAP_WAVES - 1) / MAP_WAVES); }
+
+// workgroups (of 4 waves) of a record scanner's tile-walking kernels: a wave per 16-KB tile, at most 8 workgroups per CU
+static uint32_t fx_grid(const mq_index *idx, uint32_t n_tiles) { return std::max<uint32_t>(1, std::min<uint32_t>((n_tiles + 3) / 4, (uint32_t)idx->n_cu * 8u)); }
 
 static int ensure_geometry(mq_index *idx) {
     std::call_once(idx->geometry_once, [idx] { idx->geometry_rc = ensure_geometry_once(idx); });  // contexts of one index start concurrently

@@ -14,13 +14,6 @@
 
 namespace mq {
 
-// per byte of a dword: 0x80 where the byte equals '\r' (nl_mask32's construction)
-__device__ __forceinline__ uint32_t cr_mask32(uint32_t w) {
-    const uint32_t x = w ^ 0x0D0D0D0Du;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-__device__ __forceinline__ uint32_t pack_mask4(uint32_t m) { return ((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u); }
-
 // Bit b of the result: byte p0 + b is a kept byte of R.  v: the 16 bytes at p0 (zero when p0 >= end: nothing is loaded there).  The byte
 // behind a lane's last one is the first byte of the lane above; the last lane reads that one byte itself.  All 64 lanes call this.
 __device__ __forceinline__ uint32_t join_keep16(const uint8_t *__restrict__ buf, uint64_t p0, uint64_t begin, uint64_t end, uint32_t lane, uint4 &v) {
@@ -28,15 +21,12 @@ __device__ __forceinline__ uint32_t join_keep16(const uint8_t *__restrict__ buf,
     v = make_uint4(0, 0, 0, 0);
     if (p0 < end) {
         v = *reinterpret_cast<const uint4 *>(buf + p0);
-        nl = pack_mask4(nl_mask32(v.x)) | (pack_mask4(nl_mask32(v.y)) << 4) | (pack_mask4(nl_mask32(v.z)) << 8) | (pack_mask4(nl_mask32(v.w)) << 12);
-        cr = pack_mask4(cr_mask32(v.x)) | (pack_mask4(cr_mask32(v.y)) << 4) | (pack_mask4(cr_mask32(v.z)) << 8) | (pack_mask4(cr_mask32(v.w)) << 12);
-        if (p0 + 16u > end) nl |= (0xFFFFu << (uint32_t)(end - p0)) & 0xFFFFu;
+        nl = eq_bits16<'\n'>(v) | (~below16(p0, end) & 0xFFFFu);
+        cr = eq_bits16<'\r'>(v);
     }
     uint32_t next = (uint32_t)__shfl_down((int)(nl & 1u), 1, 64);
     if (lane == 63u) next = p0 + 16u >= end ? 1u : (buf[p0 + 16u] == '\n' ? 1u : 0u);
-    uint32_t keep = ~(nl | (cr & ((nl >> 1) | (next << 15)))) & 0xFFFFu;
-    if (p0 < begin) keep &= begin - p0 >= 16u ? 0u : (0xFFFFu << (uint32_t)(begin - p0));
-    return keep;
+    return ~(nl | (cr & ((nl >> 1) | (next << 15)))) & ~below16(p0, begin) & 0xFFFFu;
 }
 
 // buf: 16-byte aligned, readable up to the next multiple of 16 behind `end`; tile t = 16 KB from (begin & ~15) + t * FX_TILE
@@ -61,24 +51,16 @@ __global__ __launch_bounds__(256) void join_count_kernel(const uint8_t *__restri
 __global__ __launch_bounds__(1024) void join_scan_kernel(const uint32_t *__restrict__ tile_counts, uint32_t n_tiles, unsigned long long *__restrict__ tile_off,
                                                          unsigned long long *__restrict__ total) {
     __shared__ unsigned long long part[1024];
-    const uint32_t t = threadIdx.x, per = (n_tiles + 1023u) / 1024u;
-    const uint32_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    uint32_t lo, hi;
     unsigned long long sum = 0;
+    tile_span(n_tiles, lo, hi);
     for (uint32_t i = lo; i < hi; ++i) sum += tile_counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const unsigned long long v = t >= d ? part[t - d] : 0ull;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - sum;
+    unsigned long long run = block_excl_scan_1024(part, sum);
     for (uint32_t i = lo; i < hi; ++i) {
         tile_off[i] = run;
         run += tile_counts[i];
     }
-    if (t == 1023u) *total = part[1023];
+    if (threadIdx.x == 1023u) *total = part[1023];
 }
 
 // 16 / 8 / 4 / 2 bytes to d, d of any alignment (one store each: the target takes unaligned global accesses)

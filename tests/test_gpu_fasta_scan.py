@@ -300,3 +300,108 @@ def test_native_driver_fasta_device_and_host_parse(mq, oracle, world, tmp_path):
                 assert r.returncode == 0, r.stderr
                 assert open(prefix + ".paf").read() == want_txt, (str(path), chunk, env)
                 assert open(prefix + ".unmapped.out").read().split() == [n for n, w_ in zip(rn, want) if not w_["mapped"]]
+
+
+def _map(ix, seqs):
+    bases = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(s) for s in seqs])
+    return ix.map_batch(bases, offs)
+
+
+def _line_ends(txt):
+    """where a host parser finds the line ends: every '\\n', and the end of a last line without one"""
+    pos = np.flatnonzero(np.frombuffer(txt, dtype=np.uint8) == 0x0A).tolist()
+    return pos if txt.endswith(b"\n") else pos + [len(txt)]
+
+
+@pytest.mark.parametrize("fastq", [False, True])
+def test_more_than_1024_tiles(mq, world, fastq):
+    """a piece of a little over 1,024 tiles of 16,384 bytes (the world's records, repeated): scan_tiles_kernel's threads take more than
+    one tile each.  Hits against map_batch, line ends and record count against the line split."""
+    txt, seqs = _fastq(world) if fastq else _fasta(world)
+    reps = 17_000_000 // len(txt) + 1
+    txt, seqs = txt * reps, seqs * reps
+    assert len(txt) > 1024 * 16384 + 200_000
+    ix = world["ix"]
+    want = _map(ix, seqs)
+    ctx = ix.context()
+    ctx.submit_fasta(np.frombuffer(txt, dtype=np.uint8), fastq=fastq)
+    hits, lines, flags = ctx.wait_fasta()
+    ctx.close()
+    assert flags == 0 and hits.size == len(seqs) >= 1400 and lines.size == (4 if fastq else 2) * len(seqs)
+    assert lines.tolist() == _line_ends(txt)
+    assert np.array_equal(hits.view(np.uint8), want.view(np.uint8))
+    assert (want["status"] == 1).sum() > 1000
+
+
+@pytest.fixture(scope="module")
+def overflowing(mq, simlib):
+    """the k = 1 mosaic read of test_gpu_fasta_lines.py::test_overflow_reads_are_redone (more Match runs than the default scratch holds:
+    status 2 on the plain device form), then five ordinary reads, then two more overflowing ones; map_batch's hits of the eight"""
+    import mosaic
+    from hipmem import DevBuf, device_sync
+    g, off, names = mosaic.mosaic_genome(simlib)
+    ps, bases, offs, _ = mosaic.leg("k1", g, off)
+    ix = mq.Index(mq.Params(**ps))
+    for r in range(off.size - 1):
+        ix.add_ref(r, names[r], g[int(off[r]):int(off[r + 1])])
+    ix.finalize()
+    n = offs.size - 1
+    db, do, out = DevBuf.from_numpy(bases), DevBuf.from_numpy(offs), DevBuf(n * mq.hit_dtype.itemsize)
+    ix.reserve(n, int(offs[-1]))
+    ix.map_batch_device(db.ptr, do.ptr, n, int(offs[-1]), out.ptr)
+    device_sync()
+    dev = out.to_numpy(mq.hit_dtype, n)
+    for x in (db, do, out):
+        x.free()
+    over = np.flatnonzero(dev["status"] == mq.MQ_HIT_OVERFLOW)
+    assert over.size >= 3  # they do overflow on the plain device form
+    pick = [int(over[0])] + [k for k in range(n) if k not in over][:5] + [int(k) for k in over[1:3]]
+    o = offs.astype(np.int64)
+    rd = [(b"m%d" % k, bases[o[k]:o[k + 1]].tobytes()) for k in pick]
+    want = _map(ix, [s for _, s in rd])
+    assert not (want["status"] == mq.MQ_HIT_OVERFLOW).any()
+    return dict(ix=ix, rd=rd, want=want)
+
+
+@pytest.mark.parametrize("form", ["fasta", "fasta_crlf", "fasta_no_final_newline", "fastq"])
+def test_overflow_reads_are_redone_through_wait_fasta(mq, overflowing, form):
+    """mq_ctx_wait_fasta maps the reads that came back MQ_HIT_OVERFLOW again, with room: no status 2 comes back and the hits are
+    map_batch's -- with CR-LF too (the redo cuts the '\\r' exactly as the span kernel did), without a final newline, and from FASTQ"""
+    ix, rd, want = overflowing["ix"], overflowing["rd"], overflowing["want"]
+    nl = b"\r\n" if form == "fasta_crlf" else b"\n"
+    if form == "fastq":
+        piece = b"".join(b"@" + i + b"\n" + s + b"\n+\n" + b"I" * len(s) + b"\n" for i, s in rd)
+    else:
+        piece = b"".join(b">" + i + nl + s + nl for i, s in rd)
+    if form == "fasta_no_final_newline":
+        piece = piece[:-1]
+    ctx = ix.context()
+    ctx.submit_fasta(np.frombuffer(piece, dtype=np.uint8), fastq=form == "fastq")
+    hits, lines, flags = ctx.wait_fasta()
+    ctx.close()
+    assert flags == 0 and hits.size == len(rd) and lines.tolist() == _line_ends(piece)
+    assert not (hits["status"] == mq.MQ_HIT_OVERFLOW).any()
+    assert np.array_equal(hits.view(np.uint8), want.view(np.uint8))
+
+
+@pytest.mark.parametrize("fastq", [False, True])
+def test_every_record_is_written_into_a_poisoned_hit_buffer(mq, world, monkeypatch, fastq):
+    """MQ_FX_POISON_HITS: the context's device hit buffer is filled with 0xFF before the map kernels of the piece are launched; a record
+    no wave writes would keep status 0xFFFFFFFF.  The hook used to be read by mq_ctx_wait_fasta_lines alone -- against a library of
+    that time this test passes without exercising anything; since the two waits share the code that maps a found piece (fx_map_found)
+    the hook covers this route and the check is real."""
+    from test_gpu_poison import _assert_all_written
+    txt, seqs = _fastq(world) if fastq else _fasta(world)
+    ix = world["ix"]
+    want = _map(ix, seqs)
+    ctx = ix.context()
+    monkeypatch.setenv("MQ_FX_POISON_HITS", "1")
+    ctx.submit_fasta(np.frombuffer(txt, dtype=np.uint8), fastq=fastq)
+    hits, lines, flags = ctx.wait_fasta()
+    monkeypatch.delenv("MQ_FX_POISON_HITS")
+    ctx.close()
+    assert flags == 0 and hits.size == 700
+    _assert_all_written(hits)
+    assert np.array_equal(hits.view(np.uint8), want.view(np.uint8))

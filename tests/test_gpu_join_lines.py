@@ -288,3 +288,15 @@ def test_index_of_joined_records_other_paths(mq, genome, monkeypatch, how):
     _same_index(a, b, w["names"], seqs, w["reads"])
     a.close()
     b.close()
+
+
+def test_one_region_of_more_than_1024_tiles(mq):
+    """17 MB wrapped at 80 columns, CR-LF in its second half: join_scan_kernel's threads take more than one tile each"""
+    rng = np.random.default_rng(1024)
+    region = _wrap(_bases(rng, 9_000_000), 80, b"\n") + _wrap(_bases(rng, 8_000_000), 80, b"\r\n", final=False)
+    assert len(region) > 1024 * TILE + 200_000
+    blob = b">big\n" + region + b">next\n"
+    ix = mq.Index(mq.Params())
+    _stage(mq, ix, blob, (), rng)
+    assert ix.staged_sequence(5, len(region)).tobytes() == model(region)
+    ix.close()
