@@ -1,0 +1,302 @@
+// map_pipeline.hpp -- the map phase of the native driver (mapquik_main.cc): chunks of reads from the feeder go to the GPUs through the
+// stream slots of the submitting threads, come back with their hits, are formatted as PAF by a small pool and written in input order
+// by the calling thread (main_thread_mer, src/closures.rs:117-123).  One mutex and one condition variable guard the queue between
+// submitters and formatters and the map of formatted chunks waiting for their turn.
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstdio>
+#include <deque>
+#include <map>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "fastx_feeder.hpp"
+#include "mapquik_host.hpp"
+
+namespace mapquik {
+
+using Clock = std::chrono::steady_clock;
+inline double secs(Clock::time_point a) { return std::chrono::duration<double>(Clock::now() - a).count(); }
+inline long long us_since(Clock::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - a).count(); }
+
+// The records of a chunk that was submitted unparsed (mq_ctx_submit_fastx): hits and line ends (or header spans, fx_format
+// MQ_FASTX_FASTA_LINES) come back together and become the chunk's spans and hits.  A chunk the device hands back MQ_FASTA_IRREGULAR
+// (sequences over several lines, blank lines, ...) goes the old way: parsed here, its spans submitted, waited for.  Returns whether it did.
+inline bool collect_device_records(mq_ctx *ctx, feeder::Chunk &c, uint32_t fx_format) {
+    const bool wrapped = fx_format == MQ_FASTX_FASTA_LINES;
+    uint32_t n = 0, n_lines = 0, flags = 0;
+    const uint32_t *line_ends = nullptr, *hdr_begin = nullptr, *hdr_end = nullptr, *seq_lens = nullptr;
+    const mq_hit *hits = nullptr;
+    if (wrapped ? mq_ctx_wait_fasta_lines(ctx, &n, &hdr_begin, &hdr_end, &seq_lens, &hits, &flags) != MQ_OK
+                : mq_ctx_wait_fasta(ctx, &n, &line_ends, &n_lines, &hits, &flags) != MQ_OK)
+        throw Error(std::string(wrapped ? "mq_ctx_wait_fasta_lines: " : "mq_ctx_wait_fasta: ") + last_error());
+    if (flags & MQ_FASTA_IRREGULAR) {
+        c.materialize();  // a view of the mapped file: the parser compacts sequence lines in place
+        feeder::parse_chunk(c, fx_format == MQ_FASTX_FASTQ);
+        c.hits.resize(c.starts.size());
+        if (!c.starts.empty() && (mq_ctx_submit_spans(ctx, c.buf, c.bytes, c.starts.data(), c.lens.data(), (uint32_t)c.starts.size(), c.hits.data()) != MQ_OK ||
+                                  mq_ctx_wait(ctx) != MQ_OK))
+            throw Error(std::string("mq_ctx_submit_spans: ") + last_error());
+        return true;
+    }
+    if (wrapped) feeder::spans_from_headers(c, hdr_begin, hdr_end, seq_lens, n);
+    else feeder::spans_from_line_ends(c, line_ends, n_lines, fx_format == MQ_FASTX_FASTQ ? 4u : 2u);
+    c.hits.assign(hits, hits + n);
+    return false;
+}
+
+// A mapped chunk's output: PAF lines of the mapped reads (src/mers.rs:181), and of the unmapped ones the names (want_unmapped) and the
+// records as FASTA (want_fasta, for a second pass).  Returns the error text for a hit that is neither, "" else.
+inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta) {
+    std::string id;
+    c.paf.reserve(c.lens.size() * 96);
+    for (size_t i = 0; i < c.lens.size(); ++i) {
+        const mq_hit &h = c.hits[i];
+        if (h.status == MQ_HIT_MAPPED) {
+            pw.append(c.paf, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);  // src/mers.rs:181
+            continue;
+        }
+        id.assign((const char *)c.buf + c.ids[i].off, c.ids[i].len);
+        if (h.status != MQ_HIT_UNMAPPED) return "find_matches: read " + id + " could not be processed";
+        if (want_unmapped) { c.unmapped += id; c.unmapped.push_back('\n'); }
+        if (want_fasta) {
+            c.unmapped_fa.push_back('>');
+            c.unmapped_fa += id;
+            c.unmapped_fa.push_back('\n');
+            if (!c.regions.empty()) feeder::append_joined_region(c, c.regions[i].first, c.regions[i].second, c.unmapped_fa);  // (joined on the device: no starts)
+            else c.unmapped_fa.append((const char *)c.buf + c.starts[i], c.lens[i]);
+            c.unmapped_fa.push_back('\n');
+        }
+    }
+    return std::string();
+}
+
+class MapPipeline {
+  public:
+    struct Config {
+        int n_format;        // PAF formatters
+        uint32_t fx_format;  // MQ_FASTX_* of the chunks that come unparsed
+        long fail_at;        // MQ_DRIVER_FAIL_AT (test hook): the submitter that takes this chunk number reports a failure; -1: none
+    };
+    // slots[w]: the stream slots of submitter w (n_sub submitters per GPU, each over its GPU's index); index: where the formatters look
+    // reference names up; paf, unmapped, unmapped_fa: the open output files, the last two may be null
+    MapPipeline(feeder::Feeder &feed, std::vector<std::vector<Ctx>> &slots, const ReadOnlyIndex &index, FILE *paf, FILE *unmapped, FILE *unmapped_fa, const Config &cfg)
+        : feed_(feed), slots_(slots), index_(index), paf_(paf), unm_(unmapped), ufa_(unmapped_fa), cfg_(cfg), submitters_left_((int)slots.size()) {}
+
+    // Starts the submitters and the formatters, writes on the calling thread, joins.  On a failure the feeder is aborted and the first
+    // error is thrown.
+    void run() {
+        std::vector<std::thread> submitters, formatters;
+        for (size_t w = 0; w < slots_.size(); ++w) submitters.emplace_back([this, w] { submit_loop(w); });
+        for (int f = 0; f < cfg_.n_format; ++f) formatters.emplace_back([this] { format_loop(); });
+        write_in_order();
+        // On a failure the chunks in flight are never recycled, so the feeder's workers (waiting for a buffer) and the submitters
+        // (waiting for a chunk) would wait forever: the feeder is told to give up, which wakes both.
+        if (failed()) feed_.abort();
+        for (auto &t : submitters) t.join();
+        cv_.notify_all();
+        for (auto &t : formatters) t.join();
+        if (!werr_.empty()) throw Error(werr_);
+    }
+
+    // MQ_DRIVER_TIMING (diagnostic, stderr): where the map phase's threads spent their time
+    void report(double phase_secs) const {
+        fprintf(stderr, "map phase %.3f s; summed over threads: submit %.3f s, finish (wait + spans) %.3f s, waiting for a chunk %.3f s (%d submitters), "
+                        "format %.3f s (%d formatters), write + recycle %.3f s\n", phase_secs, t_submit_us_ / 1e6, t_finish_us_ / 1e6, t_fetch_us_ / 1e6, (int)slots_.size(),
+                t_format_us_ / 1e6, cfg_.n_format, t_write_us_ / 1e6);
+        fprintf(stderr, "unparsed chunks %llu irregular %llu\n", (unsigned long long)n_unparsed_.load(), (unsigned long long)n_irregular_.load());
+    }
+
+  private:
+    using Chunk = feeder::Chunk;
+
+    // one submitting thread: its stream slots and the chunks in flight in them
+    struct Submitter {
+        MapPipeline &p;
+        std::vector<Ctx> &ctx;
+        std::vector<Chunk *> inflight;
+        std::vector<size_t> age;  // submit order of the chunk in the slot
+        size_t submitted = 0;
+        Submitter(MapPipeline &p_, std::vector<Ctx> &ctx_) : p(p_), ctx(ctx_), inflight(ctx_.size(), nullptr), age(ctx_.size(), 0) {}
+
+        int free_slot() const {
+            for (int sl = 0; sl < (int)inflight.size(); ++sl)
+                if (!inflight[sl]) return sl;
+            return -1;
+        }
+        // the busy slot that was submitted longest ago (-1: none is busy)
+        int oldest_busy() const {
+            int best = -1;
+            for (int sl = 0; sl < (int)inflight.size(); ++sl)
+                if (inflight[sl] && (best < 0 || age[sl] < age[best])) best = sl;
+            return best;
+        }
+        void submit(Chunk *c, int sl) {
+            const auto ts0 = Clock::now();
+            if (c->unparsed) {
+                if (mq_ctx_submit_fastx(ctx[sl].handle(), c->buf, c->begin, c->bytes, p.cfg_.fx_format) != MQ_OK) throw Error(std::string("mq_ctx_submit_fastx: ") + last_error());
+            } else if (mq_ctx_submit_spans(ctx[sl].handle(), c->buf, c->bytes, c->starts.data(), c->lens.data(), (uint32_t)c->starts.size(), c->hits.data()) != MQ_OK) {
+                throw Error(std::string("mq_ctx_submit_spans: ") + last_error());
+            }
+            p.t_submit_us_ += us_since(ts0);
+            inflight[sl] = c;
+            age[sl] = submitted++;
+        }
+        // waits for the slot's chunk and passes it to the formatters (after a failure too: the writer counts on every chunk)
+        void finish_slot(int sl) {
+            if (!inflight[sl]) return;
+            const auto tf0 = Clock::now();
+            Chunk *c = inflight[sl];
+            try {
+                if (c->unparsed) {  // records found on the device
+                    ++p.n_unparsed_;
+                    if (collect_device_records(ctx[sl].handle(), *c, p.cfg_.fx_format)) ++p.n_irregular_;
+                } else if (mq_ctx_wait(ctx[sl].handle()) != MQ_OK) {
+                    throw Error(std::string("mq_ctx_wait: ") + last_error());
+                }
+            } catch (const std::exception &e) { p.fail(e.what()); }
+            c->unparsed = false;
+            inflight[sl] = nullptr;
+            p.to_formatters(c);
+            p.t_finish_us_ += us_since(tf0);
+        }
+    };
+
+    void fail(const std::string &m) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (werr_.empty()) werr_ = m;
+        }
+        cv_.notify_all();
+    }
+    bool failed() {
+        std::lock_guard<std::mutex> lk(mu_);
+        return !werr_.empty();
+    }
+    void to_formatters(Chunk *c) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            to_format_.push_back(c);
+        }
+        cv_.notify_all();
+    }
+
+    void submit_loop(size_t worker) {
+        Submitter s(*this, slots_[worker]);
+        try {
+            for (;;) {
+                if (failed()) break;  // somebody failed: stop pulling chunks
+                // Never wait for a new chunk while holding submitted ones: the writer may be waiting for exactly one of
+                // them while every other buffer of the pool sits behind the writer (formatted, out of turn) -- then no
+                // new chunk can ever be parsed.  With nothing ready, the oldest submitted chunk is passed on first.
+                bool end = false;
+                Chunk *c = feed_.poll(end);
+                if (!c) {
+                    if (end) break;
+                    const int busy = s.oldest_busy();
+                    if (busy >= 0) {
+                        s.finish_slot(busy);
+                        continue;
+                    }
+                    const auto tq0 = Clock::now();
+                    c = feed_.next();
+                    t_fetch_us_ += us_since(tq0);
+                    if (!c) break;
+                }
+                if (cfg_.fail_at >= 0 && (long)c->seq_no == cfg_.fail_at) throw Error("injected failure (MQ_DRIVER_FAIL_AT)");
+                // the slot to use: a free one, else the one submitted longest ago
+                int sl = s.free_slot();
+                if (sl < 0) {
+                    sl = s.oldest_busy();
+                    s.finish_slot(sl);
+                }
+                if (!c->unparsed) {
+                    c->hits.resize(c->starts.size());
+                    if (c->starts.empty()) {  // nothing to map in this chunk (the middle of a very long record)
+                        to_formatters(c);
+                        continue;
+                    }
+                }
+                s.submit(c, sl);
+            }
+            for (int q = s.oldest_busy(); q >= 0; q = s.oldest_busy()) s.finish_slot(q);
+        } catch (const std::exception &e) { fail(e.what()); }
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            submitters_left_--;
+        }
+        cv_.notify_all();
+    }
+
+    void format_loop() {
+        PafWriter pw(index_);
+        for (;;) {
+            Chunk *c = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return !to_format_.empty() || submitters_left_ == 0; });
+                if (to_format_.empty()) return;
+                c = to_format_.front();
+                to_format_.pop_front();
+                formatting_++;
+            }
+            const auto tm0 = Clock::now();
+            try {
+                const std::string err = format_chunk(*c, pw, unm_ != nullptr, ufa_ != nullptr);
+                if (!err.empty()) fail(err);
+            } catch (const std::exception &e) { fail(e.what()); }
+            t_format_us_ += us_since(tm0);
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                done_[c->seq_no] = c;
+                formatting_--;
+            }
+            cv_.notify_all();
+        }
+    }
+
+    // the calling thread: chunks in input order (main_thread_mer, src/closures.rs:117-123), until everything is written or somebody failed
+    void write_in_order() {
+        for (size_t next_out = 0;; ++next_out) {
+            Chunk *c = nullptr;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] {
+                    return done_.count(next_out) != 0 || !werr_.empty() || (submitters_left_ == 0 && to_format_.empty() && formatting_ == 0);
+                });
+                auto it = done_.find(next_out);
+                if (it == done_.end()) return;
+                c = it->second;
+                done_.erase(it);
+            }
+            const auto tw0 = Clock::now();
+            if (!c->paf.empty()) fwrite(c->paf.data(), 1, c->paf.size(), paf_);
+            if (unm_ && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm_);
+            if (ufa_ && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa_);
+            feed_.recycle(c);
+            t_write_us_ += us_since(tw0);
+        }
+    }
+
+    feeder::Feeder &feed_;
+    std::vector<std::vector<Ctx>> &slots_;
+    const ReadOnlyIndex &index_;
+    FILE *paf_, *unm_, *ufa_;
+    const Config cfg_;
+
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::deque<Chunk *> to_format_;     // mapped, waiting for a formatter
+    std::map<size_t, Chunk *> done_;    // formatted, waiting for their turn in the output
+    int submitters_left_;
+    int formatting_ = 0;                // chunks a formatter is working on right now
+    std::string werr_;                  // the first error
+    std::atomic<long long> t_submit_us_{0}, t_finish_us_{0}, t_fetch_us_{0}, t_format_us_{0}, t_write_us_{0};
+    std::atomic<unsigned long long> n_unparsed_{0}, n_irregular_{0};  // chunks submitted unparsed / handed back by the device for the host's parser
+};
+
+}  // namespace mapquik

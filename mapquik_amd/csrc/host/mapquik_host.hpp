@@ -126,6 +126,27 @@ inline ReadOnlyIndex Index::into_read_only() && {
     return ReadOnlyIndex(h, (uint64_t)u);
 }
 
+// A stream slot of an index (mq_ctx: device staging, minimizer lists, Match scratch of one batch in flight).  It uses its index until
+// it is destroyed: contexts go before their index.
+class Ctx {
+  public:
+    explicit Ctx(mq_index *index) : h_(mq_ctx_new(index)) {
+        if (!h_) throw Error("mq_ctx_new: " + last_error());
+    }
+    Ctx(const Ctx &) = delete;
+    Ctx &operator=(const Ctx &) = delete;
+    Ctx(Ctx &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~Ctx() { mq_ctx_free(h_); }
+    mq_ctx *handle() const { return h_; }
+    // room for batches of up to max_reads reads in max_bytes bytes, so that the first batches do not grow the slot
+    void reserve(uint32_t max_reads, uint64_t max_bytes) {
+        if (mq_ctx_reserve(h_, max_reads, max_bytes) != MQ_OK) throw Error("mq_ctx_reserve: " + last_error());
+    }
+
+  private:
+    mq_ctx *h_ = nullptr;
+};
+
 // The format! of src/mers.rs:181 for many reads: the same bytes as mq_format_paf, appended to a string, with the reference names and
 // lengths looked up once per reference (a formatter thread of the native driver writes ~200,000 lines per batch; snprintf and a map
 // lookup per line were 3-4 us of it).

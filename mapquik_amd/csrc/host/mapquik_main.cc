@@ -3,7 +3,7 @@
 // The hot path runs on the GPU through mapquik_host.hpp / the C ABI.  Reads come through fastx_feeder.hpp (parallel chunk
 // reader for raw files, one inflate thread + parser threads for .gz / .lz4), go to the GPU as raw FASTX bytes + spans
 // (mq_ctx_submit_spans, three stream slots per GPU so that copy-in, kernels and copy-out of consecutive chunks overlap),
-// and the PAF is formatted by a small thread pool and written in input order.  The reference FASTA comes through the same
+// and the PAF is formatted by a small thread pool and written in input order (map_pipeline.hpp).  The reference FASTA comes through the same
 // feeder (its records go to mq_index_add_ref straight from the page-locked chunks).
 #include <zlib.h>
 
@@ -27,20 +27,36 @@
 #include <sys/stat.h>
 
 #include "fastx_feeder.hpp"
+#include "map_pipeline.hpp"
 #include "mapquik_host.hpp"
 #include "ref_loader.hpp"
 
 using namespace mapquik;
-using Clock = std::chrono::steady_clock;
 
-static double secs(Clock::time_point a) { return std::chrono::duration<double>(Clock::now() - a).count(); }
+// every environment variable the driver listens to, read once (the feeder's own: feeder::Knobs)
+struct DriverKnobs {
+    // diagnostic, stderr: where the wall time of a whole job goes -- seconds since main() started at every step of the reference phase,
+    // the map phase and the teardown (on a 0.1-s map phase the fixed costs around it are most of the job) -- and where the map phase's
+    // threads spend their time
+    bool timing = set("MQ_DRIVER_TIMING");
+    bool ref_host = set("MQ_DRIVER_REF_HOST");        // diagnostic: earlier rounds' path (reference records copied from pageable memory one by one)
+    bool ref_preload = set("MQ_DRIVER_REF_PRELOAD");  // experiment: the reference read into host memory whole, before the first HIP call
+    bool no_reserve = set("MQ_DRIVER_NO_RESERVE");    // the index's table is not allocated ahead of the first insert
+    bool late_slots = set("MQ_DRIVER_LATE_SLOTS");    // diagnostic: no stream slot or chunk buffer is set up beside the reference phase
+    bool prefetch = set("MQ_DRIVER_PREFETCH") && !set("MQ_DRIVER_NO_PREFETCH");  // the read feeder starts while the reference is still being indexed
+    bool host_parse = set("MQ_DRIVER_HOST_PARSE");    // every chunk of reads is parsed by the reader threads
+    bool fastq_device = getenv("MQ_DRIVER_FASTQ") && strcmp(getenv("MQ_DRIVER_FASTQ"), "device") == 0;  // FASTQ records found on the device
+    long fail_at = set("MQ_DRIVER_FAIL_AT") ? atol(getenv("MQ_DRIVER_FAIL_AT")) : -1;  // test hook: the worker that takes this chunk number reports a failure
+    bool fast_exit = set("MQ_DRIVER_FAST_EXIT");      // experiment: the last pass leaves without unwinding
+    bool fake_multi = set("MQ_FAKE_MULTI");           // test hook: several workers on one device
 
-// MQ_DRIVER_TIMING=1 (diagnostic, stderr): where the wall time of a whole job goes -- seconds since main() started at every step of the
-// reference phase, the map phase and the teardown (on a 0.1-s map phase the fixed costs around it are most of the job)
+    static bool set(const char *name) { return getenv(name) != nullptr; }
+};
+static const DriverKnobs g_knobs;
+
 static const Clock::time_point g_t_main = Clock::now();
-static const bool g_timeline = getenv("MQ_DRIVER_TIMING") != nullptr;
 static void tl(const char *what) {
-    if (g_timeline) fprintf(stderr, "[+%.3f s] %s\n", secs(g_t_main), what);
+    if (g_knobs.timing) fprintf(stderr, "[+%.3f s] %s\n", secs(g_t_main), what);
 }
 
 // `{:?}` of a std::time::Duration
@@ -139,12 +155,12 @@ static void print_totals(Clock::time_point start) {
     printf("Maximum RSS: %sGB\n", strchr(fb, '.') || strchr(fb, 'e') ? fb : (std::string(fb) + ".0").c_str());  // src/main.rs:271
 }
 
-// ---------------------------------------------------------------- the reference phase: one function per route (run_pass decides which)
+// ---------------------------------------------------------------- the reference phase: one function per route (build_or_load_index decides which)
 // what the routes share
 struct RefPhase {
     const Opt &o;
     const Params &P;
-    std::unique_ptr<Index> &index;  // the index being built (run_pass replaces it when the streamer gives a file back late)
+    std::unique_ptr<Index> &index;  // the index being built (build_or_load_index replaces it when the streamer gives a file back late)
     int n_parse;                    // host threads
     const std::function<void()> &start_feed;  // starts the read feeder (once)
     bool prefetch;                  // MQ_DRIVER_PREFETCH: the read feeder starts while the reference is still being indexed
@@ -201,7 +217,7 @@ static feeder::RefStreamer::Result stream_reference(const RefPhase &rp) {
         const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
                                      : mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
         if (cnt < 0) throw Error("ref_extract: " + last_error());
-        if (g_timeline && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
+        if (g_knobs.timing && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
         lines.push_back("Indexed reference " + id + ": " + std::to_string(cnt) + " k-min-mers.");  // src/closures.rs:58
     });
     if (!res.irregular) {
@@ -339,498 +355,362 @@ static void feed_reference_chunked(const RefPhase &rp, bool ref_fasta) {
     flush();
 }
 
+// ---------------------------------------------------------------- one pass: what run_pass is made of, in the order it runs
+
+// A thread that is joined when it goes out of scope: an exception on the way finds it joined before what it works on goes away.
+struct JoiningThread {
+    std::thread t;
+    JoiningThread() = default;
+    explicit JoiningThread(std::function<void()> f) : t(std::move(f)) {}
+    JoiningThread(JoiningThread &&) = default;
+    JoiningThread &operator=(JoiningThread &&) = default;
+    ~JoiningThread() { join(); }
+    void join() {
+        if (t.joinable()) t.join();
+    }
+};
+
+// every task on a thread of its own, all joined, then the first error (in task order) rethrown
+static void run_all(const std::vector<std::function<void()>> &tasks) {
+    std::vector<std::exception_ptr> errs(tasks.size());
+    std::vector<std::thread> th;
+    for (size_t i = 0; i < tasks.size(); ++i)
+        th.emplace_back([&, i]() {
+            try {
+                tasks[i]();
+            } catch (...) { errs[i] = std::current_exception(); }
+        });
+    for (auto &t : th) t.join();
+    for (auto &e : errs)
+        if (e) std::rethrow_exception(e);
+}
+
+// The files of one pass: <prefix>.paf, created first (src/closures.rs:32; it stays behind, empty, when the reference phase fails),
+// <prefix>.unmapped.out, and the unmapped reads as FASTA for a second pass (seqtk subseq in the reference's script).  The one place
+// that closes them.
+struct OutputFiles {
+    const std::string paf_path;
+    FILE *paf, *unm = nullptr, *ufa = nullptr;
+    OutputFiles(const std::string &prefix, bool unmapped, const std::string &second_fa) : paf_path(prefix + ".paf"), paf(fopen(paf_path.c_str(), "w")) {
+        if (!paf) return;
+        if (unmapped) unm = fopen((prefix + ".unmapped.out").c_str(), "w");
+        if (!second_fa.empty()) ufa = fopen(second_fa.c_str(), "w");
+    }
+    OutputFiles(const OutputFiles &) = delete;
+    ~OutputFiles() { close(); }
+    void close() {
+        for (FILE **f : {&paf, &unm, &ufa}) {
+            if (*f) fclose(*f);
+            *f = nullptr;
+        }
+    }
+    // the map phase failed: never leave a partial PAF behind a failure
+    void discard_paf() {
+        close();
+        remove(paf_path.c_str());
+    }
+};
+
+// --gpus N: the index is replicated (every GPU indexes the same reference), read batches are dealt round-robin,
+// PAF lines are written in batch order = input order.  No collective: reads are independent.
+struct Devices {
+    int first, visible;
+    bool fake;  // MQ_FAKE_MULTI (test hook): several workers on one device
+    bool enough_for(int gpus) const { return fake || first + gpus <= visible || visible <= 0; }
+    int of(int g) const { return fake && visible > 0 ? (first + g) % visible : first + g; }
+};
+
+static const int N_SLOTS = 3;  // stream slots per submitting thread: copy-in, kernels and copy-out of consecutive chunks overlap
+
+// How the reference and the reads of this pass travel: decided from the arguments, the file names and the environment alone.
+struct Routes {
+    int n_parse;   // host threads
+    int n_format;  // PAF formatters (the reader threads of a mapped FASTA file have next to nothing to do)
+    unsigned long long batch_bases;
+    // An uncompressed reference FASTA goes to the device through a small pool of page-locked blocks as it is read (RefStreamer);
+    // a file that is not one sequence line per record is read into host memory whole, its records joined there (RefLoader).
+    // MQ_DRIVER_REF_PRELOAD=1 (experiment): the whole-file read starts before the first HIP call -- bringing the HIP runtime up
+    // takes 0.15-0.3 s of one thread, reading 3.1 GB 0.08-0.1 s of the others -- and the records go to the device from that buffer,
+    // page-locked in one call.  Measured slower than streaming on the bench's job (profiles/r05_driver_medians.txt): 3 GB of host
+    // memory cost 0.14 s to hand back on this platform (pages are cleared when freed: tools/thp_probe.c, 45 ms per GB), whoever does it.
+    bool ref_fasta, ref_plain, ref_preload;
+    bool preload_now;  // a RefLoader starts reading the reference before the first HIP call
+    bool stream_ref;   // RefStreamer
+    // An uncompressed FASTA file goes to the GPU as it lies in the file: the reader threads only copy file bytes into page-locked
+    // chunks (pread, cut at record starts), the records are found on the device (mq_ctx_submit_fasta) and the host reads a header
+    // only to print it.  MQ_DRIVER_HOST_PARSE=1: every chunk is parsed by the reader threads as in earlier rounds (same PAF; tests compare).
+    // FASTQ: the lean reader by default -- header and sequence lines only, one pread per record, qualities never read: 1 byte per base
+    // from the file and on the link: 12 / 20 / 31 / 35 Gbases/s at 2 / 4 / 8 / 16 reader threads against 9 / 17 / 22 / 21 with the
+    // records found on the device, where the whole file (2 bytes per base) is read and crosses the link
+    // (profiles/r05_fastq_readers.txt).  MQ_DRIVER_FASTQ=device selects that path (mq_ctx_submit_fastx).
+    bool on_device;
+    // --reads-join device: FASTA chunks as MQ_FASTX_FASTA_LINES -- sequences over several lines (60, 70, 80 columns) are joined on the
+    // device instead of coming back irregular for a host thread to compact
+    uint32_t fx_format;
+};
+
+static Routes describe_routes(const Opt &o, const std::string &reads_path, bool reads_fasta, bool ref_fasta, size_t threads) {
+    Routes rt;
+    rt.n_parse = (int)std::max<size_t>(1, threads);
+    rt.n_format = std::max(2, std::min(8, rt.n_parse));
+    rt.batch_bases = o.batch_bases;
+    if (rt.batch_bases == 0) {
+        struct stat sb;
+        rt.batch_bases = (rt.n_parse <= 4 && stat(reads_path.c_str(), &sb) == 0 && (unsigned long long)sb.st_size >= (2ull << 30)) ? (1ull << 26) : (1ull << 25);
+    }
+    rt.ref_fasta = ref_fasta;
+    rt.ref_plain = ref_fasta && !ends_with(o.reference, ".gz") && !ends_with(o.reference, ".lz4");
+    rt.ref_preload = g_knobs.ref_preload && !o.low_memory;
+    rt.preload_now = rt.ref_plain && o.load_index.empty() && (rt.ref_preload || g_knobs.ref_host);
+    rt.stream_ref = rt.ref_plain && o.load_index.empty() && !rt.ref_preload && !g_knobs.ref_host;
+    rt.on_device = !g_knobs.host_parse && (reads_fasta || g_knobs.fastq_device);
+    rt.fx_format = !reads_fasta ? MQ_FASTX_FASTQ : o.reads_join_device ? MQ_FASTX_FASTA_LINES : MQ_FASTX_FASTA;
+    return rt;
+}
+
+// The stream slots of the map phase, [submitting thread][slot] (device staging, minimizer lists, Match scratch: a few hundred MB of
+// device memory per submitting thread).  run_pass declares them after the indexes, so that on every path they go first.
+struct StreamSlots {
+    std::vector<std::vector<Ctx>> of;
+    const uint64_t chunk_bytes;  // what a slot has room for from the start
+    StreamSlots(size_t n_submitters, uint64_t batch_bases, uint64_t bytes_in)
+        : of(n_submitters), chunk_bytes(std::min<uint64_t>(batch_bases + batch_bases / 8 + (1u << 20), bytes_in + 64)) {
+        for (auto &v : of) v.reserve((size_t)N_SLOTS);
+    }
+    bool complete(size_t w) const { return of[w].size() == (size_t)N_SLOTS; }
+    // the slots submitter w still lacks, over index h
+    void fill(size_t w, mq_index *h) {
+        while (!complete(w)) {
+            of[w].emplace_back(h);
+            of[w].back().reserve((uint32_t)std::min<uint64_t>(chunk_bytes / 16000 + 512, 1u << 24), chunk_bytes);  // (sized for long reads; a chunk of short reads makes its slot grow once)
+        }
+    }
+    void drop() {
+        for (auto &v : of) v.clear();
+    }
+};
+
+// The stream slots and the feeder's first page-locked chunk buffers depend on neither the reference nor the reads: the first GPU's
+// are set up by a thread of its own BESIDE the reference phase (0.03-0.04 s of a 0.1-s phase when they came after it).
+class EarlySetup {
+  public:
+    // n_buffers: chunk buffers to preallocate, 0 for none (MQ_DRIVER_PREFETCH: the feeder, started early, allocates its own)
+    EarlySetup(StreamSlots &slots, feeder::Feeder &feed, int n_sub, int n_buffers) : slots_(slots), feed_(feed), n_sub_(n_sub), n_buffers_(n_buffers) {}
+    void start(mq_index *h) {
+        if (g_knobs.late_slots) return;  // (diagnostic: everything after the reference phase, as in earlier rounds)
+        thread_ = JoiningThread([this, h]() {
+            try {
+                for (int w = 0; w < n_sub_; ++w) slots_.fill((size_t)w, h);
+                if (n_buffers_ > 0) {
+                    feed_.preallocate(n_buffers_);
+                    pool_ready_ = true;
+                }
+            } catch (const std::exception &e) { err_ = e.what(); }
+        });
+    }
+    void join() { thread_.join(); }
+    // after join():
+    const std::string &error() const { return err_; }
+    bool pool_ready() const { return pool_ready_; }
+
+  private:
+    StreamSlots &slots_;
+    feeder::Feeder &feed_;
+    const int n_sub_, n_buffers_;
+    std::string err_;
+    bool pool_ready_ = false;
+    JoiningThread thread_;  // (last: joined before the rest goes away)
+};
+
+static std::unique_ptr<Index> new_index(const Opt &o, const Params &P, int device) {
+    std::unique_ptr<Index> index(new Index(P, device));
+    index->table_factor((uint32_t)o.table_factor);
+    return index;
+}
+
+static void reserve_table(const Opt &o, const Params &P, bool ref_plain, Index &index) {
+    if (!ref_plain || g_knobs.no_reserve) return;
+    // Index::new sizes its map before the first insert (src/index.rs:83: with_capacity(39,821,990), CHM13 at the defaults); here the
+    // expected count follows from the reference's size: canonical selection keeps 1 - (1 - d)^2 of the l-mers, homopolymer
+    // compression about three quarters of the bases.  The table is allocated in the background while the reference is read and seeded.
+    struct stat rst;
+    if (stat(o.reference.c_str(), &rst) == 0 && rst.st_size > 0) {
+        const double d = std::min(1.0, std::max(0.0, P.density));
+        index.with_capacity((uint64_t)((double)rst.st_size * (1.0 - (1.0 - d) * (1.0 - d)) * (P.use_hpc ? 0.75 : 1.0)) + 1);
+    }
+}
+
+// --index: the table from a file, into `loaded`.  Else index_mers (src/closures.rs:46-51) per reference record, in file order, on the
+// first GPU, into rp.index, by the route the file takes; the kernels fold soft-masked lower case.  Device allocations queue behind
+// each other, hence this order: the reference's staging buffer, the table (in the background), the stream slots (EarlySetup).
+static void build_or_load_index(const RefPhase &rp, const Routes &rt, int device, std::unique_ptr<feeder::RefLoader> &preload,
+                                std::unique_ptr<ReadOnlyIndex> &loaded, StreamSlots &slots, EarlySetup &early) {
+    const Opt &o = rp.o;
+    if (!o.load_index.empty()) {
+        loaded = load_index_file(o, rp.P, device);
+        return;
+    }
+    rp.index = new_index(o, rp.P, device);
+    tl("Index::new returned (HIP runtime up, device chosen)");
+    if (rt.stream_ref || (preload && !g_knobs.ref_host)) {
+        // the device's staging buffer of the reference FIRST: device allocations queue behind each other, and this one (the file's
+        // size) must not wait behind the table's, which is larger and not needed before the last record is indexed
+        struct stat rst;
+        if (stat(o.reference.c_str(), &rst) != 0) throw Error("Error opening compressed file: " + o.reference);  // get_reader's message (src/main.rs:62)
+        if (mq_index_stage_begin(rp.index->handle(), (uint64_t)rst.st_size) != MQ_OK) throw Error("mq_index_stage_begin: " + last_error());
+        tl("staging buffer for the reference allocated");
+    }
+    reserve_table(o, rp.P, rt.ref_plain, *rp.index);
+    early.start(rp.index->handle());
+    feeder::RefStreamer::Result streamed;  // the streamer's, where it ran
+    bool index_replaced = false;           // ... and gave the file back after records had been indexed: that index was replaced by a new one
+    if (rt.stream_ref) {
+        streamed = stream_reference(rp);
+        if (streamed.irregular) {
+            // not one sequence line per record (a line-wrapped FASTA shows in its first block, before anything was indexed): an index
+            // that took records already is dropped, and the file goes through the loader below
+            if (streamed.handed > 0) {  // (an index that has seen nothing stays: its table is being allocated in the background already)
+                early.join();  // the slots set up so far belong to the index that goes away
+                slots.drop();
+                rp.index.reset();
+                rp.index = new_index(o, rp.P, device);
+                index_replaced = true;
+                reserve_table(o, rp.P, rt.ref_plain, *rp.index);
+            }
+            tl("reference is not one line per record: host loader");
+        }
+    }
+    if (!rt.stream_ref || streamed.irregular) {
+        if (rt.ref_plain && !(o.low_memory && rt.stream_ref)) {  // (--low-memory: a file the streamer gave back goes through the chunked reader, record by record)
+            if (!preload) preload.reset(new feeder::RefLoader(o.reference, rt.n_parse, false));  // (the streamer above sent the file here)
+            load_reference_whole(rp, *preload, g_knobs.ref_host, index_replaced);
+        } else {
+            feed_reference_chunked(rp, rt.ref_fasta);
+        }
+    }
+}
+
+// The index built on the first GPU is finalized, saved where --save-index asks for it, and the finalized table is copied device to
+// device to the other GPUs (mq_index_clone).
+static void finalise_save_clone(const Opt &o, const Devices &dev, std::unique_ptr<Index> &building, std::vector<std::unique_ptr<ReadOnlyIndex>> &ro) {
+    if (building) {
+        ro[0].reset(new ReadOnlyIndex(std::move(*building).into_read_only()));
+        tl("into_read_only returned (table allocated, k-min-mers inserted)");
+        building.reset();
+    }
+    if (!o.save_index.empty()) {
+        const auto ts = Clock::now();
+        ro[0]->save(o.save_index);
+        printf("Saved index to %s in %s.\n", o.save_index.c_str(), rust_duration(secs(ts)).c_str());
+    }
+    std::vector<std::function<void()>> clones;
+    for (int g = 1; g < o.gpus; ++g) clones.push_back([&, g]() { ro[g].reset(new ReadOnlyIndex(ro[0]->clone_to(dev.of(g)))); });
+    run_all(clones);
+}
+
+// The stream slots of the other GPUs (the first GPU's were set up beside the reference phase), whatever of the first GPU's is still
+// missing, and the first page-locked chunk buffers (n_buffers of them; 0: the feeder allocates its own).
+static void finish_slots_and_pool(EarlySetup &early, StreamSlots &slots, const std::vector<std::unique_ptr<ReadOnlyIndex>> &ro, feeder::Feeder &feed, int n_buffers) {
+    early.join();
+    if (!early.error().empty()) throw Error(early.error());
+    const size_t n_sub = slots.of.size() / ro.size();
+    std::vector<std::function<void()>> tasks;
+    for (size_t w = 0; w < slots.of.size(); ++w)
+        if (!slots.complete(w)) tasks.push_back([&, w]() { slots.fill(w, ro[w / n_sub]->handle()); });
+    if (n_buffers > 0 && !early.pool_ready()) tasks.push_back([&]() { feed.preallocate(n_buffers); });
+    run_all(tasks);
+}
+
+// teardown, side by side: the stream slots and then the indexes (contexts go before their index) on one thread, the feeder's
+// page-locked pool on this one -- 0.08 s one after the other on a 0.6-s job
+static void teardown(const Opt &o, StreamSlots &slots, std::vector<std::unique_ptr<ReadOnlyIndex>> &ro, std::unique_ptr<feeder::RefLoader> &preload, feeder::Feeder &feed) {
+    if (o.last_pass && g_knobs.fast_exit) {
+        // EXPERIMENT: the run's output is complete and closed -- leave without unwinding (stream slots, the table, the page-locked
+        // pool: the operating system takes a process's device and host memory back in one go when it ends)
+        print_totals(g_t_main);
+        fflush(stdout);
+        fflush(stderr);
+        _exit(0);
+    }
+    JoiningThread dev_side([&]() {
+        slots.drop();
+        ro.clear();
+    });
+    JoiningThread ref_reaper;
+    if (preload) ref_reaper = JoiningThread([pl = preload.release()]() { delete pl; });
+    feed.release_buffers();
+    dev_side.join();
+    ref_reaper.join();
+}
+
 // One run of the reference's flow (src/closures.rs:22-212): index the reference, map the reads, write <prefix>.paf in input
 // order.  second_fa != "": the reads left unmapped also go to that FASTA file (for the second pass).
 static int run_pass(const Opt &o, const Params &P, const std::string &reads_path, bool reads_fasta, bool ref_fasta, const std::string &prefix,
                     size_t threads, const std::string &second_fa) {
-        FILE *paf = fopen((prefix + ".paf").c_str(), "w");  // src/closures.rs:32
-        if (!paf) { fprintf(stderr, "Couldn't create %s.paf\n", prefix.c_str()); return 101; }
-        FILE *unm = (o.unmapped || !o.second.empty()) ? fopen((prefix + ".unmapped.out").c_str(), "w") : nullptr;
-        FILE *ufa = second_fa.empty() ? nullptr : fopen(second_fa.c_str(), "w");  // the unmapped reads as FASTA (seqtk subseq in the reference's script)
+    OutputFiles out(prefix, o.unmapped || !o.second.empty(), second_fa);
+    if (!out.paf) { fprintf(stderr, "Couldn't create %s.paf\n", prefix.c_str()); return 101; }
 
-        // An uncompressed reference FASTA goes to the device through a small pool of page-locked blocks as it is read (RefStreamer, below);
-        // a file that is not one sequence line per record is read into host memory whole, its records joined there (RefLoader).
-        // MQ_DRIVER_REF_PRELOAD=1 (experiment): the whole-file read starts HERE, before the first HIP call -- bringing the HIP runtime up
-        // takes 0.15-0.3 s of one thread, reading 3.1 GB 0.08-0.1 s of the others -- and the records go to the device from that buffer,
-        // page-locked in one call.  Measured slower than streaming on the bench's job (profiles/r05_driver_medians.txt): 3 GB of host
-        // memory cost 0.14 s to hand back on this platform (pages are cleared when freed: tools/thp_probe.c, 45 ms per GB), whoever does it.
-        const int n_parse = (int)std::max<size_t>(1, threads);
-        const bool ref_plain = ref_fasta && !ends_with(o.reference, ".gz") && !ends_with(o.reference, ".lz4");
-        const bool ref_host = getenv("MQ_DRIVER_REF_HOST") != nullptr;  // diagnostic: earlier rounds' path (records copied from pageable memory one by one)
-        const bool ref_preload = getenv("MQ_DRIVER_REF_PRELOAD") != nullptr && !o.low_memory;
-        std::unique_ptr<feeder::RefLoader> preload;
-        if (ref_plain && o.load_index.empty() && (ref_preload || ref_host)) preload.reset(new feeder::RefLoader(o.reference, n_parse, !ref_host));
+    const Routes rt = describe_routes(o, reads_path, reads_fasta, ref_fasta, threads);
+    std::unique_ptr<feeder::RefLoader> preload;
+    if (rt.preload_now) preload.reset(new feeder::RefLoader(o.reference, rt.n_parse, !g_knobs.ref_host));  // (HERE: before the first HIP call)
+    const Devices dev{o.device, mq_device_count(), g_knobs.fake_multi};
+    tl("HIP runtime up (first HIP call returned)");
+    if (!dev.enough_for(o.gpus)) {
+        fprintf(stderr, "mapquik: --gpus %d from device %d needs %d devices, %d visible\n", o.gpus, o.device, o.device + o.gpus, dev.visible);
+        return 101;
+    }
 
-        // --gpus N: the index is replicated (every GPU indexes the same reference), read batches are dealt round-robin,
-        // PAF lines are written in batch order = input order.  No collective: reads are independent.
-        const int n_dev = mq_device_count();
-        tl("HIP runtime up (first HIP call returned)");
-        const bool fake = getenv("MQ_FAKE_MULTI") != nullptr;  // test hook: several workers on one device
-        if (!fake && o.device + o.gpus > n_dev && n_dev > 0) {
-            fprintf(stderr, "mapquik: --gpus %d from device %d needs %d devices, %d visible\n", o.gpus, o.device, o.device + o.gpus, n_dev);
-            return 101;
+    // The read feeder (constructed here, started below): parsing reads does not depend on the index.
+    feeder::Feeder feed(reads_path, !reads_fasta, rt.batch_bases, rt.n_parse, rt.n_parse + o.gpus * (N_SLOTS + 1) + rt.n_format + 2);
+    feed.leave_unparsed(rt.on_device);  // (acts on uncompressed input only, FASTA or FASTQ)
+    feed.premap();  // MQ_FEEDER_MAPPED_FASTA=1 only (experiment): the file is mapped, not read, while the reference is indexed
+    // The read feeder starts when the index is ready.  MQ_DRIVER_PREFETCH=1 starts it while the reference is still being indexed
+    // (it then allocates its page-locked chunk buffers and parses the first chunks early): that was the default while pinning
+    // the pool was the read phase's start-up cost; with the huge-page pool it makes the map phase 15 % shorter and the index
+    // phase twice as long (the pool's hipHostRegister calls and the index calls share the driver) -- 1.47 s against 1.0 s for
+    // the whole job on the bench's input.
+    bool feed_started = false;
+    const std::function<void()> start_feed = [&]() {
+        if (!feed_started) {
+            feed.start();
+            feed_started = true;
         }
-        auto dev_of = [&](int g) { return fake && n_dev > 0 ? (o.device + g) % n_dev : o.device + g; };
+    };
 
-        // The read feeder (constructed here, started below): parsing reads does not depend on the index.
-        using feeder::Chunk;
-        const int n_slots = 3;  // stream slots per GPU: copy-in, kernels and copy-out of consecutive chunks overlap
-        const int n_format = std::max(2, std::min(8, n_parse));  // PAF formatters (the reader threads of a mapped FASTA file have next to nothing to do)
-        unsigned long long batch_bases = o.batch_bases;
-        if (batch_bases == 0) {
-            struct stat sb;
-            batch_bases = (n_parse <= 4 && stat(reads_path.c_str(), &sb) == 0 && (unsigned long long)sb.st_size >= (2ull << 30)) ? (1ull << 26) : (1ull << 25);
-        }
-        feeder::Feeder feed(reads_path, !reads_fasta, batch_bases, n_parse, n_parse + o.gpus * (n_slots + 1) + n_format + 2);
-        // An uncompressed FASTA file goes to the GPU as it lies in the file: the reader threads only copy file bytes into page-locked
-        // chunks (pread, cut at record starts), the records are found on the device (mq_ctx_submit_fasta) and the host reads a header
-        // only to print it.  MQ_DRIVER_HOST_PARSE=1: every chunk is parsed by the reader threads as in earlier rounds (same PAF; tests compare).
-        // FASTQ: the lean reader by default -- header and sequence lines only, one pread per record, qualities never read: 1 byte per base
-        // from the file and on the link: 12 / 20 / 31 / 35 Gbases/s at 2 / 4 / 8 / 16 reader threads against 9 / 17 / 22 / 21 with the
-        // records found on the device, where the whole file (2 bytes per base) is read and crosses the link
-        // (profiles/r05_fastq_readers.txt).  MQ_DRIVER_FASTQ=device selects that path (mq_ctx_submit_fastx).
-        bool on_device = getenv("MQ_DRIVER_HOST_PARSE") == nullptr;
-        if (on_device && !reads_fasta) {
-            const char *fq = getenv("MQ_DRIVER_FASTQ");
-            on_device = fq && strcmp(fq, "device") == 0;
-        }
-        feed.leave_unparsed(on_device);  // (acts on uncompressed input only, FASTA or FASTQ)
-        // --reads-join device: FASTA chunks as MQ_FASTX_FASTA_LINES -- sequences over several lines (60, 70, 80 columns) are joined on the
-        // device instead of coming back irregular for a host thread to compact
-        const bool fx_wrapped = reads_fasta && o.reads_join_device;
-        const uint32_t fx_format = !reads_fasta ? MQ_FASTX_FASTQ : fx_wrapped ? MQ_FASTX_FASTA_LINES : MQ_FASTX_FASTA, fx_lpr = reads_fasta ? 2u : 4u;
-        feed.premap();  // MQ_FEEDER_MAPPED_FASTA=1 only (experiment): the file is mapped, not read, while the reference is indexed
-        // The read feeder starts when the index is ready.  MQ_DRIVER_PREFETCH=1 starts it while the reference is still being indexed
-        // (it then allocates its page-locked chunk buffers and parses the first chunks early): that was the default while pinning
-        // the pool was the read phase's start-up cost; with the huge-page pool it makes the map phase 15 % shorter and the index
-        // phase twice as long (the pool's hipHostRegister calls and the index calls share the driver) -- 1.47 s against 1.0 s for
-        // the whole job on the bench's input.
-        const bool prefetch = getenv("MQ_DRIVER_PREFETCH") != nullptr && getenv("MQ_DRIVER_NO_PREFETCH") == nullptr;
-        bool feed_started = false;
-        const std::function<void()> start_feed = [&]() {
-            if (!feed_started) {
-                feed.start();
-                feed_started = true;
-            }
-        };
+    auto t0 = Clock::now();
+    // Declared in this order, so that on every path out of here the early thread is joined first, then the stream slots go, then
+    // the indexes they work on.
+    std::unique_ptr<Index> building;
+    std::vector<std::unique_ptr<ReadOnlyIndex>> ro((size_t)o.gpus);
+    // Submitting threads per GPU.  Chunks that are views of the mapped file are copied to the device from pageable memory: that
+    // copy occupies the thread that asks for it, hence two (experimental path, MQ_FEEDER_MAPPED_FASTA=1; see Feeder::premap).
+    const int n_sub = feed.mapped_views() ? 2 : 1;
+    StreamSlots slots((size_t)(o.gpus * n_sub), rt.batch_bases, feed.bytes_in());
+    const int n_buffers = g_knobs.prefetch ? 0 : rt.n_parse + N_SLOTS;  // chunk buffers page-locked ahead of the feeder's start
+    EarlySetup early(slots, feed, n_sub, n_buffers);
+    build_or_load_index(RefPhase{o, P, building, rt.n_parse, start_feed, g_knobs.prefetch}, rt, dev.of(0), preload, ro[0], slots, early);
+    tl("every reference record handed to ref_extract");
+    finalise_save_clone(o, dev, building, ro);
+    finish_slots_and_pool(early, slots, ro, feed, n_buffers);
+    tl("replicas cloned, stream slots and first chunk buffers set up");
+    printf("Indexed %llu unique k-min-mers in %s.\n", (unsigned long long)ro[0]->unique_count(), rust_duration(secs(t0)).c_str());
 
-        auto t0 = Clock::now();
-        // index_mers (src/closures.rs:46-51) per reference record, in file order, on the first GPU; the finalized table is then
-        // copied device to device to the other GPUs (mq_index_clone).  The kernels fold soft-masked lower case.
-        std::vector<std::unique_ptr<Index>> building(1);
-        if (o.load_index.empty()) {
-            building[0].reset(new Index(P, dev_of(0)));
-            building[0]->table_factor((uint32_t)o.table_factor);
-            tl("Index::new returned (HIP runtime up, device chosen)");
-        }
-        const bool stream_ref = ref_plain && o.load_index.empty() && !ref_preload && !ref_host;  // RefStreamer (below)
-        // The stream slots of the map phase (device staging, minimizer lists, Match scratch: a few hundred MB of device memory per
-        // submitting thread) and the feeder's first page-locked chunk buffers depend on neither the reference nor the reads: the first
-        // GPU's are set up by a thread of its own BESIDE the reference phase (0.03-0.04 s of a 0.1-s phase when they came after it).
-        const int n_sub = feed.mapped_views() ? 2 : 1;  // submitting threads per GPU (see below)
-        std::vector<std::vector<mq_ctx *>> slots((size_t)(o.gpus * n_sub), std::vector<mq_ctx *>((size_t)n_slots, nullptr));
-        auto make_slots = [&](size_t gw, mq_index *h) -> std::string {
-            for (int sl = 0; sl < n_slots; ++sl) {
-                if (slots[gw][sl]) continue;
-                slots[gw][sl] = mq_ctx_new(h);
-                if (!slots[gw][sl]) return std::string("mq_ctx_new: ") + last_error();
-                const uint64_t cb = std::min<uint64_t>(batch_bases + batch_bases / 8 + (1u << 20), feed.bytes_in() + 64);
-                if (mq_ctx_reserve(slots[gw][sl], (uint32_t)std::min<uint64_t>(cb / 16000 + 512, 1u << 24), cb) != MQ_OK)  // (sized for long reads; a chunk of short reads makes its slot grow once)
-                    return std::string("mq_ctx_reserve: ") + last_error();
-            }
-            return std::string();
-        };
-        std::thread early;
-        std::string early_err;
-        bool pool_ready = false;
-        auto early_join = [&]() {
-            if (early.joinable()) early.join();
-        };
-        auto early_start = [&]() {
-            if (getenv("MQ_DRIVER_LATE_SLOTS") != nullptr) return;  // (diagnostic: everything after the reference phase, as in earlier rounds)
-            mq_index *h = building[0]->handle();
-            early = std::thread([&, h]() {
-                for (int w = 0; w < n_sub && early_err.empty(); ++w) early_err = make_slots((size_t)w, h);
-                if (!prefetch && early_err.empty()) {
-                    try {
-                        feed.preallocate(n_parse + n_slots);
-                        pool_ready = true;
-                    } catch (const std::exception &e) { early_err = e.what(); }
-                }
-            });
-        };
-        struct EarlyGuard {  // an exception on the way: the thread is joined before its captures go away
-            std::thread &t;
-            ~EarlyGuard() { if (t.joinable()) t.join(); }
-        } early_guard{early};
-        auto reserve_table = [&]() {
-            if (!ref_plain || getenv("MQ_DRIVER_NO_RESERVE") != nullptr) return;
-            // Index::new sizes its map before the first insert (src/index.rs:83: with_capacity(39,821,990), CHM13 at the defaults); here the
-            // expected count follows from the reference's size: canonical selection keeps 1 - (1 - d)^2 of the l-mers, homopolymer
-            // compression about three quarters of the bases.  The table is allocated in the background while the reference is read and seeded.
-            struct stat rst;
-            if (stat(o.reference.c_str(), &rst) == 0 && rst.st_size > 0) {
-                const double d = std::min(1.0, std::max(0.0, P.density));
-                building[0]->with_capacity((uint64_t)((double)rst.st_size * (1.0 - (1.0 - d) * (1.0 - d)) * (P.use_hpc ? 0.75 : 1.0)) + 1);
-            }
-        };
-        std::thread ref_reaper;
-        struct ReaperGuard {
-            std::thread &t;
-            ~ReaperGuard() { if (t.joinable()) t.join(); }
-        } reaper_guard{ref_reaper};
-        std::unique_ptr<ReadOnlyIndex> loaded;
-        if (!o.load_index.empty()) {
-            building.clear();
-            loaded = load_index_file(o, P, dev_of(0));
-        } else {
-            if (stream_ref || (preload && !ref_host)) {
-                // the device's staging buffer of the reference FIRST: device allocations queue behind each other, and this one (the file's
-                // size) must not wait behind the table's, which is larger and not needed before the last record is indexed
-                struct stat rst;
-                if (stat(o.reference.c_str(), &rst) != 0) throw Error("Error opening compressed file: " + o.reference);  // get_reader's message (src/main.rs:62)
-                if (mq_index_stage_begin(building[0]->handle(), (uint64_t)rst.st_size) != MQ_OK) throw Error("mq_index_stage_begin: " + last_error());
-                tl("staging buffer for the reference allocated");
-            }
-            reserve_table();
-            early_start();
-            const RefPhase rp{o, P, building[0], n_parse, start_feed, prefetch};
-            feeder::RefStreamer::Result streamed;  // the streamer's, where it ran
-            bool index_replaced = false;           // ... and gave the file back after records had been indexed: that index was replaced by a new one
-            if (stream_ref) {
-                streamed = stream_reference(rp);
-                if (streamed.irregular) {
-                    // not one sequence line per record (a line-wrapped FASTA shows in its first block, before anything was indexed): an index
-                    // that took records already is dropped, and the file goes through the loader below
-                    if (streamed.handed > 0) {  // (an index that has seen nothing stays: its table is being allocated in the background already)
-                        early_join();      // the slots set up so far belong to the index that goes away
-                        for (auto &v : slots) for (auto &c : v) { mq_ctx_free(c); c = nullptr; }
-                        building[0].reset();
-                        building[0].reset(new Index(P, dev_of(0)));
-                        building[0]->table_factor((uint32_t)o.table_factor);
-                        index_replaced = true;
-                        reserve_table();
-                    }
-                    tl("reference is not one line per record: host loader");
-                }
-            }
-            if (!stream_ref || streamed.irregular) {
-                if (ref_plain && !(o.low_memory && stream_ref)) {  // (--low-memory: a file the streamer gave back goes through the chunked reader, record by record)
-                    if (!preload) preload.reset(new feeder::RefLoader(o.reference, n_parse, false));  // (the streamer above sent the file here)
-                    load_reference_whole(rp, *preload, ref_host, index_replaced);
-                } else {
-                    feed_reference_chunked(rp, ref_fasta);
-                }
-            }
-        }
-        std::vector<std::unique_ptr<ReadOnlyIndex>> ro((size_t)o.gpus);
-        tl("every reference record handed to ref_extract");
-        {
-            if (loaded) {
-                ro[0] = std::move(loaded);
-            } else {
-                ro[0].reset(new ReadOnlyIndex(std::move(*building[0]).into_read_only()));
-                tl("into_read_only returned (table allocated, k-min-mers inserted)");
-                building.clear();
-            }
-            if (!o.save_index.empty()) {
-                const auto ts = Clock::now();
-                ro[0]->save(o.save_index);
-                printf("Saved index to %s in %s.\n", o.save_index.c_str(), rust_duration(secs(ts)).c_str());
-            }
-            std::vector<std::string> errs((size_t)o.gpus);
-            std::vector<std::thread> th;
-            for (int g = 1; g < o.gpus; ++g)
-                th.emplace_back([&, g]() {
-                    try {
-                        ro[g].reset(new ReadOnlyIndex(ro[0]->clone_to(dev_of(g))));
-                    } catch (const Error &e) { errs[g] = e.what(); }
-                });
-            for (auto &t : th) t.join();
-            for (auto &e : errs) if (!e.empty()) throw Error(e);
-        }
-        // The stream slots of the other GPUs (the first GPU's were set up beside the reference phase) and whatever of the first GPU's
-        // is still missing.
-        early_join();
-        if (!early_err.empty()) {
-            for (auto &v : slots) for (auto c : v) mq_ctx_free(c);
-            throw Error(early_err);
-        }
-        {
-            std::vector<std::string> errs(slots.size());
-            std::vector<std::thread> th;
-            for (size_t gw = 0; gw < slots.size(); ++gw)
-                if (!slots[gw][(size_t)n_slots - 1]) th.emplace_back([&, gw]() { errs[gw] = make_slots(gw, ro[gw / (size_t)n_sub]->handle()); });
-            if (!prefetch && !pool_ready) th.emplace_back([&]() { feed.preallocate(n_parse + n_slots); });  // and the first page-locked chunk buffers
-            for (auto &t : th) t.join();
-            for (auto &e : errs)
-                if (!e.empty()) {
-                    for (auto &v : slots) for (auto c : v) mq_ctx_free(c);
-                    throw Error(e);
-                }
-        }
-        tl("replicas cloned, stream slots and first chunk buffers set up");
-        printf("Indexed %llu unique k-min-mers in %s.\n", (unsigned long long)ro[0]->unique_count(), rust_duration(secs(t0)).c_str());
-
-        t0 = Clock::now();
-        if (P.use_pfx && !ends_with(reads_path, ".gz") && !ends_with(reads_path, ".lz4")) puts("Warning: using experimental rust-parallelfastx (exciting!)");
-        start_feed();
-        std::mutex mu;
-        std::condition_variable cv;
-        std::deque<Chunk *> to_format;               // mapped, waiting for a formatter
-        std::map<size_t, Chunk *> done;              // formatted, waiting for their turn in the output
-        // Submitting threads per GPU (n_sub).  Chunks that are views of the mapped file are copied to the device from pageable memory: that
-        // copy occupies the thread that asks for it, hence two (experimental path, MQ_FEEDER_MAPPED_FASTA=1; see Feeder::premap).
-        int gpu_workers_left = o.gpus * n_sub;
-        int formatting = 0;                          // chunks a formatter is working on right now
-        std::string werr;
-        auto fail = [&](const std::string &m) {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (werr.empty()) werr = m;
-            }
-            cv.notify_all();
-        };
-        auto failed = [&]() {
-            std::lock_guard<std::mutex> lk(mu);
-            return !werr.empty();
-        };
-        const bool drv_timing = getenv("MQ_DRIVER_TIMING") != nullptr;  // diagnostic: where the map phase's threads spend their time (stderr)
-        std::atomic<long long> t_submit_us{0}, t_finish_us{0}, t_fetch_us{0}, t_format_us{0}, t_write_us{0};
-        std::atomic<unsigned long long> n_unparsed{0}, n_irregular{0};  // chunks submitted unparsed / handed back by the device for the host's parser
-        auto us_since = [](Clock::time_point a) { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(Clock::now() - a).count(); };
-        const char *fail_at_env = getenv("MQ_DRIVER_FAIL_AT");  // test hook: the worker that takes this chunk number reports a failure
-        const long fail_at = fail_at_env ? atol(fail_at_env) : -1;
-        std::vector<std::thread> workers;
-        for (int gw = 0; gw < o.gpus * n_sub; ++gw)
-            workers.emplace_back([&, gw]() {
-                std::vector<mq_ctx *> &ctx = slots[(size_t)gw];
-                std::vector<Chunk *> inflight((size_t)n_slots, nullptr);
-                std::vector<size_t> age((size_t)n_slots, 0);  // submit order of the chunk in the slot
-                size_t submitted = 0;
-                auto finish_slot = [&](int sl) {
-                    if (!inflight[sl]) return;
-                    const auto tf0 = Clock::now();
-                    Chunk *fc = inflight[sl];
-                    if (fc->unparsed) {  // records found on the device: hits and line ends (or header spans) come back together
-                        uint32_t n = 0, n_lines = 0, flags = 0;
-                        const uint32_t *line_ends = nullptr, *hdr_begin = nullptr, *hdr_end = nullptr, *seq_lens = nullptr;
-                        const mq_hit *hits = nullptr;
-                        ++n_unparsed;
-                        if (fx_wrapped ? mq_ctx_wait_fasta_lines(ctx[sl], &n, &hdr_begin, &hdr_end, &seq_lens, &hits, &flags) != MQ_OK
-                                       : mq_ctx_wait_fasta(ctx[sl], &n, &line_ends, &n_lines, &hits, &flags) != MQ_OK) {
-                            fail(std::string(fx_wrapped ? "mq_ctx_wait_fasta_lines: " : "mq_ctx_wait_fasta: ") + last_error());
-                        } else if (flags & MQ_FASTA_IRREGULAR) {
-                            // sequences over several lines, blank lines, ...: this chunk the old way (parsed here, spans to the device)
-                            ++n_irregular;
-                            try {
-                                fc->materialize();  // a view of the mapped file: the parser compacts sequence lines in place
-                                feeder::parse_chunk(*fc, !reads_fasta);
-                                fc->hits.resize(fc->starts.size());
-                                if (!fc->starts.empty() &&
-                                    (mq_ctx_submit_spans(ctx[sl], fc->buf, fc->bytes, fc->starts.data(), fc->lens.data(), (uint32_t)fc->starts.size(), fc->hits.data()) != MQ_OK ||
-                                     mq_ctx_wait(ctx[sl]) != MQ_OK))
-                                    fail(std::string("mq_ctx_submit_spans: ") + last_error());
-                            } catch (const std::exception &e) { fail(e.what()); }
-                        } else if (fx_wrapped) {
-                            feeder::spans_from_headers(*fc, hdr_begin, hdr_end, seq_lens, n);
-                            fc->hits.assign(hits, hits + n);
-                        } else {
-                            feeder::spans_from_line_ends(*fc, line_ends, n_lines, fx_lpr);
-                            fc->hits.assign(hits, hits + n);
-                        }
-                        fc->unparsed = false;
-                    } else if (mq_ctx_wait(ctx[sl]) != MQ_OK) fail(std::string("mq_ctx_wait: ") + last_error());
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        to_format.push_back(inflight[sl]);
-                    }
-                    inflight[sl] = nullptr;
-                    cv.notify_all();
-                    t_finish_us += us_since(tf0);
-                };
-                // the slot to use next: a free one, else the one submitted longest ago (-1 with free_only when none is free)
-                auto oldest_busy = [&]() {
-                    int best = -1;
-                    for (int sl = 0; sl < n_slots; ++sl)
-                        if (inflight[sl] && (best < 0 || age[sl] < age[best])) best = sl;
-                    return best;
-                };
-                try {
-                    for (;;) {
-                        if (failed()) break;  // somebody failed: stop pulling chunks
-                        // Never wait for a new chunk while holding submitted ones: the writer may be waiting for exactly one of
-                        // them while every other buffer of the pool sits behind the writer (formatted, out of turn) -- then no
-                        // new chunk can ever be parsed.  With nothing ready, the oldest submitted chunk is passed on first.
-                        bool end = false;
-                        Chunk *c = feed.poll(end);
-                        if (!c) {
-                            if (end) break;
-                            const int busy = oldest_busy();
-                            if (busy >= 0) {
-                                finish_slot(busy);
-                                continue;
-                            }
-                            const auto tq0 = Clock::now();
-                            c = feed.next();
-                            t_fetch_us += us_since(tq0);
-                            if (!c) break;
-                        }
-                        if (fail_at >= 0 && (long)c->seq_no == fail_at) throw Error("injected failure (MQ_DRIVER_FAIL_AT)");
-                        int sl = -1;
-                        for (int q = 0; q < n_slots; ++q)
-                            if (!inflight[q]) { sl = q; break; }
-                        if (sl < 0) {
-                            sl = oldest_busy();
-                            finish_slot(sl);
-                        }
-                        if (c->unparsed) {
-                            const auto ts0 = Clock::now();
-                            if (mq_ctx_submit_fastx(ctx[sl], c->buf, c->begin, c->bytes, fx_format) != MQ_OK) throw Error(std::string("mq_ctx_submit_fastx: ") + last_error());
-                            t_submit_us += us_since(ts0);
-                            inflight[sl] = c;
-                            age[sl] = submitted++;
-                            continue;
-                        }
-                        c->hits.resize(c->starts.size());
-                        if (c->starts.empty()) {  // nothing to map in this chunk (the middle of a very long record)
-                            std::lock_guard<std::mutex> lk(mu);
-                            to_format.push_back(c);
-                            cv.notify_all();
-                            continue;
-                        }
-                        const auto ts0 = Clock::now();
-                        if (mq_ctx_submit_spans(ctx[sl], c->buf, c->bytes, c->starts.data(), c->lens.data(), (uint32_t)c->starts.size(),
-                                                c->hits.data()) != MQ_OK)
-                            throw Error(std::string("mq_ctx_submit_spans: ") + last_error());
-                        t_submit_us += us_since(ts0);
-                        inflight[sl] = c;
-                        age[sl] = submitted++;
-                    }
-                    for (int q = oldest_busy(); q >= 0; q = oldest_busy()) finish_slot(q);
-                } catch (const std::exception &e) { fail(e.what()); }
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    gpu_workers_left--;
-                }
-                cv.notify_all();
-            });
-        std::vector<std::thread> formatters;
-        for (int f = 0; f < n_format; ++f)
-            formatters.emplace_back([&]() {
-                std::string id;
-                PafWriter pw(*ro[0]);
-                for (;;) {
-                    Chunk *c = nullptr;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv.wait(lk, [&] { return !to_format.empty() || gpu_workers_left == 0; });
-                        if (to_format.empty()) return;
-                        c = to_format.front();
-                        to_format.pop_front();
-                        formatting++;
-                    }
-                    const auto tm0 = Clock::now();
-                    try {
-                    c->paf.reserve(c->lens.size() * 96);
-                    for (size_t i = 0; i < c->lens.size(); ++i) {
-                        const mq_hit &h = c->hits[i];
-                        if (h.status == MQ_HIT_MAPPED) {
-                            pw.append(c->paf, (const char *)c->buf + c->ids[i].off, c->ids[i].len, c->lens[i], h);  // src/mers.rs:181
-                            continue;
-                        }
-                        id.assign((const char *)c->buf + c->ids[i].off, c->ids[i].len);
-                        if (h.status == MQ_HIT_UNMAPPED) {
-                            if (unm) { c->unmapped += id; c->unmapped.push_back('\n'); }
-                            if (ufa) {
-                                c->unmapped_fa.push_back('>');
-                                c->unmapped_fa += id;
-                                c->unmapped_fa.push_back('\n');
-                                if (!c->regions.empty()) feeder::append_joined_region(*c, c->regions[i].first, c->regions[i].second, c->unmapped_fa);  // (joined on the device: no starts)
-                                else c->unmapped_fa.append((const char *)c->buf + c->starts[i], c->lens[i]);
-                                c->unmapped_fa.push_back('\n');
-                            }
-                        } else {
-                            fail("find_matches: read " + id + " could not be processed");
-                            break;
-                        }
-                    }
-                    } catch (const std::exception &e) { fail(e.what()); }
-                    t_format_us += us_since(tm0);
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        done[c->seq_no] = c;
-                        formatting--;
-                    }
-                    cv.notify_all();
-                }
-            });
-        // main thread: chunks in input order (main_thread_mer, src/closures.rs:117-123)
-        for (size_t next_out = 0;;) {
-            Chunk *c = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] {
-                    return done.count(next_out) != 0 || !werr.empty() || (gpu_workers_left == 0 && to_format.empty() && formatting == 0);
-                });
-                auto it = done.find(next_out);
-                if (it == done.end()) break;  // everything written, or a worker failed
-                c = it->second;
-                done.erase(it);
-            }
-            const auto tw0 = Clock::now();
-            if (!c->paf.empty()) fwrite(c->paf.data(), 1, c->paf.size(), paf);
-            if (unm && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm);
-            if (ufa && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa);
-            feed.recycle(c);
-            t_write_us += us_since(tw0);
-            ++next_out;
-        }
-        // On a failure the chunks in flight are never recycled, so the feeder's workers (waiting for a buffer) and the GPU workers
-        // (waiting for a chunk) would wait forever: the feeder is told to give up, which wakes both.
-        if (failed()) feed.abort();
-        for (auto &t : workers) t.join();
-        cv.notify_all();
-        for (auto &t : formatters) if (t.joinable()) t.join();
-        if (!werr.empty()) {
-            for (auto &v : slots) for (auto c : v) mq_ctx_free(c);
-            fclose(paf);
-            if (unm) fclose(unm);
-            if (ufa) fclose(ufa);
-            remove((prefix + ".paf").c_str());  // never leave a partial PAF behind a failure
-            throw Error(werr);
-        }
-        fclose(paf);
-        if (unm) fclose(unm);
-        if (ufa) fclose(ufa);
-        if (drv_timing)
-            fprintf(stderr, "map phase %.3f s; summed over threads: submit %.3f s, finish (wait + spans) %.3f s, waiting for a chunk %.3f s (%d submitters), "
-                            "format %.3f s (%d formatters), write + recycle %.3f s\n", secs(t0), t_submit_us / 1e6, t_finish_us / 1e6, t_fetch_us / 1e6, o.gpus * n_sub,
-                    t_format_us / 1e6, n_format, t_write_us / 1e6);
-        if (drv_timing) fprintf(stderr, "unparsed chunks %llu irregular %llu\n", (unsigned long long)n_unparsed.load(), (unsigned long long)n_irregular.load());
-        printf("Mapped query sequences in %s.\n", rust_duration(secs(t0)).c_str());  // src/closures.rs:211
-        tl("PAF written");
-        if (o.last_pass && getenv("MQ_DRIVER_FAST_EXIT") != nullptr) {
-            // EXPERIMENT: the run's output is complete and closed -- leave without unwinding (stream slots, the table, the page-locked
-            // pool: the operating system takes a process's device and host memory back in one go when it ends)
-            print_totals(g_t_main);
-            fflush(stdout);
-            fflush(stderr);
-            _exit(0);
-        }
-        // teardown, side by side: the stream slots and then the indexes (contexts go before their index) on one thread, the feeder's
-        // page-locked pool on this one -- 0.08 s one after the other on a 0.6-s job
-        {
-            std::thread dev_side([&]() {
-                for (auto &v : slots) for (auto c : v) mq_ctx_free(c);
-                ro.clear();
-            });
-            if (preload) ref_reaper = std::thread([pl = preload.release()]() { delete pl; });
-            feed.release_buffers();
-            dev_side.join();
-            if (ref_reaper.joinable()) ref_reaper.join();
-        }
-        tl("stream slots, indexes and the page-locked pool released");
+    t0 = Clock::now();
+    if (P.use_pfx && !ends_with(reads_path, ".gz") && !ends_with(reads_path, ".lz4")) puts("Warning: using experimental rust-parallelfastx (exciting!)");
+    start_feed();
+    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at});
+    try {
+        pipeline.run();
+    } catch (...) {
+        out.discard_paf();
+        throw;
+    }
+    out.close();
+    if (g_knobs.timing) pipeline.report(secs(t0));
+    printf("Mapped query sequences in %s.\n", rust_duration(secs(t0)).c_str());  // src/closures.rs:211
+    tl("PAF written");
+    teardown(o, slots, ro, preload, feed);
+    tl("stream slots, indexes and the page-locked pool released");
     return 0;
 }
 
