@@ -82,7 +82,7 @@ int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general
     return guarded([&]() -> int {
         if (!idx || !n_fast || !n_general) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
         int rc = use_device(idx);
         if (rc) return rc;
@@ -99,7 +99,7 @@ int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first) {
     return guarded([&]() -> int {
         if (!idx || !n_flagged || !n_first) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
         int rc = use_device(idx);
         if (rc) return rc;
@@ -138,7 +138,7 @@ int mq_map_probe_stats(mq_index *idx, const uint8_t *d_bases, const uint64_t *d_
     return guarded([&]() -> int {
         if (!idx || !lookups || !extra_steps) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         int rc = ctx_map_device(c, d_bases, d_offsets, n, total_bases, d_out, nullptr, true);  // the choice travels with this launch: contexts never see it
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
@@ -156,7 +156,7 @@ int mq_last_read_cycles(mq_index *idx, uint32_t n, uint32_t *cycles, uint64_t *s
     return guarded([&]() -> int {
         if (!idx || !cycles || !start_ticks) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         if (!c->ev_valid || n > c->reads_cap) return set_err(MQ_ESTATE, "no instrumented launch of that size recorded");
         int rc = use_device(idx);
         if (rc) return rc;
@@ -173,7 +173,7 @@ int mq_last_stage_clocks(mq_index *idx, uint64_t *out16) {
     return guarded([&]() -> int {
         if (!idx || !out16) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
         int rc = use_device(idx);
         if (rc) return rc;
@@ -187,7 +187,7 @@ int mq_last_map_ms(mq_index *idx, float *ms) {
     return guarded([&]() -> int {
         if (!idx || !ms) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        mq_ctx *c = idx->def_ctx;
+        mq_ctx *c = idx->def_ctx.get();
         if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
         HIPCHK(hipEventSynchronize(c->ev1));
         HIPCHK(hipEventElapsedTime(ms, c->ev0, c->ev1));

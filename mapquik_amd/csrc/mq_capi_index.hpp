@@ -3,28 +3,24 @@
 // throw runs inside guarded(); what a function allocates for itself is a Buf or a Scoped handle, so every early return gives it back.
 #pragma once
 
+using IndexPtr = std::unique_ptr<mq_index>;  // a half-built or refused index goes through ~mq_index, like one the caller frees
+
+static int check_params(const mq_params *params) {
+    if (!params) return set_err(MQ_EINVAL, "params is NULL");
+    if (params->l < 1 || params->l > MAX_L || params->k < 1 || params->k > MAX_K) return set_err(MQ_EINVAL, "unsupported k/l: need 1 <= l <= 64 and 1 <= k <= 32");
+    if (params->flags & ~(MQ_FLAG_FOLD_CASE | MQ_FLAG_FAST_KH | MQ_FLAG_SEED_VARIANT_MASK)) return set_err(MQ_EINVAL, "undefined bits in mq_params.flags");
+    const uint32_t variant = (params->flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT;
+    if ((variant & MQ_SEEDVAR_POS_RUN_END) && params->l < 2)
+        return set_err(MQ_EINVAL, "seeding variant 8 (position = end of the homopolymer run) needs l >= 2: the run's end is read off the window's second base");
+    return MQ_OK;
+}
+
 extern "C" {
 
 mq_index *mq_index_new(const mq_params *params, int device) {
     return guarded([&]() -> mq_index * {
-        if (!params) {
-            set_err(MQ_EINVAL, "params is NULL");
-            return nullptr;
-        }
-        if (params->l < 1 || params->l > MAX_L || params->k < 1 || params->k > MAX_K) {
-            set_err(MQ_EINVAL, "unsupported k/l: need 1 <= l <= 64 and 1 <= k <= 32");
-            return nullptr;
-        }
-        if (params->flags & ~(MQ_FLAG_FOLD_CASE | MQ_FLAG_FAST_KH | MQ_FLAG_SEED_VARIANT_MASK)) {
-            set_err(MQ_EINVAL, "undefined bits in mq_params.flags");
-            return nullptr;
-        }
-        const uint32_t variant = (params->flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT;
-        if ((variant & MQ_SEEDVAR_POS_RUN_END) && params->l < 2) {
-            set_err(MQ_EINVAL, "seeding variant 8 (position = end of the homopolymer run) needs l >= 2: the run's end is read off the window's second base");
-            return nullptr;
-        }
-        const bool init_timing = getenv("MQ_DRIVER_TIMING") != nullptr;  // diagnostic (stderr): where the first index's start-up time goes
+        if (check_params(params) != MQ_OK) return nullptr;
+        const bool init_timing = env_set("MQ_DRIVER_TIMING");  // diagnostic (stderr): where the first index's start-up time goes
         const auto ti0 = std::chrono::steady_clock::now();
         auto stamp = [&](const char *what) {
             if (init_timing) fprintf(stderr, "    mq_index_new: +%.3f s %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - ti0).count(), what);
@@ -39,24 +35,13 @@ mq_index *mq_index_new(const mq_params *params, int device) {
             set_err(MQ_EINVAL, "device ordinal out of range");
             return nullptr;
         }
-        std::unique_ptr<mq_index> idx(new mq_index());  // (what it holds by then goes with it on the ways out below: the device is selected)
+        IndexPtr idx(new mq_index());
         idx->params = *params;
         idx->device = device;
-        set_dev_bound(idx->dp, params->density, variant);
-        idx->dp.k = params->k;
-        idx->dp.l = params->l;
-        idx->dp.use_hpc = params->use_hpc ? 1 : 0;
-        idx->dp.c = params->c;
-        idx->dp.s = params->s;
-        idx->dp.g = params->g;
-        idx->dp.fold = (params->flags & MQ_FLAG_FOLD_CASE) ? 1u : 0u;
-        idx->dp.fast_kh = (params->flags & MQ_FLAG_FAST_KH) ? 1u : 0u;
-        const char *cc = getenv("MQ_CHAIN_CHUNK");
-        if (cc && atoi(cc) == 4) idx->chain_chunk = 4;
-        const char *fg = getenv("MQ_FORCE_GENERAL");
-        idx->force_general = fg && atoi(fg) != 0;
-        const char *hf = getenv("MQ_HEAVY_FIRST");
-        idx->heavy_first = !(hf && atoi(hf) == 0);
+        idx->dp = dev_params_from(*params, (params->flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT);
+        if (env_int("MQ_CHAIN_CHUNK", 64) == 4) idx->chain_chunk = 4;
+        idx->force_general = env_int("MQ_FORCE_GENERAL", 0) != 0;
+        idx->heavy_first = env_int("MQ_HEAVY_FIRST", 1) != 0;
         const char *pl = getenv("MQ_PIPELINE");
         idx->split = pl && strcmp(pl, "split") == 0;
         hipDeviceProp_t prop;
@@ -69,124 +54,135 @@ mq_index *mq_index_new(const mq_params *params, int device) {
         // an empty one-bucket table so that seeding-only calls work before finalize
         if (alloc_table(idx.get(), 2) != MQ_OK) return nullptr;
         stamp("first hipMalloc + hipMemset (code objects loaded)");
-        idx->def_ctx = ctx_create(idx.get());
+        idx->def_ctx.reset(ctx_create(idx.get()));
         stamp("stream created");
         if (!idx->def_ctx) return nullptr;
         return idx.release();
     });
 }
 
-void mq_index_free(mq_index *idx) {
-    if (!idx) return;
-    rsv_join(idx);
-    hipSetDevice(idx->device);
-    idx->rsv_table.reset();
-    idx->chunks.clear();
-    free_build_scratch(idx);
-    idx->table.reset();
-    idx->d_ref_lens.reset();
-    ctx_release(idx->def_ctx);
-    delete idx;
-}
+void mq_index_free(mq_index *idx) { delete idx; }
 
-static int64_t add_ref_device_locked(mq_index *idx, uint32_t ref_id, const char *name, const uint8_t *d_seq, uint64_t len) {
-    if (!idx || (!d_seq && len)) return set_err(MQ_EINVAL, "bad arguments");
+}  // extern "C"
+
+// ---- mq_index_add_ref_device in steps (all on the null stream: the next call's kernels, and finalize, are ordered behind them)
+
+// what every mq_index_add_ref* refuses before anything is registered or overwritten
+static int check_new_ref(const mq_index *idx, uint32_t ref_id, uint64_t len) {
     if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
     if (len >= (1ull << 32)) return set_err(MQ_EINVAL, "sequence length must be < 2^32");
     if (ref_id >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, "ref_id must be < 2^24 (reference lengths are kept in a dense device array)");
     if (idx->refs.count(ref_id)) return set_err(MQ_EINVAL, "duplicate ref_id");
-    int rc = use_device(idx);
-    if (rc) return rc;
-    idx->refs[ref_id] = std::make_pair(std::string(name ? name : ""), len);
-    const DevParams &P = idx->dp;
-    if (len < (uint64_t)P.l + P.k - 1) return 0;  // src/mers.rs:18
-    if (P.keep_none) return 0;                    // (seeding variant 1 with a bound of 0: no l-mer passes `hash < 0`)
-    const bool with_last = (P.variant & MQ_SEEDVAR_END_COMPRESSED) != 0;
+    return MQ_OK;
+}
 
+static uint32_t *dense_last_of(mq_index *idx) { return (idx->dp.variant & MQ_SEEDVAR_END_COMPRESSED) ? idx->bld.dense_last.p : nullptr; }
+
+// the scratch of the seeders sized for this sequence (and cleared where they count), and their arguments
+static int plan_ref_seed(mq_index *idx, const uint8_t *d_seq, uint64_t len, RefSeedArgs *A) {
+    BuildScratch &b = idx->bld;
+    const bool with_last = (idx->dp.variant & MQ_SEEDVAR_END_COMPRESSED) != 0;
     const uint32_t n_seg = (uint32_t)((len + REF_SEG - 1) / REF_SEG);
     // expected minimizers per segment: 2 * density of the compressed l-mers; cap with slack, worst case on retry
     double dens = idx->params.density;
     if (!(dens > 0)) dens = 0;
     if (dens > 1) dens = 1;
     uint32_t cap = (uint32_t)std::min<double>((double)REF_SEG, 3.0 * 2.0 * dens * (double)REF_SEG + 256.0);
-    if (const char *e = getenv("MQ_REF_CAP")) cap = (uint32_t)std::max(1, atoi(e));  // test hook: tiny regions, so that segments take the redo path
-    if ((rc = idx->bld.counts.ensure(n_seg))) return rc;
-    if ((rc = idx->bld.queue.ensure(n_seg))) return rc;
-    if ((rc = idx->bld.seg_off.ensure((uint64_t)n_seg + 1))) return rc;
-    if (!idx->bld.info && (rc = idx->bld.info.alloc(8))) return rc;
+    if (env_set("MQ_REF_CAP")) cap = (uint32_t)std::max(1, env_int("MQ_REF_CAP", 1));  // test hook: tiny regions, so that segments take the redo path
+    int rc;
+    if ((rc = b.counts.ensure(n_seg))) return rc;
+    if ((rc = b.queue.ensure(n_seg))) return rc;
+    if ((rc = b.seg_off.ensure((uint64_t)n_seg + 1))) return rc;
+    if (!b.info && (rc = b.info.alloc(8))) return rc;
     if (!idx->grid_ref) {
         int occ = 0;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)seed_ref_kernel, 64 * SEED_WAVES, 0));
         idx->grid_ref = std::max(1, occ) * idx->n_cu;
     }
-    unsigned long long info[2] = {0, 0};
-    if ((rc = idx->bld.seg_hash.ensure((uint64_t)n_seg * cap))) return rc;
-    if ((rc = idx->bld.seg_pos.ensure((uint64_t)n_seg * cap))) return rc;
-    if (with_last && (rc = idx->bld.seg_last.ensure((uint64_t)n_seg * cap))) return rc;
-    HIPCHK(hipMemsetAsync(idx->bld.info, 0, 64, 0));
-    RefSeedArgs A;
-    A.seq = d_seq;
-    A.len = len;
-    A.n_seg = n_seg;
-    A.P = P;
-    A.seg_hash = idx->bld.seg_hash;
-    A.seg_pos = idx->bld.seg_pos;
-    A.seg_last = with_last ? idx->bld.seg_last.p : nullptr;
-    A.cap = cap;
-    A.counts = idx->bld.counts;
-    A.queue = idx->bld.queue;
-    A.counters = reinterpret_cast<uint32_t *>(idx->bld.info + 2);
-    A.force_general = idx->force_general ? 1u : 0u;
-    {
-        const uint32_t g1 = std::min<uint32_t>((uint32_t)idx->grid_ref, (n_seg + SEED_WAVES - 1) / SEED_WAVES);
-        hipLaunchKernelGGL(seed_ref_kernel, dim3(g1), dim3(64 * SEED_WAVES), 0, 0, A);
-        HIPCHK(hipGetLastError());
-        // the queue's length lives on the device: a fixed grid, waves that find the queue empty leave at once
-        hipLaunchKernelGGL(seed_ref_general_kernel, dim3(std::min<uint32_t>((uint32_t)idx->n_cu * 32u, n_seg)), dim3(64), 0, 0, A);
-        HIPCHK(hipGetLastError());
-        // (the fast seeder's queue is consumed by now: the same array takes the numbers of the segments whose list outgrew its region)
-        hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, 0, idx->bld.counts, n_seg, cap, idx->bld.seg_off, idx->bld.info, idx->bld.queue);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(info, idx->bld.info, 16, hipMemcpyDeviceToHost));
-    }
-    const uint32_t n_over = (uint32_t)info[1];
-    const uint64_t n_mz = info[0];
-    int64_t n_kmm = 0;
-    if (n_mz >= P.k) {
-        n_kmm = (int64_t)(n_mz - P.k + 1);
-        if ((rc = idx->bld.dense_hash.ensure(n_mz))) return rc;
-        if ((rc = idx->bld.dense_pos.ensure(n_mz))) return rc;
-        if (with_last && (rc = idx->bld.dense_last.ensure(n_mz))) return rc;
-        uint32_t *const dense_last = with_last ? idx->bld.dense_last.p : nullptr;
-        hipLaunchKernelGGL(compact_lists_kernel, dim3(std::min<uint32_t>(n_seg, 65535u)), dim3(64), 0, 0, idx->bld.seg_hash, idx->bld.seg_pos, cap,
-                           idx->bld.counts, idx->bld.seg_off, n_seg, idx->bld.dense_hash, idx->bld.dense_pos, A.seg_last, dense_last);
-        HIPCHK(hipGetLastError());
-        if (n_over) {
-            hipLaunchKernelGGL(seed_ref_redo_kernel, dim3(std::min<uint32_t>(n_over, (uint32_t)idx->n_cu * 32u)), dim3(64), 0, 0, A, idx->bld.queue, n_over,
-                               idx->bld.seg_off, idx->bld.dense_hash, idx->bld.dense_pos, dense_last);
-            HIPCHK(hipGetLastError());
-        }
-        // the reference's k-min-mers go behind those of the previous references in the current chunk while it has room
-        if (idx->chunks.empty() || idx->chunks.back().n + (uint64_t)n_kmm > idx->chunks.back().d.cap) {
-            KmmChunk ch;
-            if ((rc = ch.d.alloc(std::max<uint64_t>((uint64_t)n_kmm, 16ull << 20)))) return rc;
-            idx->chunks.push_back(std::move(ch));
-        }
-        KmmChunk &ch = idx->chunks.back();
-        const uint32_t kb = (uint32_t)std::min<uint64_t>(((uint64_t)n_kmm + 255) / 256, 65535ull);
-        hipLaunchKernelGGL(ref_kminmers_kernel, dim3(kb), dim3(256), 0, 0, idx->bld.dense_hash, idx->bld.dense_pos, n_mz, P, ref_id, ch.d + ch.n, dense_last);
-        HIPCHK(hipGetLastError());
-        ch.n += (uint64_t)n_kmm;
-        idx->n_kmm_total += (uint64_t)n_kmm;
-    }
-    return n_kmm;  // everything above runs on the null stream: the next call's kernels (and finalize) are ordered behind it
+    if ((rc = b.seg_hash.ensure((uint64_t)n_seg * cap))) return rc;
+    if ((rc = b.seg_pos.ensure((uint64_t)n_seg * cap))) return rc;
+    if (with_last && (rc = b.seg_last.ensure((uint64_t)n_seg * cap))) return rc;
+    HIPCHK(hipMemsetAsync(b.info, 0, 64, 0));
+    *A = RefSeedArgs{d_seq, len, n_seg, idx->dp, b.seg_hash, b.seg_pos, with_last ? b.seg_last.p : nullptr, cap, b.counts, b.queue,
+                     reinterpret_cast<uint32_t *>(b.info + 2), idx->force_general ? 1u : 0u};
+    return MQ_OK;
 }
+
+// the fast seeder, the general one for the segments it declined, the scan of the counts; *n_mz: minimizers of the sequence, *n_over:
+// segments whose list outgrew its region
+static int seed_ref_segments(mq_index *idx, const RefSeedArgs &A, uint64_t *n_mz, uint32_t *n_over) {
+    BuildScratch &b = idx->bld;
+    int rc;
+    if ((rc = launch(seed_ref_kernel, std::min<uint32_t>((uint32_t)idx->grid_ref, (A.n_seg + SEED_WAVES - 1) / SEED_WAVES), 64 * SEED_WAVES, 0, A))) return rc;
+    // the queue's length lives on the device: a fixed grid, waves that find the queue empty leave at once
+    if ((rc = launch(seed_ref_general_kernel, std::min<uint32_t>((uint32_t)idx->n_cu * 32u, A.n_seg), 64, 0, A))) return rc;
+    // (the fast seeder's queue is consumed by now: the same array takes the numbers of the segments whose list outgrew its region)
+    if ((rc = launch(scan_counts_kernel, 1, 1024, 0, b.counts, A.n_seg, A.cap, b.seg_off, b.info, b.queue))) return rc;
+    unsigned long long info[2] = {0, 0};
+    HIPCHK(hipMemcpy(info, b.info, 16, hipMemcpyDeviceToHost));
+    *n_mz = info[0];
+    *n_over = (uint32_t)info[1];
+    return MQ_OK;
+}
+
+// the segments' lists into the sequence's dense list; the segments that overflowed seeded again, straight into their place in it
+static int compact_and_redo(mq_index *idx, const RefSeedArgs &A, uint64_t n_mz, uint32_t n_over) {
+    BuildScratch &b = idx->bld;
+    int rc;
+    if ((rc = b.dense_hash.ensure(n_mz))) return rc;
+    if ((rc = b.dense_pos.ensure(n_mz))) return rc;
+    if (A.seg_last && (rc = b.dense_last.ensure(n_mz))) return rc;
+    if ((rc = launch(compact_lists_kernel, std::min<uint32_t>(A.n_seg, 65535u), 64, 0, b.seg_hash, b.seg_pos, A.cap, b.counts, b.seg_off, A.n_seg, b.dense_hash, b.dense_pos,
+                     A.seg_last, dense_last_of(idx))))
+        return rc;
+    if (!n_over) return MQ_OK;
+    return launch(seed_ref_redo_kernel, std::min<uint32_t>(n_over, (uint32_t)idx->n_cu * 32u), 64, 0, A, b.queue, n_over, b.seg_off, b.dense_hash, b.dense_pos, dense_last_of(idx));
+}
+
+// the reference's k-min-mers go behind those of the previous references in the current chunk while it has room
+static int append_kminmers(mq_index *idx, uint32_t ref_id, uint64_t n_mz, uint64_t n_kmm) {
+    int rc;
+    if (idx->chunks.empty() || idx->chunks.back().n + n_kmm > idx->chunks.back().d.cap) {
+        KmmChunk ch;
+        if ((rc = ch.d.alloc(std::max<uint64_t>(n_kmm, 16ull << 20)))) return rc;
+        idx->chunks.push_back(std::move(ch));
+    }
+    KmmChunk &ch = idx->chunks.back();
+    const uint32_t kb = (uint32_t)std::min<uint64_t>((n_kmm + 255) / 256, 65535ull);
+    if ((rc = launch(ref_kminmers_kernel, kb, 256, 0, idx->bld.dense_hash, idx->bld.dense_pos, n_mz, idx->dp, ref_id, ch.d + ch.n, dense_last_of(idx)))) return rc;
+    ch.n += n_kmm;
+    idx->n_kmm_total += n_kmm;
+    return MQ_OK;
+}
+
+static int64_t add_ref_device_locked(mq_index *idx, uint32_t ref_id, const char *name, const uint8_t *d_seq, uint64_t len) {
+    if (!idx || (!d_seq && len)) return set_err(MQ_EINVAL, "bad arguments");
+    int rc = check_new_ref(idx, ref_id, len);
+    if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
+    idx->refs[ref_id] = std::make_pair(std::string(name ? name : ""), len);
+    const DevParams &P = idx->dp;
+    if (len < (uint64_t)P.l + P.k - 1) return 0;  // src/mers.rs:18
+    if (P.keep_none) return 0;                    // (seeding variant 1 with a bound of 0: no l-mer passes `hash < 0`)
+    RefSeedArgs A;
+    uint64_t n_mz = 0;
+    uint32_t n_over = 0;
+    if ((rc = plan_ref_seed(idx, d_seq, len, &A))) return rc;
+    if ((rc = seed_ref_segments(idx, A, &n_mz, &n_over))) return rc;
+    if (n_mz < P.k) return 0;
+    const uint64_t n_kmm = n_mz - P.k + 1;
+    if ((rc = compact_and_redo(idx, A, n_mz, n_over))) return rc;
+    if ((rc = append_kminmers(idx, ref_id, n_mz, n_kmm))) return rc;
+    return (int64_t)n_kmm;
+}
+
+extern "C" {
 
 int64_t mq_index_add_ref_device(mq_index *idx, uint32_t ref_id, const char *name, const uint8_t *d_seq, uint64_t len) {
     return guarded([&]() -> int64_t {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
-        if (!getenv("MQ_BUILD_TIMING")) return add_ref_device_locked(idx, ref_id, name, d_seq, len);
+        if (!env_set("MQ_BUILD_TIMING")) return add_ref_device_locked(idx, ref_id, name, d_seq, len);
         hipDeviceSynchronize();
         const auto t0 = std::chrono::steady_clock::now();
         const int64_t r = add_ref_device_locked(idx, ref_id, name, d_seq, len);
@@ -221,17 +217,7 @@ int mq_index_stage_begin(mq_index *idx, uint64_t total_bytes) {
         if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
         int rc = use_device(idx);
         if (rc) return rc;
-        std::lock_guard<std::mutex> lk(idx->stg_mu);
-        if (idx->stg_buf) return set_err(MQ_ESTATE, "mq_index_stage_begin: one staging buffer per index");
-        if ((rc = idx->stg_buf.alloc(total_bytes + 64))) return rc;
-        const hipError_t es = hipStreamCreateWithFlags(&idx->stg_stream, hipStreamNonBlocking);
-        if (es != hipSuccess) {  // no buffer without its stream: a later mq_index_stage_piece must not find one
-            idx->stg_buf.reset();
-            idx->stg_stream = nullptr;
-            return set_err(MQ_EHIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(es));
-        }
-        idx->stg_bytes = total_bytes;
-        return MQ_OK;
+        return idx->stage.begin(total_bytes);
     });
 }
 
@@ -240,20 +226,7 @@ int mq_index_stage_piece(mq_index *idx, uint64_t at, const uint8_t *src, uint64_
         if (!idx || (!src && n) || !ticket) return set_err(MQ_EINVAL, "bad arguments");
         int rc = use_device(idx);
         if (rc) return rc;
-        std::lock_guard<std::mutex> lk(idx->stg_mu);
-        if (!idx->stg_buf) return set_err(MQ_ESTATE, "mq_index_stage_piece before mq_index_stage_begin");
-        if (at > idx->stg_bytes || n > idx->stg_bytes - at) return set_err(MQ_EINVAL, "piece outside the staging buffer");
-        if (n) HIPCHK(hipMemcpyAsync(idx->stg_buf + at, src, n, hipMemcpyHostToDevice, idx->stg_stream));
-        // ticket t <=> stg_events[t], a RECORDED event: the event joins the list only once its record has succeeded (a ticket that indexed an
-        // event never recorded would let a wait return at once and a record be indexed before its bytes arrive)
-        ScopedEvent ev;
-        HIPCHK(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-        const hipError_t er = hipEventRecord(ev, idx->stg_stream);
-        if (er != hipSuccess) return set_err(MQ_EHIP, std::string("hipEventRecord: ") + hipGetErrorString(er));
-        idx->stg_events.push_back(ev);
-        ev.h = nullptr;  // (the list's events are free_stage's to destroy)
-        *ticket = idx->stg_issued++;
-        return MQ_OK;
+        return idx->stage.piece(at, src, n, ticket);
     });
 }
 
@@ -262,39 +235,8 @@ int mq_index_stage_done(mq_index *idx, uint64_t ticket, int wait) {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         int rc = use_device(idx);
         if (rc) return rc;
-        hipEvent_t ev;
-        {
-            std::lock_guard<std::mutex> lk(idx->stg_mu);
-            if (ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
-            ev = idx->stg_events[(size_t)ticket];
-        }
-        if (wait) {
-            HIPCHK(hipEventSynchronize(ev));
-            return 1;
-        }
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) return 1;
-        if (e == hipErrorNotReady) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        return set_err(MQ_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
+        return idx->stage.done(ticket, wait);
     });
-}
-
-// the state, range and ticket checks of the calls that read the staging buffer, and the null stream made to wait for the pieces;
-// *d_region: buffer + at
-static int staged_region(mq_index *idx, const char *who, uint64_t at, uint64_t bytes, uint64_t after_ticket, const uint8_t **d_region) {
-    std::lock_guard<std::mutex> lk(idx->stg_mu);
-    if (!idx->stg_buf) return set_err(MQ_ESTATE, std::string(who) + " before mq_index_stage_begin");
-    if (at > idx->stg_bytes || bytes > idx->stg_bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
-    if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= idx->stg_issued) return set_err(MQ_EINVAL, "unknown ticket");
-    // the build's kernels run on the null stream: it waits (on the device, not here) for the piece named (pieces complete in issue
-    // order, so for every piece up to it), or for every piece issued so far
-    const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? idx->stg_issued : after_ticket + 1;
-    if (upto) HIPCHK(hipStreamWaitEvent(0, idx->stg_events[(size_t)upto - 1], 0));
-    *d_region = idx->stg_buf + at;
-    return MQ_OK;
 }
 
 int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name, uint64_t at, uint64_t len, uint64_t after_ticket) {
@@ -303,7 +245,7 @@ int64_t mq_index_add_ref_staged(mq_index *idx, uint32_t ref_id, const char *name
         int rc = use_device(idx);
         if (rc) return rc;
         const uint8_t *d_seq = nullptr;
-        if ((rc = staged_region(idx, "mq_index_add_ref_staged", at, len, after_ticket, &d_seq))) return rc;
+        if ((rc = idx->stage.region("mq_index_add_ref_staged", at, len, after_ticket, &d_seq))) return rc;
         std::lock_guard<std::mutex> lk(idx->mu);
         return add_ref_device_locked(idx, ref_id, name, d_seq, len);
     });
@@ -330,12 +272,9 @@ static int join_lines_locked(mq_index *idx, const uint8_t *d_region, uint64_t at
     if ((rc = idx->bld.join_off.ensure(n_tiles))) return rc;
     if (!idx->bld.join_total && (rc = idx->bld.join_total.alloc(1))) return rc;
     const uint32_t grid = fx_grid(idx, n_tiles);
-    hipLaunchKernelGGL(join_count_kernel, dim3(grid), dim3(256), 0, 0, base, begin, end, n_tiles, idx->bld.join_counts);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(join_scan_kernel, dim3(1), dim3(1024), 0, 0, idx->bld.join_counts, n_tiles, idx->bld.join_off, idx->bld.join_total);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(join_write_kernel, dim3(grid), dim3(256), 0, 0, base, begin, end, n_tiles, idx->bld.join_off, idx->bld.seq);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(join_count_kernel, grid, 256, 0, base, begin, end, n_tiles, idx->bld.join_counts))) return rc;
+    if ((rc = launch(join_scan_kernel, 1, 1024, 0, idx->bld.join_counts, n_tiles, idx->bld.join_off, idx->bld.join_total))) return rc;
+    if ((rc = launch(join_write_kernel, grid, 256, 0, base, begin, end, n_tiles, idx->bld.join_off, idx->bld.seq))) return rc;
     unsigned long long total = 0;
     HIPCHK(hipMemcpy(&total, idx->bld.join_total, 8, hipMemcpyDeviceToHost));
     *joined = total;
@@ -348,12 +287,9 @@ int64_t mq_index_add_ref_staged_lines(mq_index *idx, uint32_t ref_id, const char
         int rc = use_device(idx);
         if (rc) return rc;
         const uint8_t *d_region = nullptr;
-        if ((rc = staged_region(idx, "mq_index_add_ref_staged_lines", at, bytes, after_ticket, &d_region))) return rc;
+        if ((rc = idx->stage.region("mq_index_add_ref_staged_lines", at, bytes, after_ticket, &d_region))) return rc;
         std::lock_guard<std::mutex> lk(idx->mu);
-        // (what add_ref_device_locked would refuse is refused before the join: nothing is registered, nothing is overwritten)
-        if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
-        if (ref_id >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, "ref_id must be < 2^24 (reference lengths are kept in a dense device array)");
-        if (idx->refs.count(ref_id)) return set_err(MQ_EINVAL, "duplicate ref_id");
+        if ((rc = check_new_ref(idx, ref_id, 0))) return rc;  // before the join overwrites bld.seq (the joined length is not known yet)
         uint64_t joined = 0;
         if ((rc = join_lines_locked(idx, d_region, at, bytes, &joined))) return rc;
         if (joined >= (1ull << 32)) return set_err(MQ_EINVAL, "sequence length must be < 2^32");
@@ -368,7 +304,7 @@ int64_t mq_index_staged_sequence(mq_index *idx, uint64_t at, uint64_t bytes, uin
         int rc = use_device(idx);
         if (rc) return rc;
         const uint8_t *d_region = nullptr;
-        if ((rc = staged_region(idx, "mq_index_staged_sequence", at, bytes, after_ticket, &d_region))) return rc;
+        if ((rc = idx->stage.region("mq_index_staged_sequence", at, bytes, after_ticket, &d_region))) return rc;
         std::lock_guard<std::mutex> lk(idx->mu);
         if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
         uint64_t joined = 0;
@@ -390,7 +326,7 @@ int mq_index_set_table_factor(mq_index *idx, uint32_t slots_per_kminmer) {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         if (slots_per_kminmer < 2 || slots_per_kminmer > 64) return set_err(MQ_EINVAL, "slots per k-min-mer: 2..64");
         std::lock_guard<std::mutex> lk(idx->mu);
-        if (idx->finalized || idx->rsv_thread.joinable() || idx->rsv_table) return set_err(MQ_ESTATE, "mq_index_set_table_factor: before mq_index_reserve / mq_index_finalize");
+        if (idx->finalized || idx->rsv.made()) return set_err(MQ_ESTATE, "mq_index_set_table_factor: before mq_index_reserve / mq_index_finalize");
         idx->table_factor = slots_per_kminmer;
         return MQ_OK;
     });
@@ -406,23 +342,8 @@ int mq_index_reserve(mq_index *idx, uint64_t expected_kminmers) {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
         if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
-        if (idx->rsv_thread.joinable() || idx->rsv_table) return MQ_OK;  // one reservation per index
-        const uint64_t nslots = table_slots_for(idx, expected_kminmers);
-        idx->rsv_nslots = nslots;
-        const int device = idx->device;
-        idx->rsv_thread = std::thread([idx, nslots, device]() {
-            hipError_t e = hipSetDevice(device);
-            Buf<Bucket> t;
-            const auto t0 = std::chrono::steady_clock::now();
-            if (e == hipSuccess) e = t.try_alloc(table_bytes_of(nslots) / sizeof(Bucket));
-            ScopedStream st;
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.h, hipStreamNonBlocking);  // not the null stream: the build's kernels run there
-            if (e == hipSuccess) e = hipMemsetAsync(t, 0, table_bytes_of(nslots), st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            idx->rsv_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            if (e == hipSuccess) idx->rsv_table = std::move(t);  // (finalize joins this thread before it looks)
-            idx->rsv_err = (int)e;
-        });
+        if (idx->rsv.made()) return MQ_OK;  // one reservation per index
+        idx->rsv.start(idx->device, table_slots_for(idx, expected_kminmers));
         return MQ_OK;
     });
 }
@@ -434,7 +355,7 @@ int64_t mq_index_finalize(mq_index *idx) {
         if (idx->finalized) return (int64_t)idx->n_unique;
         int rc = use_device(idx);
         if (rc) return rc;
-        const bool timing = getenv("MQ_BUILD_TIMING") != nullptr;  // diagnostic: where the wall time of finalize goes (stderr)
+        const bool timing = env_set("MQ_BUILD_TIMING");  // diagnostic: where the wall time of finalize goes (stderr)
         auto tnow = [&]() {
             if (timing) hipDeviceSynchronize();
             return std::chrono::steady_clock::now();
@@ -445,15 +366,12 @@ int64_t mq_index_finalize(mq_index *idx) {
         // random access of a memory system that sustains ~52 G of them per second (tools/probe_rate.py).  Measured on the CHM13-like
         // bench: factor 2: 926, 4: 1000, 8: 1034, 16: 1044, 32: 1051 Gbases/s.
         const uint64_t nslots = table_slots_for(idx, idx->n_kmm_total);
-        rsv_join(idx);
-        if (idx->rsv_table && idx->rsv_nslots == nslots && idx->rsv_err == 0) {  // the table mq_index_reserve allocated and cleared
-            idx->table = std::move(idx->rsv_table);
+        if (Buf<Bucket> reserved = idx->rsv.take(nslots)) {  // the table mq_index_reserve allocated and cleared
+            idx->table = std::move(reserved);
             idx->nslots = nslots;
-            idx->table_alloc_ms = idx->rsv_ms;
-        } else {
-            idx->rsv_table.reset();  // the estimate was off: the table is allocated now, at the size the reference needs
-            rc = alloc_table(idx, nslots);
-            if (rc) return rc;
+            idx->table_alloc_ms = idx->rsv.ms;
+        } else if ((rc = alloc_table(idx, nslots))) {  // no reservation, or the estimate was off: allocated now, at the size the reference needs
+            return rc;
         }
         auto t_1 = tnow();
         Buf<unsigned long long> d_acc;
@@ -462,8 +380,7 @@ int64_t mq_index_finalize(mq_index *idx) {
         for (auto &c : idx->chunks) {
             if (!c.n) continue;
             const uint32_t nb = (uint32_t)std::min<uint64_t>((c.n + 255) / 256, 1u << 20);
-            hipLaunchKernelGGL(insert_kernel, dim3(nb), dim3(256), 0, 0, c.d, c.n, idx->table, nslots - 1, d_acc);
-            HIPCHK(hipGetLastError());
+            if ((rc = launch(insert_kernel, nb, 256, 0, c.d, c.n, idx->table, nslots - 1, d_acc))) return rc;
         }
         auto t_2 = tnow();
         // Index::get_count (src/index.rs:90-92): keys claimed minus keys that turned dead, counted by the insertions themselves

@@ -532,7 +532,7 @@ int mq_map_batch_device(mq_index *idx, const uint8_t *d_bases, const uint64_t *d
     return guarded([&]() -> int {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
-        return ctx_map_device(idx->def_ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
+        return ctx_map_device(idx->def_ctx.get(), d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
     });
 }
 
@@ -540,9 +540,9 @@ int mq_map_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, u
     return guarded([&]() -> int {
         if (!idx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        int rc = ctx_submit(idx->def_ctx, bases, 0, offsets, nullptr, n, out);
+        int rc = ctx_submit(idx->def_ctx.get(), bases, 0, offsets, nullptr, n, out);
         if (rc) return rc;
-        return ctx_wait(idx->def_ctx);
+        return ctx_wait(idx->def_ctx.get());
     });
 }
 
@@ -559,7 +559,7 @@ int mq_kminmers_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offse
         for (uint32_t i = 0; i < n; ++i)
             if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= (1ull << 32)) return set_err(MQ_EINVAL, "bad offsets / sequence length must be < 2^32");
         // parity/debug entry point: list regions sized for the worst case (one minimizer per base), so no sequence overflows
-        rc = ctx_ensure(idx->def_ctx, n, total, 65536u);
+        rc = ctx_ensure(idx->def_ctx.get(), n, total, 65536u);
         if (rc) return rc;
         Buf<uint8_t> d_b;
         Buf<uint64_t> d_o, d_ko;
@@ -590,7 +590,7 @@ int mq_kminmers_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offse
             o.d_dump_off = d_ko;
             o.d_dump_counts = d_c;
             o.f16 = 65536u;
-            rc = launch_map(idx->def_ctx, d_b, d_o, n, d_h, 0, o);
+            rc = launch_map(idx->def_ctx.get(), d_b, d_o, n, d_h, 0, o);
         }
         if (rc) return rc;
         ok(hipMemcpy(counts, d_c, (size_t)n * 4, hipMemcpyDeviceToHost));

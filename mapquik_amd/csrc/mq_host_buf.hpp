@@ -62,20 +62,37 @@ static void reset_all(B &...b) {  // a group of buffers under one capacity: all 
     (b.reset(), ...);
 }
 
-// One handle (an event, a stream, a block of mq_host_alloc) given back when its owner goes.
+// One handle (an event, a stream, a block of mq_host_alloc) given back when its owner goes.  Movable, so that a std::vector can hold them.
 template <class H, auto Destroy>
 struct Scoped {
     H h = nullptr;
     Scoped() = default;
-    Scoped(const Scoped &) = delete;
+    Scoped(Scoped &&o) noexcept : h(o.h) { o.h = nullptr; }
     Scoped &operator=(const Scoped &) = delete;
-    ~Scoped() {
+    ~Scoped() { reset(); }
+    void reset() {
         if (h) (void)Destroy(h);
+        h = nullptr;
     }
     operator H() const { return h; }
 };
 using ScopedEvent = Scoped<hipEvent_t, hipEventDestroy>;
 using ScopedStream = Scoped<hipStream_t, hipStreamDestroy>;
+
+// A file descriptor closed when its owner goes; close() for the caller who wants to know how the close went.
+struct ScopedFd {
+    int fd = -1;
+    explicit ScopedFd(int f) : fd(f) {}
+    ScopedFd(const ScopedFd &) = delete;
+    ScopedFd &operator=(const ScopedFd &) = delete;
+    ~ScopedFd() { (void)close(); }
+    bool close() {
+        const bool ok = fd < 0 || ::close(fd) == 0;
+        fd = -1;
+        return ok;
+    }
+    operator int() const { return fd; }
+};
 
 // The extern "C" boundary: no exception leaves the library.  R is the entry point's return type: an error code for int / int64_t, nullptr
 // for the entry points that return a handle.

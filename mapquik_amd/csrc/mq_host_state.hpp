@@ -1,11 +1,27 @@
-// mq_host_state.hpp -- host-side state behind the C ABI (part of the one translation unit mq_capi.hip): mq_ctx (a stream slot) and mq_index, whose
-// buffers are the owning types of mq_host_buf.hpp, the table of map kernels, launch geometry, scratch management.
+// mq_host_state.hpp -- host-side state behind the C ABI (part of the one translation unit mq_capi.hip): mq_ctx (a stream slot) and mq_index
+// with the owners of its parts (StageState, TableReservation, BuildScratch; buffers and handles are the owning types of mq_host_buf.hpp),
+// the table of map kernels, launch geometry, scratch management.
 #pragma once
 
 // =================================================================== host side
 
 constexpr uint32_t MQ_MAX_REF_ID = 1u << 24;
 struct mq_index;
+
+// The MQ_* test and diagnostic hooks.  Each is read where it acts, never cached at mq_index_new: tests change them between calls.
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
+static int env_int(const char *name, int fallback) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : fallback;
+}
+
+// One kernel launch with its launch error checked.  The arguments are taken as the kernel's own parameter types, so a Buf converts at the call.
+template <class... KA>
+static int launch(void (*kernel)(KA...), uint32_t grid, uint32_t block, hipStream_t stream, std::common_type_t<KA>... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, args...);
+    HIPCHK(hipGetLastError());
+    return MQ_OK;
+}
 
 // A piece of a FASTX file whose records the device finds (mq_ctx_submit_fastx): none in flight, or its format
 enum class FxKind { None, Fasta, Fastq, FastaLines };
@@ -63,6 +79,17 @@ struct mq_ctx {
     mq_hit *p_out = nullptr;
 };
 
+// (the caller has selected the index's device: the context's buffers, events and stream go with it)
+static void ctx_release(mq_ctx *c) {
+    if (!c) return;
+    if (c->stream) hipStreamSynchronize(c->stream);
+    delete c;
+}
+struct CtxRelease {
+    void operator()(mq_ctx *c) const { ctx_release(c); }
+};
+using CtxPtr = std::unique_ptr<mq_ctx, CtxRelease>;
+
 struct KmmChunk {
     Buf<RefKmm> d;   // d.cap k-min-mers of room
     uint64_t n = 0;  // k-min-mers of several references share a chunk (assemblies with 10^5 small contigs)
@@ -84,6 +111,132 @@ struct BuildScratch {
     Buf<unsigned long long> join_off, join_total;
 };
 
+// mq_index_stage_*: the reference file's bytes on their way to the device piece by piece (a buffer of the file's size, an upload
+// stream, one event per piece); a state of its own behind its own lock, so that pieces keep flowing while a record is being indexed.
+// (The caller has selected the index's device.)
+struct StageState {
+    std::mutex mu;
+    Buf<uint8_t> buf;
+    uint64_t bytes = 0;
+    ScopedStream stream;
+    std::vector<ScopedEvent> events;  // ticket t = event t (tickets count from 0): the pieces issued so far, every event RECORDED
+
+    int begin(uint64_t total_bytes) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (buf) return set_err(MQ_ESTATE, "mq_index_stage_begin: one staging buffer per index");
+        // no buffer without its stream (a later piece() must not find one): the buffer becomes the state's only once the stream exists
+        Buf<uint8_t> b;
+        int rc = b.alloc(total_bytes + 64);
+        if (rc) return rc;
+        hipStream_t st = nullptr;
+        const hipError_t es = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (es != hipSuccess) return set_err(MQ_EHIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(es));
+        stream.h = st;
+        buf = std::move(b);
+        bytes = total_bytes;
+        return MQ_OK;
+    }
+    int piece(uint64_t at, const uint8_t *src, uint64_t n, uint64_t *ticket) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!buf) return set_err(MQ_ESTATE, "mq_index_stage_piece before mq_index_stage_begin");
+        if (at > bytes || n > bytes - at) return set_err(MQ_EINVAL, "piece outside the staging buffer");
+        if (n) HIPCHK(hipMemcpyAsync(buf + at, src, n, hipMemcpyHostToDevice, stream));
+        // the event joins the list, and its ticket exists, only once its record has succeeded (a ticket that indexed an event never
+        // recorded would let a wait return at once and a record be indexed before its bytes arrive)
+        ScopedEvent ev;
+        HIPCHK(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
+        const hipError_t er = hipEventRecord(ev, stream);
+        if (er != hipSuccess) return set_err(MQ_EHIP, std::string("hipEventRecord: ") + hipGetErrorString(er));
+        events.push_back(std::move(ev));
+        *ticket = events.size() - 1;
+        return MQ_OK;
+    }
+    // 1: the piece has arrived, 0: not yet (wait == 0 only)
+    int done(uint64_t ticket, int wait) {
+        hipEvent_t ev;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (ticket >= events.size()) return set_err(MQ_EINVAL, "unknown ticket");
+            ev = events[(size_t)ticket];
+        }
+        if (wait) {
+            HIPCHK(hipEventSynchronize(ev));
+            return 1;
+        }
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipSuccess) return 1;
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        return set_err(MQ_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
+    }
+    // the state, range and ticket checks of the calls that read the staging buffer, and the null stream made to wait for the pieces;
+    // *d_region: buffer + at
+    int region(const char *who, uint64_t at, uint64_t n, uint64_t after_ticket, const uint8_t **d_region) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!buf) return set_err(MQ_ESTATE, std::string(who) + " before mq_index_stage_begin");
+        if (at > bytes || n > bytes - at) return set_err(MQ_EINVAL, "record outside the staging buffer");
+        if (after_ticket != MQ_STAGE_ALL_ISSUED && after_ticket >= events.size()) return set_err(MQ_EINVAL, "unknown ticket");
+        // the build's kernels run on the null stream: it waits (on the device, not here) for the piece named (pieces complete in issue
+        // order, so for every piece up to it), or for every piece issued so far
+        const uint64_t upto = after_ticket == MQ_STAGE_ALL_ISSUED ? events.size() : after_ticket + 1;
+        if (upto) HIPCHK(hipStreamWaitEvent(0, events[(size_t)upto - 1], 0));
+        *d_region = buf + at;
+        return MQ_OK;
+    }
+    // pieces still on their way arrive first; then the events, the stream and the buffer go
+    void reset() {
+        std::lock_guard<std::mutex> lk(mu);
+        if (stream) hipStreamSynchronize(stream);
+        events.clear();
+        stream.reset();
+        buf.reset();
+        bytes = 0;
+    }
+    ~StageState() { reset(); }
+};
+
+static size_t table_bytes_of(uint64_t nslots) { return (size_t)(nslots / 2 + 1) * sizeof(Bucket); }
+
+// mq_index_reserve: the table allocated and cleared ahead of time by a thread of its own; finalize takes it when the size fits.
+// (Under the index's lock; the thread writes table, err and ms, which nobody reads before join().)
+struct TableReservation {
+    std::thread thread;
+    Buf<Bucket> table;
+    uint64_t nslots = 0;
+    int err = 0;    // hipError_t of the background allocation
+    double ms = 0;  // what hipMalloc + memset + synchronize took there
+    bool made() const { return thread.joinable() || table; }
+    void start(int device, uint64_t n) {
+        nslots = n;
+        thread = std::thread([this, device]() {
+            hipError_t e = hipSetDevice(device);
+            Buf<Bucket> t;
+            const auto t0 = std::chrono::steady_clock::now();
+            if (e == hipSuccess) e = t.try_alloc(table_bytes_of(nslots) / sizeof(Bucket));
+            ScopedStream st;
+            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.h, hipStreamNonBlocking);  // not the null stream: the build's kernels run there
+            if (e == hipSuccess) e = hipMemsetAsync(t, 0, table_bytes_of(nslots), st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (e == hipSuccess) table = std::move(t);
+            err = (int)e;
+        });
+    }
+    void join() {
+        if (thread.joinable()) thread.join();
+    }
+    // the reserved table when it has `want` slots, else nothing: an estimate that was off, or an allocation that failed, is given back
+    Buf<Bucket> take(uint64_t want) {
+        join();
+        Buf<Bucket> t = std::move(table);
+        if (nslots != want || err != 0) t.reset();
+        return t;
+    }
+    ~TableReservation() { join(); }
+};
+
 struct mq_index {
     mq_params params;
     DevParams dp;
@@ -93,15 +246,11 @@ struct mq_index {
     int geometry_rc = MQ_OK;
     std::mutex mu;  // serialises the index-level entry points (add_ref, finalize, and everything that uses the default context)
     std::map<uint32_t, std::pair<std::string, uint64_t>> refs;
-    std::vector<KmmChunk> chunks;
     uint64_t n_kmm_total = 0;
     bool finalized = false;
     uint32_t table_factor = 0;  // mq_index_set_table_factor: slots per inserted k-min-mer (0: the default, 8)
-    Buf<Bucket> table;  // nslots / 2 buckets + the extra bucket of the key 0
     uint64_t nslots = 0;
-    Buf<uint64_t> d_ref_lens;
     uint64_t n_unique = 0, n_keys = 0;
-    BuildScratch bld;
     int grid_ref = 0;                        // workgroups of seed_ref_kernel that stay resident
     // launch geometry (workgroups) and scratch sizes, fixed at the first map call
     uint32_t grid_fused = 0, grid_seed = 0, grid_map = 0;  // map_kernel; seed_reads_kernel, map_lists_kernel (split)
@@ -110,35 +259,32 @@ struct mq_index {
     bool force_general = false;     // test hook MQ_FORCE_GENERAL=1: never take the fast seeding path
     bool heavy_first = true;        // order_reads_kernel puts reads that look like short-period tandem arrays first (MQ_HEAVY_FIRST=0: A/B hook, reads in their own order)
     int chain_chunk = 64;           // test hook: MQ_CHAIN_CHUNK=4 exercises the multi-chunk chain path
-    mq_ctx *def_ctx = nullptr;      // the context behind the index-level map entry points
     double t_add_ms = 0;            // MQ_BUILD_TIMING: wall time spent in mq_index_add_ref[_device] so far
-    // mq_index_stage_*: the reference file's bytes on their way to the device piece by piece (a buffer of the file's size, an upload
-    // stream, one event per piece); a state of its own behind its own lock, so that pieces keep flowing while a record is being indexed
-    std::mutex stg_mu;
-    Buf<uint8_t> stg_buf;
-    uint64_t stg_bytes = 0;
-    hipStream_t stg_stream = nullptr;
-    std::vector<hipEvent_t> stg_events;  // ticket t = event t (tickets count from 0)
-    uint64_t stg_issued = 0;             // pieces issued so far
-    // mq_index_reserve: the table allocated and cleared ahead of time by a thread of its own (finalize adopts it when the size fits)
-    std::thread rsv_thread;
-    Buf<Bucket> rsv_table;
-    uint64_t rsv_nslots = 0;
-    int rsv_err = 0;                // hipError_t of the background allocation
     double table_alloc_ms = 0;      // what allocating + clearing the table that is in use took (hipMalloc + memset + synchronize), wherever it ran
-    double rsv_ms = 0;              // the same for the reservation (becomes table_alloc_ms when finalize adopts the reserved table)
+    // What lives on the device.  ~mq_index joins the reservation and selects the device; then the members go last to first: the reserved
+    // table, the k-min-mer chunks, the staged pieces (synchronised first), the build scratch, the table, the reference lengths, and
+    // last the default context (synchronised, then released).
+    CtxPtr def_ctx;      // the context behind the index-level map entry points
+    Buf<uint64_t> d_ref_lens;
+    Buf<Bucket> table;   // nslots / 2 buckets + the extra bucket of the key 0
+    BuildScratch bld;
+    StageState stage;
+    std::vector<KmmChunk> chunks;
+    TableReservation rsv;
+
+    ~mq_index() {
+        rsv.join();
+        hipSetDevice(device);
+    }
 };
 
 // slots of the table for n inserted k-min-mers: MQ_TABLE_FACTOR (default 8: load <= 0.125) times n, rounded up to a power of two
 static uint64_t table_slots_for(const mq_index *idx, uint64_t n_kmm) {
-    const char *lf = getenv("MQ_TABLE_FACTOR");  // (test / experiment hook: overrides the caller's choice)
-    const uint64_t factor = lf && atoi(lf) >= 2 ? (uint64_t)atoi(lf) : idx->table_factor ? (uint64_t)idx->table_factor : 8ull;  // >= 2: a full table would make a miss walk forever
+    const int lf = env_int("MQ_TABLE_FACTOR", 0);  // (test / experiment hook: overrides the caller's choice)
+    const uint64_t factor = lf >= 2 ? (uint64_t)lf : idx->table_factor ? (uint64_t)idx->table_factor : 8ull;  // >= 2: a full table would make a miss walk forever
     uint64_t nslots = 1024;
     while (nslots < factor * n_kmm) nslots <<= 1;
     return nslots;
-}
-static void rsv_join(mq_index *idx) {
-    if (idx->rsv_thread.joinable()) idx->rsv_thread.join();
 }
 
 extern "C" {
@@ -208,12 +354,28 @@ static void set_dev_bound(DevParams &dp, double density, uint32_t variant) {
     dp.variant = variant;
 }
 
+// DevParams of an index with these parameters (mq_index_new, and mq_index_set_map_params for the ones that act at mapping time)
+static DevParams dev_params_from(const mq_params &p, uint32_t variant) {
+    DevParams dp{};
+    set_dev_bound(dp, p.density, variant);
+    dp.k = p.k;
+    dp.l = p.l;
+    dp.use_hpc = p.use_hpc ? 1 : 0;
+    dp.c = p.c;
+    dp.s = p.s;
+    dp.g = p.g;
+    dp.fold = (p.flags & MQ_FLAG_FOLD_CASE) ? 1u : 0u;
+    dp.fast_kh = (p.flags & MQ_FLAG_FAST_KH) ? 1u : 0u;
+    return dp;
+}
+
 static int use_device(const mq_index *idx) {
     HIPCHK(hipSetDevice(idx->device));
     return MQ_OK;
 }
 
-static size_t table_bytes_of(uint64_t nslots) { return (size_t)(nslots / 2 + 1) * sizeof(Bucket); }
+// workgroups (of 256 threads) of a kernel that walks the table's nb1 buckets, two slots each
+static uint32_t bucket_walk_grid(uint64_t nb1) { return (uint32_t)std::min<uint64_t>((2 * nb1 + 255) / 256, 1u << 16); }
 
 static int alloc_table(mq_index *idx, uint64_t nslots) {
     if (nslots < 2) nslots = 2;  // whole buckets
@@ -246,8 +408,8 @@ static int ensure_geometry_once(mq_index *idx) {
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, 0));
         if (occ < 1) occ = 1;
         if (occ > 8) occ = 8;
-        const char *oe = getenv("MQ_OCC");  // diagnostic: cap workgroups per CU
-        if (oe && atoi(oe) >= 1 && atoi(oe) < occ) occ = atoi(oe);
+        const int oe = env_int("MQ_OCC", 0);  // diagnostic: cap workgroups per CU
+        if (oe >= 1 && oe < occ) occ = oe;
         return MQ_OK;
     };
     int occ = 0, occ_min = INT_MAX, rc;
@@ -267,8 +429,7 @@ static int ensure_geometry_once(mq_index *idx) {
     if ((rc = occ_of((const void *)map_lists_kernel<64, false>, 64 * ML_WAVES, occ))) return rc;
     idx->grid_map = (uint32_t)(occ * idx->n_cu);
     // Match runs per read held in HBM scratch; a read with more runs is reported MQ_HIT_OVERFLOW (never silently wrong)
-    const char *e = getenv("MQ_MATCH_CAP");
-    idx->cap_matches = e ? (uint32_t)strtoul(e, nullptr, 10) : 2048u;
+    idx->cap_matches = (uint32_t)env_int("MQ_MATCH_CAP", 2048);
     if (idx->cap_matches < 1) idx->cap_matches = 1;
     return MQ_OK;
 }
@@ -291,8 +452,8 @@ static uint32_t list_f16(const mq_index *idx) {
     if (!(d > 0)) d = 0;
     double f = 4.0 * d + 1.0 / 512.0;
     if (f > 1.0) f = 1.0;
-    const char *e = getenv("MQ_LIST_F16");  // test hook: force list-region overflows
-    if (e && atoi(e) >= 0) return (uint32_t)std::min(65536, atoi(e));
+    const int e = env_int("MQ_LIST_F16", -1);  // test hook: force list-region overflows
+    if (e >= 0) return (uint32_t)std::min(65536, e);
     return (uint32_t)std::ceil(f * 65536.0);
 }
 constexpr uint32_t LIST_SLACK = 64;
@@ -350,13 +511,6 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
     return MQ_OK;
 }
 
-// (the caller has selected the index's device: the context's buffers, events and stream go with it)
-static void ctx_release(mq_ctx *c) {
-    if (!c) return;
-    if (c->stream) hipStreamSynchronize(c->stream);
-    delete c;
-}
-
 static mq_ctx *ctx_create(mq_index *idx) {
     mq_ctx *c = new (std::nothrow) mq_ctx();
     if (!c) {
@@ -373,18 +527,6 @@ static mq_ctx *ctx_create(mq_index *idx) {
     return c;
 }
 
-static void free_stage(mq_index *idx) {
-    std::lock_guard<std::mutex> lk(idx->stg_mu);
-    if (idx->stg_stream) hipStreamSynchronize(idx->stg_stream);
-    for (hipEvent_t e : idx->stg_events) hipEventDestroy(e);
-    idx->stg_events.clear();
-    if (idx->stg_stream) hipStreamDestroy(idx->stg_stream);
-    idx->stg_stream = nullptr;
-    idx->stg_buf.reset();
-    idx->stg_bytes = 0;
-    idx->stg_issued = 0;
-}
-
 // ref_map lengths (src/closures.rs:49), dense by ref id
 static uint32_t max_ref_id(const mq_index *idx) { return idx->refs.empty() ? 0 : idx->refs.rbegin()->first; }
 static int upload_ref_lens(mq_index *idx) {
@@ -397,6 +539,6 @@ static int upload_ref_lens(mq_index *idx) {
 }
 
 static void free_build_scratch(mq_index *idx) {
-    free_stage(idx);
+    idx->stage.reset();
     idx->bld = BuildScratch();
 }

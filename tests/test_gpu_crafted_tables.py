@@ -287,6 +287,49 @@ def test_files_that_must_be_refused(mq, oracle, simlib, tmp_path):
     assert before - after < (64 << 20), (before, after)
 
 
+def test_load_refused_at_every_section(mq, tmp_path):
+    """A valid small file (two references, 40 keys) cut inside the header, inside the reference table, in the middle of a reference
+    name, inside the slots and one byte short of its end, and the whole file with one byte behind it: each load is refused with the
+    text of its section, and a good file still loads afterwards with the header's numbers."""
+    rng = np.random.default_rng(12)
+    e = np.zeros(40, dtype=mqx.entry_dtype)
+    e["key"] = np.unique(rng.integers(1, 2**64, size=64, dtype=np.uint64))[:40]
+    e["id"] = np.arange(40) % 2
+    e["start"] = 10 * np.arange(40)
+    e["end"] = e["start"] + 31
+    e["offset"] = np.arange(40)
+    e["rc"] = np.arange(40) & 1
+    e["count"] = 1
+    t = mqx.Table(mqx.params(), 128, [(0, "alpha", 5000), (1, "beta", 3000)], e, "two refs, 40 keys")
+    good = str(tmp_path / "good.mqx")
+    hdr = t.to_file(good)
+    blob = open(good, "rb").read()
+    head = 8 + 40 + 48
+    refs_end = head + (16 + len("alpha")) + (16 + len("beta"))
+    assert len(blob) == refs_end + 40 * mqx.SLOT_BYTES
+    not_an_index = "not a mapquik HIP index (or another layout version): "
+    truncated = "truncated or unreadable index file: "
+    cases = [("header", blob[:50], not_an_index),
+             ("reference table", blob[:head + 16 + len("alpha") + 8], truncated),
+             ("reference name", blob[:head + 16 + 2], truncated),
+             ("slots", blob[:refs_end + 10 * mqx.SLOT_BYTES + 7], truncated),
+             ("one byte short", blob[:-1], truncated),
+             ("one byte more", blob + b"\0", "corrupt index file (bytes after the last slot): ")]
+    for what, content, text in cases:
+        p = str(tmp_path / "cut.mqx")
+        with open(p, "wb") as f:
+            f.write(content)
+        with pytest.raises(mq.MapquikError) as ei:
+            mq.Index.load(p)
+        print("%s: %s" % (what, ei.value))
+        assert str(ei.value) == "mq_index_load: " + text + p, what
+    ix = mq.Index.load(good)
+    st = ix.stats()
+    assert {k: st[k] for k in mqx.HEADER_NAMES} == hdr
+    assert [ix.ref_info(r) for r in (0, 1)] == [("alpha", 5000), ("beta", 3000)]
+    ix.close()
+
+
 def test_probe_stats_walks(mq, oracle, simlib, tmp_path, capsys):
     """Slots visited beyond the home slot by the reads' lookups (the instrumented launch).  Lower bounds from the table's
     content and the probe order alone: on `one_empty` every miss steps at least once except those homed at the one empty

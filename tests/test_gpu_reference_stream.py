@@ -184,6 +184,39 @@ def test_stage_api_pieces_in_any_order(mq, oracle, simlib):
     pin.close()
 
 
+def test_an_index_freed_mid_build_leaves_the_device_usable(mq, simlib):
+    """An index closed in the middle of its build -- pieces from pageable memory still on their way (nobody waited for their tickets), a
+    table reservation running or done, one record indexed from the staging buffer, no finalize -- gives everything back in an order the
+    device survives: an index built afterwards maps byte for byte like one built before the first was opened."""
+    g, off, names = simlib.make_genome([700000, 300000, 50], seed=9, repeat_frac=0.1)
+    txt = b"".join(b">" + names[r].encode() + b"\n" + g[int(off[r]):int(off[r + 1])].tobytes() + b"\n" for r in range(3))
+    buf = np.frombuffer(txt, dtype=np.uint8)
+    reads = simlib.make_reads(g, off, 200, seed=3)
+    P = mq.Params()
+
+    def build():
+        ix = mq.Index(P)
+        counts = [ix.add_ref(r, names[r], g[int(off[r]):int(off[r + 1])]) for r in range(3)]
+        return ix, counts, ix.finalize()
+
+    a, counts, unique = build()
+    want = a.map_batch(reads["bases"], reads["offsets"])
+    assert int((want["status"] == 1).sum()) >= 100
+    b = mq.Index(P)
+    b.stage_begin(buf.size)
+    cuts = [0, 300001, 700123, buf.size]
+    pieces = [buf[cuts[i]:cuts[i + 1]].copy() for i in range(3)]
+    assert [b.stage_piece(cuts[i], pieces[i]) for i in range(3)] == [0, 1, 2]
+    b.reserve_table(sum(counts))
+    assert b.add_ref_staged(0, names[0], len(names[0]) + 2, int(off[1] - off[0])) == counts[0]
+    b.close()
+    c, counts_c, unique_c = build()
+    assert (counts_c, unique_c) == (counts, unique)
+    assert np.array_equal(c.map_batch(reads["bases"], reads["offsets"]).view(np.uint8), want.view(np.uint8))
+    a.close()
+    c.close()
+
+
 def test_on_disk_index_from_the_command_line(world, mq):
     """--save-index writes the finalized index, --index maps against it without the reference (both drivers): the PAF of the
     FASTA-indexed run, the index phase's last log line kept; other seeding parameters than the file's are refused, other chaining
