@@ -234,14 +234,17 @@ int mq_ctx_submit_spans(mq_ctx *ctx, const uint8_t *buf, uint64_t buf_bytes, con
                         mq_hit *out);
 /* FASTA records found on the device (the batch form of closures.rs:100-123 for a reader that does not parse): buf[begin, bytes) is a
  * piece of an uncompressed FASTA file that holds WHOLE records, begin at a record's '>'.  The bytes go to the device as they are,
- * kernels find the line ends, and read i is the second line of record i (a '\r' in front of the '\n' is cut; a last line without
- * '\n' ends at `bytes`).  mq_ctx_submit_fasta queues copy and scan and returns; mq_ctx_wait_fasta launches the map kernels once the
- * record count is known and returns pointers into the context's page-locked memory, valid until its next submit:
+ * kernels find the line ends, and read i is the second line of record i (ONE '\r' at the end of the line is cut; a last line without
+ * '\n' ends at `bytes`, and a '\r' that is the piece's last byte is cut from it like one in front of a '\n').  mq_ctx_submit_fasta
+ * queues copy and scan and returns; mq_ctx_wait_fasta launches the map kernels once the record count is known and returns pointers
+ * into the context's page-locked memory, valid until its next submit:
  *   line_ends[0 .. n_lines)  positions of the line ends in buf, ascending; record i: header = buf[(i ? line_ends[2i-1]+1 : begin), line_ends[2i]),
  *                            sequence = buf[line_ends[2i]+1, line_ends[2i+1])   (n_lines = 2 * n_reads)
  *   hits[0 .. n_reads)       as mq_ctx_wait fills them (overflow reads redone)
- * flags & MQ_FASTA_IRREGULAR: the piece is not "header line, sequence line" all through (sequences over several lines, blank lines,
- * more line ends than bytes / 16): nothing was mapped, n_reads = 0 -- parse it on the host and use mq_ctx_submit_spans.  buf must stay
+ * flags & MQ_FASTA_IRREGULAR: the piece is not "header line, sequence line" all through (an odd number of lines, a header line that is
+ * empty or does not start with '>', a sequence line that starts with '>': sequences over several lines, blank lines, a header without
+ * its sequence line; or more line ends than the list holds, min(bytes / 16 + 4096, 2^28)): nothing was mapped, n_reads = n_lines = 0 --
+ * parse it on the host and use mq_ctx_submit_spans.  An empty piece (begin == bytes) is regular: 0 records.  buf must stay
  * valid until mq_ctx_wait_fasta has returned; page-locked memory (mq_host_alloc) gives the full PCIe rate. */
 #define MQ_FASTA_IRREGULAR 1u
 int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_t bytes);
@@ -249,7 +252,8 @@ int mq_ctx_submit_fasta(mq_ctx *ctx, const uint8_t *buf, uint64_t begin, uint64_
  * run is an uncompressed FASTQ, experiments/table1.sh:50).  MQ_FASTX_FASTQ: buf[begin, bytes) holds whole four-line records, begin at a
  * record's '@'; read i is the second line of record i, and mq_ctx_wait_fasta reports n_lines = 4 * n_reads line ends (record i: header
  * = buf[(i ? line_ends[4i-1]+1 : begin), line_ends[4i]), sequence = buf[line_ends[4i]+1, line_ends[4i+1])).  The device checks every
- * record the way the reference's reader would have to: '@' opens it, '+' opens its third line, one quality per base; anything else
+ * record the way the reference's reader would have to: '@' opens it, '+' opens its third line, one quality per base (ONE '\r' at the
+ * end cut from the sequence and from the quality line; both may be empty); anything else
  * (sequences or qualities over several lines, blank lines, a truncated record) comes back MQ_FASTA_IRREGULAR for the host's parser.
  * The quality bytes cross the link but no host thread reads them. */
 #define MQ_FASTX_FASTA 0u

@@ -237,16 +237,16 @@ inline void parse_chunk(Chunk &c, bool fastq) {
             if (b[p] != '>') throw FeederError("malformed FASTA record");
             const uint64_t e1 = line_end(p);
             add_id(p, e1);
-            uint64_t s = e1 + 1 < end ? e1 + 1 : end;
-            uint64_t e2 = line_end(s);
-            uint64_t dst = e2;
-            if (dst > s && b[dst - 1] == '\r') --dst;
-            uint64_t q = e2 < end ? e2 + 1 : end;
-            while (q < end && b[q] != '>') {  // further sequence lines: compact them onto the first one
+            const uint64_t s = e1 + 1 < end ? e1 + 1 : end;
+            uint64_t dst = s, q = s;
+            // sequence lines, compacted onto the first one.  A '>' at a line start opens the next record wherever it stands: directly
+            // behind a header line too (a record without a sequence line is an empty read and the next record keeps its own header --
+            // what next_record_start says when a chunk border falls between the two, and what the device's scanners call irregular)
+            while (q < end && b[q] != '>') {
                 const uint64_t e = line_end(q);
                 uint64_t n = e - q;
                 if (n && b[q + n - 1] == '\r') --n;
-                if (n) memmove(b + dst, b + q, n);
+                if (n && dst != q) memmove(b + dst, b + q, n);  // (the first line stays where it is: a one-line record writes nothing)
                 dst += n;
                 q = e < end ? e + 1 : end;
             }

@@ -105,7 +105,8 @@ def test_more_line_ends_than_the_scan_holds(mq, world, tmp_path):
     """A well-formed FASTA of very short records (primers, barcodes, k-mers: under ~32 bytes each) has more line ends than the scan's
     list holds (bytes / 16 + 4096): the piece must come back IRREGULAR with NO record reported -- never a record count that indexes
     past the list -- and the driver then parses it on the host: the same PAF (no line: nothing that short maps) and exit code 0.
-    Junk input full of newlines likewise."""
+    Junk input full of newlines likewise.  The list exactly full, and one entry over, with and without a last '\\n':
+    tests/test_gpu_fastx_records.py::test_line_end_list_exactly_full (tests/fastx_records_cases.py capacity_cases)."""
     ix = world["ix"]
     ctx = ix.context()
     for piece in (b">a\nAC\n" * 40000, b">a\nAC\n" * 1500000, b"\n" * 300000, b">x\n" + b"\n" * 200001):
