@@ -15,6 +15,13 @@ extern "C" {
  * the general streaming path.  Both produce identical results.  Synchronises on the launch. */
 int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general);
 
+/* Which instantiation of the fused kernel pair the last map launch ran -- of the index's default context / of a context: the id of the
+ * parameter set it was compiled for (1: k 5, l 31, homopolymer compression, SipHash; 2: the same with k 7; 3: the first with case folding),
+ * or 0 for the pair that reads its parameters at run time (every other parameter set, the seeding variants, MQ_NO_SPEC=1).
+ * (Prefix mqdiag_: the mq_ names of this header are a closed list that the boundary tests pin; later diagnostics take this prefix.) */
+int mqdiag_last_map_spec(mq_index *idx, uint32_t *spec_id);
+int mqdiag_ctx_last_map_spec(mq_ctx *ctx, uint32_t *spec_id);
+
 /* The launch order of the last map launch: how many reads looked like short-period tandem arrays to the ordering pass (n_flagged) and
  * how many of them were taken up first (n_first <= n_flagged: the front of the order holds 32,768). */
 int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first);

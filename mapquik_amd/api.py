@@ -169,6 +169,9 @@ def load_library(path=None):
     L.mq_host_free.argtypes = [vp]
     L.mq_last_map_path_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.mq_last_map_order.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "mqdiag_last_map_spec"):
+        L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
     if path is None:
         _lib = L
     return L
@@ -433,6 +436,13 @@ class Index:
             raise _err(self._L, "mq_last_map_path_counts")
         return a.value, b.value
 
+    def last_map_spec(self):
+        """Which compiled-for-its-parameters kernel pair the last launch ran (include/mapquik_hip_diag.h); 0: the run-time pair."""
+        a = C.c_uint32()
+        if self._L.mqdiag_last_map_spec(self._h, C.byref(a)) != 0:
+            raise _err(self._L, "mqdiag_last_map_spec")
+        return a.value
+
     def table_alloc_ms(self):
         """What allocating + clearing this index's table took (on mq_index_reserve's thread or inside finalize), in ms."""
         ms = C.c_float()
@@ -618,6 +628,12 @@ class Context:
         if self._L.mq_ctx_last_map_ms(self._h, C.byref(ms)) != 0:
             raise _err(self._L, "mq_ctx_last_map_ms")
         return ms.value
+
+    def last_map_spec(self):
+        a = C.c_uint32()
+        if self._L.mqdiag_ctx_last_map_spec(self._h, C.byref(a)) != 0:
+            raise _err(self._L, "mqdiag_ctx_last_map_spec")
+        return a.value
 
 
 def ref_extract(ref_idx, inp_seq_raw, params, mers_index, name=None):

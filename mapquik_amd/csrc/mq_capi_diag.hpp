@@ -95,6 +95,26 @@ int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general
     });
 }
 
+// Which MAP_SPECS pair the last fused launch sequence ran: of the index's default context / of a context (0: SpecNone)
+int mqdiag_last_map_spec(mq_index *idx, uint32_t *spec_id) {
+    return guarded([&]() -> int {
+        if (!idx || !spec_id) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        mq_ctx *c = idx->def_ctx.get();
+        if (!c->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        *spec_id = c->last_spec;
+        return MQ_OK;
+    });
+}
+int mqdiag_ctx_last_map_spec(mq_ctx *ctx, uint32_t *spec_id) {
+    return guarded([&]() -> int {
+        if (!ctx || !spec_id) return set_err(MQ_EINVAL, "bad arguments");
+        if (!ctx->ev_valid) return set_err(MQ_ESTATE, "no map launch recorded");
+        *spec_id = ctx->last_spec;
+        return MQ_OK;
+    });
+}
+
 int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first) {
     return guarded([&]() -> int {
         if (!idx || !n_flagged || !n_first) return set_err(MQ_EINVAL, "bad arguments");

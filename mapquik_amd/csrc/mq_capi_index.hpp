@@ -38,8 +38,9 @@ mq_index *mq_index_new(const mq_params *params, int device) {
         IndexPtr idx(new mq_index());
         idx->params = *params;
         idx->device = device;
-        idx->dp = dev_params_from(*params, (params->flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT);
         if (env_int("MQ_CHAIN_CHUNK", 64) == 4) idx->chain_chunk = 4;
+        idx->no_spec = env_int("MQ_NO_SPEC", 0) != 0;
+        set_dev_params(idx.get(), dev_params_from(*params, (params->flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT));
         idx->force_general = env_int("MQ_FORCE_GENERAL", 0) != 0;
         idx->heavy_first = env_int("MQ_HEAVY_FIRST", 1) != 0;
         const char *pl = getenv("MQ_PIPELINE");

@@ -282,7 +282,7 @@ int mq_index_set_map_params(mq_index *idx, uint32_t c, uint32_t s, uint32_t g, i
         idx->params.s = s;
         idx->params.g = g;
         idx->params.flags = (idx->params.flags & ~MQ_FLAG_FOLD_CASE) | (fold_case ? MQ_FLAG_FOLD_CASE : 0u);
-        idx->dp = dev_params_from(idx->params, idx->dp.variant);
+        set_dev_params(idx, dev_params_from(idx->params, idx->dp.variant));
         return MQ_OK;
     });
 }

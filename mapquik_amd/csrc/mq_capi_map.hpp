@@ -58,8 +58,9 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
         uint32_t grid = fused_grid(idx, n);
         if (o.grid_override) grid = std::min(grid, o.grid_override);
         const dim3 blk(64 * MAP_WAVES);
-        // (a seeding variant other than the frozen reading takes the instantiation built with the variants)
-        const MapPair &kp = MAP_KERNELS[idx->dp.variant != 0][o.instrumented][idx->chain_chunk == 4];
+        // (a seeding variant other than the frozen reading takes the instantiation built with the variants; the frozen reading with the
+        // parameters of a MAP_SPECS entry takes the pair compiled for them)
+        const MapPair &kp = map_pair_of(idx, o.instrumented, &c->last_spec);
         hipLaunchKernelGGL(kp.map, dim3(grid), blk, 0, st, A);
         HIPCHK(hipGetLastError());
         // the reads the fast seeder declined (queue length on the device: map_kernel's grid, its waves leave at once when there are none)

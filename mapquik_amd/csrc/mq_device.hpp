@@ -61,6 +61,42 @@ template <bool VAR> __device__ __forceinline__ bool var_keep_none(const DevParam
 // a hash as it goes into a minimizer list: the 32-bit variant's value zero-extended
 template <bool VAR> __device__ __forceinline__ uint64_t list_hash(const DevParams &P, uint64_t h) { return var_h32<VAR>(P) ? (h & 0xFFFFFFFFull) : h; }
 
+// Spec: the parameters a map kernel instantiation is COMPILED for.  k, l, use_hpc, fold and fast_kh reach the hot code of the fused pair
+// through the spec_* accessors below and nowhere else: with SpecNone they are DevParams' wave-uniform run-time values (any parameters,
+// every other kernel), with a SpecFixed they are constants -- immediates instead of SGPR operands, one tuple hash and one window hash
+// instead of a dispatch over all of them, and no kh_fast code (a SpecFixed is built for SipHash only).  The host launches a SpecFixed
+// pair only for an index whose DevParams equal it field by field (mq_host_state.hpp, MAP_SPECS): same source path, same results.
+struct SpecNone {
+    static constexpr bool FIXED = false;
+};
+template <uint32_t K_, uint32_t L_, bool HPC_, bool FOLD_>
+struct SpecFixed {
+    static constexpr bool FIXED = true;
+    static constexpr uint32_t K = K_, L = L_;
+    static constexpr bool HPC = HPC_, FOLD = FOLD_, FAST_KH = false;
+    static_assert(K_ >= 1 && K_ <= MAX_K && L_ >= 1 && L_ <= MAX_L, "k and l within MAX_K, MAX_L");
+};
+template <class Spec> __device__ __forceinline__ uint32_t spec_k(const DevParams &P) {
+    if constexpr (Spec::FIXED) return Spec::K;
+    else return P.k;
+}
+template <class Spec> __device__ __forceinline__ uint32_t spec_l(const DevParams &P) {
+    if constexpr (Spec::FIXED) return Spec::L;
+    else return P.l;
+}
+template <class Spec> __device__ __forceinline__ bool spec_hpc(const DevParams &P) {
+    if constexpr (Spec::FIXED) return Spec::HPC;
+    else return P.use_hpc != 0;
+}
+template <class Spec> __device__ __forceinline__ bool spec_fold(const DevParams &P) {
+    if constexpr (Spec::FIXED) return Spec::FOLD;
+    else return P.fold != 0;
+}
+template <class Spec> __device__ __forceinline__ bool spec_fast_kh(const DevParams &P) {
+    if constexpr (Spec::FIXED) return Spec::FAST_KH;
+    else return P.fast_kh != 0;
+}
+
 // Index table: 64-byte buckets of two 32-byte slots, both keys first so that ONE 16-byte load decides most lookups.
 //   slot s = bucket s >> 1, way s & 1;  key == 0 <=> empty (a real key 0 lives in way 0 of one extra bucket behind the table).
 // Probe sequence of a key (insert and lookup walk the same one; src/index.rs:11-39's identity hasher gives the home slot):
@@ -871,20 +907,27 @@ struct MapSink {
     }
 
     // k-min-mer `base + lane` of a minimizer list: canonical orientation, tuple hash, query coordinates
+    // (a SpecFixed holds its own k's tuple hash, SipHash only; SpecNone holds every supported k's and the opt-in kh_fast)
+    template <class Spec = SpecNone>
     __device__ __forceinline__ void batch_keys(const unsigned long long *mzh, const uint32_t *mzp, uint32_t base, bool act,
                                                uint64_t &key, bool &rev, uint32_t &q_start, uint32_t &q_end) const {
         const uint32_t i0 = base + lane_id();
+        const uint32_t k = spec_k<Spec>(P), l = spec_l<Spec>(P);
         key = 0;
         rev = false;
         q_start = q_end = 0;
         if (act) {
             auto get = [&](uint32_t i) { return (uint64_t)mzh[i0 + i]; };
-            // 5: the reference's default k (src/main.rs: -k 5); 7: experiments/table1.sh:50; 8: example/run_ecoli.sh:26
-            const bool re = rev_eq, fk = P.fast_kh != 0;
-            key = P.k == 5u ? kminmer_hash_fixed<5>(get, rev, re, fk) : P.k == 7u ? kminmer_hash_fixed<7>(get, rev, re, fk)
-                  : P.k == 8u ? kminmer_hash_fixed<8>(get, rev, re, fk) : kminmer_hash(P.k, get, rev, re, fk);
+            const bool re = rev_eq, fk = spec_fast_kh<Spec>(P);
+            if constexpr (Spec::FIXED) {
+                key = kminmer_hash_fixed<Spec::K>(get, rev, re, fk);
+            } else {
+                // 5: the reference's default k (src/main.rs: -k 5); 7: experiments/table1.sh:50; 8: example/run_ecoli.sh:26
+                key = k == 5u ? kminmer_hash_fixed<5>(get, rev, re, fk) : k == 7u ? kminmer_hash_fixed<7>(get, rev, re, fk)
+                      : k == 8u ? kminmer_hash_fixed<8>(get, rev, re, fk) : kminmer_hash(k, get, rev, re, fk);
+            }
             q_start = mzp[i0];
-            q_end = mzp[i0 + P.k - 1] + P.l - 1u;
+            q_end = mzp[i0 + k - 1] + l - 1u;
         }
     }
 
@@ -1085,12 +1128,13 @@ struct MapSink {
     // hashes_done(): called once the minimizers' hashes (mzh) have all been read -- the positions (mzp) are still needed
     // mzq (variant 16 only, else nullptr): the minimizers' second positions (the window's last compressed base), valid once
     // hashes_done() has returned (the caller stages them where the hashes were)
-    template <int NB, class F>
+    template <int NB, class Spec = SpecNone, class F>
     __device__ __forceinline__ void consume_list(const unsigned long long *mzh, const uint32_t *mzp, uint32_t have, const F &hashes_done,
                                                  const uint32_t *mzq = nullptr) {
-        if (have < P.k) return;
+        const uint32_t k = spec_k<Spec>(P), l = spec_l<Spec>(P);
+        if (have < k) return;
         const uint32_t lane = lane_id();
-        const uint32_t K = have - P.k + 1u;
+        const uint32_t K = have - k + 1u;
         uint64_t key[NB];
         uint4 kk[NB];
         uint32_t revbits = 0, actbits = 0;
@@ -1102,7 +1146,7 @@ struct MapSink {
                 const bool act = (uint32_t)c * 64u + lane < K;
                 bool rev;
                 uint32_t qs, qe;
-                batch_keys(mzh, mzp, (uint32_t)c * 64u, act, key[c], rev, qs, qe);
+                batch_keys<Spec>(mzh, mzp, (uint32_t)c * 64u, act, key[c], rev, qs, qe);
                 revbits |= (rev ? 1u : 0u) << c;
                 if (act) {
                     actbits |= 1u << c;
@@ -1129,7 +1173,7 @@ struct MapSink {
                 uint32_t qs = 0, qe = 0;
                 if (act) {
                     qs = mzp[i0];
-                    qe = mzq ? mzq[i0 + P.k - 1] : mzp[i0 + P.k - 1] + P.l - 1u;
+                    qe = mzq ? mzq[i0 + k - 1] : mzp[i0 + k - 1] + l - 1u;
                 }
                 Entry e;
                 e.start = kk[c].x;

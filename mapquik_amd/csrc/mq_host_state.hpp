@@ -35,6 +35,7 @@ struct mq_ctx {
     ScopedStream stream;            // the context's own stream (host-buffer entry points)
     ScopedEvent ev0, ev1;
     bool ev_valid = false;
+    uint32_t last_spec = 0;         // MAP_SPECS id of the pair the last fused launch sequence ran (0: SpecNone)
     Buf<uint32_t> d_counter;        // 64 words: SplitArgs::counters; [8..11] two 64-bit probe statistics of an instrumented launch
     Buf<MatchRec> scratch;          // per mapping wave: cap_matches records
     size_t scratch_waves = 0;       // waves it has windows for
@@ -259,6 +260,8 @@ struct mq_index {
     bool force_general = false;     // test hook MQ_FORCE_GENERAL=1: never take the fast seeding path
     bool heavy_first = true;        // order_reads_kernel puts reads that look like short-period tandem arrays first (MQ_HEAVY_FIRST=0: A/B hook, reads in their own order)
     int chain_chunk = 64;           // test hook: MQ_CHAIN_CHUNK=4 exercises the multi-chunk chain path
+    bool no_spec = false;           // A/B and test hook MQ_NO_SPEC=1: product launches take the SpecNone pair whatever the parameters
+    uint32_t map_spec = 0;          // MAP_SPECS id of the pair a product launch takes (0: SpecNone); follows dp (set_dev_params)
     double t_add_ms = 0;            // MQ_BUILD_TIMING: wall time spent in mq_index_add_ref[_device] so far
     double table_alloc_ms = 0;      // what allocating + clearing the table that is in use took (hipMalloc + memset + synchronize), wherever it ran
     // What lives on the device.  ~mq_index joins the reservation and selects the device; then the members go last to first: the reserved
@@ -390,17 +393,59 @@ static int alloc_table(mq_index *idx, uint64_t nslots) {
 }
 
 // Every instantiation of the fused launch sequence's two kernels, by [seeding variant != 0][instrumented][chain chunk 4]: launch_map picks
-// its pair here and the launch geometry is the minimum over the same entries.  (The instrumented launch is built for chunk 64 only.)
+// its pair here or from MAP_SPECS below (map_pair_of), and the launch geometry is the minimum over the pairs the index can launch.  (The
+// instrumented launch is built for chunk 64 only.)
 using MapFn = void (*)(SplitArgs);
 struct MapPair {
     MapFn map, declined;
 };
-template <int CH, bool TIMING, bool VAR>
+template <int CH, bool TIMING, bool VAR, class Spec = SpecNone>
 constexpr MapPair map_pair() {
-    return {map_kernel<CH, TIMING, VAR>, map_declined_kernel<CH, TIMING, VAR>};
+    return {map_kernel<CH, TIMING, VAR, Spec>, map_declined_kernel<CH, TIMING, VAR, Spec>};
 }
 static const MapPair MAP_KERNELS[2][2][2] = {{{map_pair<64, false, false>(), map_pair<4, false, false>()}, {map_pair<64, true, false>(), map_pair<64, true, false>()}},
                                              {{map_pair<64, false, true>(), map_pair<4, false, true>()}, {map_pair<64, true, true>(), map_pair<64, true, true>()}}};
+
+// The spec dimension of the table: the product pair (chunk 64, not instrumented, frozen reading) compiled for the parameters nearly
+// every run uses -- the reference's defaults -k 5 -l 31 with homopolymer compression and SipHash, the -k 7 of its real-data runs, and the
+// defaults with case folding (the native driver folds every file-fed run).  Spec id 0 = SpecNone = MAP_KERNELS: every other parameter
+// set, the seeding variants, the instrumented launch and chunk 4.  A spec is taken on an EXACT match of all five fields it fixes.
+struct MapSpec {
+    uint32_t k, l, use_hpc, fold, fast_kh;
+    MapPair pair;
+};
+template <class S>
+constexpr MapSpec map_spec() {
+    return {S::K, S::L, S::HPC ? 1u : 0u, S::FOLD ? 1u : 0u, S::FAST_KH ? 1u : 0u, map_pair<64, false, false, S>()};
+}
+static const MapSpec MAP_SPECS[] = {map_spec<SpecFixed<5, 31, true, false>>(), map_spec<SpecFixed<7, 31, true, false>>(),
+                                    map_spec<SpecFixed<5, 31, true, true>>()};
+constexpr uint32_t N_MAP_SPECS = sizeof(MAP_SPECS) / sizeof(MAP_SPECS[0]);
+
+// id (1-based, 0: none) of the spec whose fields equal dp's; any_fold: the fold field is not compared (mq_index_set_map_params may change
+// it between launches: the launch geometry covers both)
+static bool spec_matches(const MapSpec &s, const DevParams &dp, bool any_fold) {
+    return s.k == dp.k && s.l == dp.l && s.use_hpc == dp.use_hpc && s.fast_kh == dp.fast_kh && (any_fold || s.fold == dp.fold);
+}
+// The spec a product launch of this index takes (0: SpecNone).  MQ_NO_SPEC=1 (A/B and test hook, read at mq_index_new) forces SpecNone.
+static bool specs_allowed(const mq_index *idx) { return !idx->no_spec && idx->dp.variant == 0 && idx->chain_chunk != 4; }
+static uint32_t map_spec_of(const mq_index *idx) {
+    if (!specs_allowed(idx)) return 0;
+    for (uint32_t i = 0; i < N_MAP_SPECS; ++i)
+        if (spec_matches(MAP_SPECS[i], idx->dp, false)) return i + 1;
+    return 0;
+}
+// the pair of a fused launch sequence, and the spec id it carries
+static const MapPair &map_pair_of(const mq_index *idx, bool instrumented, uint32_t *spec_id = nullptr) {
+    const uint32_t sid = instrumented ? 0u : idx->map_spec;
+    if (spec_id) *spec_id = sid;
+    return sid ? MAP_SPECS[sid - 1].pair : MAP_KERNELS[idx->dp.variant != 0][instrumented][idx->chain_chunk == 4];
+}
+// an index's DevParams change in one place: the pair its launches take is chosen here, once per parameter set
+static void set_dev_params(mq_index *idx, const DevParams &dp) {
+    idx->dp = dp;
+    idx->map_spec = map_spec_of(idx);
+}
 
 // launch geometry: persistent waves, as many workgroups as stay resident
 static int ensure_geometry_once(mq_index *idx) {
@@ -415,14 +460,18 @@ static int ensure_geometry_once(mq_index *idx) {
     int occ = 0, occ_min = INT_MAX, rc;
     // the grid of a launch sequence = the workgroups that are RESIDENT together, for every instantiation launched on it: wave w's first two
     // work items are its own (items w and n_waves + w, among them the heavy reads that go first), so a workgroup that has to wait for a
-    // place would hold them back; the variants' instantiation and map_declined_kernel (more scratch) may fit fewer than the product's map_kernel
-    for (const auto &by_variant : MAP_KERNELS)
-        for (const auto &by_instrumented : by_variant)
-            for (const MapPair &kp : by_instrumented)
-                for (const MapFn fn : {kp.map, kp.declined}) {
-                    if ((rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return rc;
-                    occ_min = std::min(occ_min, occ);
-                }
+    // place would hold them back; map_declined_kernel (more scratch) may fit fewer than map_kernel.  The instantiations launched on THIS
+    // index: its SpecNone pair and the instrumented one (its seeding variant and chain chunk are fixed at mq_index_new), and the spec pairs
+    // its parameters can select (case folding may change between launches, so a spec and its fold-case twin both count)
+    std::vector<MapPair> pairs = {map_pair_of(idx, true), MAP_KERNELS[idx->dp.variant != 0][0][idx->chain_chunk == 4]};
+    if (specs_allowed(idx))
+        for (const MapSpec &s : MAP_SPECS)
+            if (spec_matches(s, idx->dp, true)) pairs.push_back(s.pair);
+    for (const MapPair &kp : pairs)
+        for (const MapFn fn : {kp.map, kp.declined}) {
+            if ((rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return rc;
+            occ_min = std::min(occ_min, occ);
+        }
     idx->grid_fused = (uint32_t)(occ_min * idx->n_cu);
     if ((rc = occ_of((const void *)seed_reads_kernel<0>, 64 * SEED_WAVES, occ))) return rc;
     idx->grid_seed = (uint32_t)(occ * idx->n_cu);

@@ -127,14 +127,14 @@ __device__ __forceinline__ bool pool_take(const SplitArgs &A, uint32_t cnt, uint
 }
 
 // seed phase, fast seeder: list length, SD_NOT_FAST (declined: non-ACGT byte, ...) or LIST_OVERFLOW; base moves with the list
-template <int STOP = 0, bool VAR = true>
+template <int STOP = 0, bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ uint32_t seed_read_fast(const SplitArgs &A, const SeedTables &T, SeedLds &S, const uint8_t *seq,
                                                    uint32_t len, uint64_t &base, uint32_t cap, uint32_t &n_moved, APre &pre, bool pre_valid) {
-    uint32_t cnt = seed_sequence_fast<STOP, false, VAR>(seq, len, A.P, T, S, A.mz_hash + base, A.mz_pos + base, cap, pre, pre_valid, SeedView(),
+    uint32_t cnt = seed_sequence_fast<STOP, false, VAR, Spec>(seq, len, A.P, T, S, A.mz_hash + base, A.mz_pos + base, cap, pre, pre_valid, SeedView(),
                                                         A.mz_last ? A.mz_last + base : nullptr);
     if (cnt != SD_NOT_FAST && cnt > cap) {  // denser than its region: once more, into an exact-size pool region
         if (pool_take(A, cnt, base)) {
-            seed_sequence_fast<0, false, VAR>(seq, len, A.P, T, S, A.mz_hash + base, A.mz_pos + base, cnt, pre, false, SeedView(), A.mz_last ? A.mz_last + base : nullptr);
+            seed_sequence_fast<0, false, VAR, Spec>(seq, len, A.P, T, S, A.mz_hash + base, A.mz_pos + base, cnt, pre, false, SeedView(), A.mz_last ? A.mz_last + base : nullptr);
             n_moved++;
         } else {
             cnt = LIST_OVERFLOW;
@@ -258,8 +258,10 @@ __device__ __forceinline__ bool next_clean_stretch(const uint8_t *__restrict__ s
     return false;
 }
 // a0 in [lo, d] such that [a0, d) holds at least `need` run heads (or a0 = lo): where the general seeder has to start for the windows that reach d
+template <class Spec = SpecNone>
 __device__ __forceinline__ uint64_t heads_back(const uint8_t *__restrict__ seq, uint64_t lo, uint64_t d, uint32_t need, const DevParams &P) {
     const uint32_t lane = lane_id();
+    const bool fold = spec_fold<Spec>(P), use_hpc = spec_hpc<Spec>(P);
     uint64_t a0 = d;
     uint32_t heads = 0;
     while (a0 > lo && heads < need) {
@@ -269,16 +271,16 @@ __device__ __forceinline__ uint64_t heads_back(const uint8_t *__restrict__ seq, 
         if (lane < step) {
             const uint64_t i = a0 + lane;
             uint32_t b = seq[i], pb = i > 0 ? (uint32_t)seq[i - 1] : 0x100u;
-            if (P.fold && b - 'a' < 26u) b -= 32u;
-            if (P.fold && pb - 'a' < 26u) pb -= 32u;
-            head = !P.use_hpc || b != pb;
+            if (fold && b - 'a' < 26u) b -= 32u;
+            if (fold && pb - 'a' < 26u) pb -= 32u;
+            head = !use_hpc || b != pb;
         }
         heads += (uint32_t)__popcll(__ballot(head));
     }
     return a0;
 }
 // tacc (instrumented launch only, else nullptr): cycles spent [0] finding stretches, [1] in the fast seeder, [2] in the general seeder
-template <bool VAR = true>
+template <bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const SeedTables &T, SeedLds &SF, WaveLds &SG, const uint8_t *seq, uint64_t len,
                                                      uint64_t &base, uint32_t cap, uint32_t &n_moved, unsigned long long *tacc = nullptr) {
     const DevParams &P = A.P;
@@ -308,7 +310,7 @@ __device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const S
         }
         uint64_t seg_a = 0, seg_min_last = 0;  // the open general segment: windows that start at or behind seg_a (and end at or behind seg_min_last)
         uint64_t pos = 0, s = 0, d = 0;
-        while (pos < len && next_clean_stretch(seq, len, pos, P.fold != 0, s, d)) {  // [s, d): whole 64-byte blocks of A C G T, at least HYB_MIN_CLEAN bytes
+        while (pos < len && next_clean_stretch(seq, len, pos, spec_fold<Spec>(P), s, d)) {  // [s, d): whole 64-byte blocks of A C G T, at least HYB_MIN_CLEAN bytes
             pos = d;
             if (d - s > 0xFFFFFF00ull) continue;
             if (s > seg_a) general(seg_a, s, seg_min_last);  // the windows that start in front of the stretch
@@ -317,7 +319,7 @@ __device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const S
             V.first_prev = 4u;
             if (s > 0) {  // the byte in front of the stretch as the seeder's 2-bit code (the stretch may begin inside a run: its first base is then no run head)
                 uint32_t b = seq[s - 1];
-                if (P.fold && b - 'a' < 26u) b -= 32u;
+                if (spec_fold<Spec>(P) && b - 'a' < 26u) b -= 32u;
                 V.first_prev = b == 'A' ? 0u : b == 'C' ? 1u : b == 'T' ? 2u : b == 'G' ? 3u : 4u;
             }
             V.elig_end = (uint32_t)(((d - s) + 127u) & ~(uint64_t)63);
@@ -325,7 +327,7 @@ __device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const S
             V.more_after = 0u;
             const uint32_t left = cap_ > n_out ? cap_ - n_out : 0u;
             charge(0);
-            const uint32_t c = seed_sequence_fast<0, true, VAR>(seq + s, (uint32_t)(d - s), P, T, SF, A.mz_hash + base_ + n_out, A.mz_pos + base_ + n_out, left, pre, false, V,
+            const uint32_t c = seed_sequence_fast<0, true, VAR, Spec>(seq + s, (uint32_t)(d - s), P, T, SF, A.mz_hash + base_ + n_out, A.mz_pos + base_ + n_out, left, pre, false, V,
                                                                 A.mz_last ? A.mz_last + base_ + n_out : nullptr);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             wave_sync();
@@ -335,7 +337,7 @@ __device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const S
                 seg_min_last = 0;
             } else {
                 n_out += c;
-                seg_a = heads_back(seq, s, d, P.l - 1u, P);
+                seg_a = heads_back<Spec>(seq, s, d, spec_l<Spec>(P) - 1u, P);
                 seg_min_last = d;
             }
         }
@@ -385,17 +387,18 @@ __device__ __forceinline__ void store_hit(const SplitArgs &A, uint32_t r, const 
     }
 }
 
-template <int CH, bool TIMING, bool VAR = true>
+template <int CH, bool TIMING, bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ void map_read(const SplitArgs &A, MapListLds &S, MatchRec *scratch, uint32_t r, uint64_t len, uint32_t cnt,
                                          uint64_t base, unsigned long long &t_steps, unsigned long long &t_lookups, mq_hit &h) {
     const uint32_t lane = lane_id();
     const DevParams &P = A.P;
+    const uint32_t k = spec_k<Spec>(P);
     h.status = MQ_HIT_UNMAPPED;
     h.ref_id = h.rc = h.mapq = h.q_start = h.q_end = h.r_start = h.r_end = h.score = h.n_kminmers = h.q_start_hi = h.q_end_hi = 0;
     uint32_t n_kmm = 0;
     if (cnt == LIST_OVERFLOW) {
         h.status = MQ_HIT_OVERFLOW;  // the list fits neither its region nor the pool: nothing was computed for this read
-    } else if (cnt >= P.k) {
+    } else if (cnt >= k) {
         mq_kminmer *d = nullptr;
         uint32_t dcap = 0;
         if (A.dump) {
@@ -405,8 +408,8 @@ __device__ __forceinline__ void map_read(const SplitArgs &A, MapListLds &S, Matc
         MapSink sink(A.table, A.mask, P, scratch, A.cap_matches, S.rec, d, dcap, var_rev_eq<VAR>(P));
         const unsigned long long *lh = A.mz_hash + base;
         const uint32_t *lp = A.mz_pos + base;
-        const uint32_t chunk = 64u * (uint32_t)ML_NB + P.k - 1u;
-        for (uint32_t g = 0; g + P.k <= cnt;) {
+        const uint32_t chunk = 64u * (uint32_t)ML_NB + k - 1u;
+        for (uint32_t g = 0; g + k <= cnt;) {
             const uint32_t have = cnt - g < chunk ? cnt - g : chunk;
             {  // L2-served loads (the list was written by this very wave), ALL in flight before the first is stored: one L2 round trip
                // per chunk (a loop that loads and stores 64 entries at a time exposes one per 64 entries)
@@ -435,7 +438,7 @@ __device__ __forceinline__ void map_read(const SplitArgs &A, MapListLds &S, Matc
             mq_clk(5);
             // seeding variant 16: the chunk's second positions take the place of its hashes once those are used up (S.h as dwords)
             uint32_t *mzq = (VAR && A.mz_last) ? reinterpret_cast<uint32_t *>(S.h) : nullptr;
-            sink.template consume_list<ML_NB>(S.h, S.p, have, [&]() {
+            sink.template consume_list<ML_NB, Spec>(S.h, S.p, have, [&]() {
                 if (mzq) {
                     const uint32_t *lq = A.mz_last + base + g;
                     wave_sync();  // every lane's reads of the staged hashes are done
@@ -444,7 +447,7 @@ __device__ __forceinline__ void map_read(const SplitArgs &A, MapListLds &S, Matc
                 }
             }, mzq);
             wave_sync();
-            g += have - (P.k - 1u);
+            g += have - (k - 1u);
         }
         sink.finish_runs();
         n_kmm = sink.kmm_count;
@@ -501,7 +504,9 @@ union MapWaveLds {
 // (Experiments that lived here behind macros until round 5 -- the next read's first super-row prefetched into LDS, the read's minimizer
 // list kept in LDS, the prefetch issued when the probes are done, staggered wave starts: all measured at or below the product path --
 // are in git history, last at commit cc976e3; numbers in profiles/NOTES.md.)
-template <int CH, bool TIMING = false, bool VAR = false>
+// Spec: the parameters the pair is compiled for (mq_device.hpp): SpecNone reads k, l, use_hpc, fold and fast_kh from A.P; a SpecFixed pair is
+// launched only for an index whose A.P says the same (MAP_SPECS, mq_host_state.hpp)
+template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone>
 __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(const SplitArgs A) {
     // one block of LDS with the tables FIRST: T.rot's entries are addressed through the 16-bit immediate offset of ds_read_b128
     __shared__ struct {
@@ -510,7 +515,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
     } W;
     SeedTables &T = W.T;
     MapWaveLds(&SS)[MAP_WAVES] = W.SS;
-    build_seed_tables(T, A.P.l, var_h32<VAR>(A.P));
+    build_seed_tables(T, spec_l<Spec>(A.P), var_h32<VAR>(A.P));
     __syncthreads();  // the only workgroup-wide rendezvous; waves are independent from here on
     const uint32_t lane = lane_id();
     const uint32_t wv = rdfirst(threadIdx.x >> 6);  // wave-uniform: per-wave bases stay in SGPRs
@@ -585,10 +590,10 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         // extract(): len < l + k - 1 => None (src/mers.rs:44)
         if (len >> 32) {
             cnt = LIST_OVERFLOW;  // beyond the documented limit (checked on the host where the host sees the lengths): loud, not wrong
-        } else if (len >= (uint64_t)P.l + P.k - 1u && !var_keep_none<VAR>(P)) {
+        } else if (len >= (uint64_t)spec_l<Spec>(P) + spec_k<Spec>(P) - 1u && !var_keep_none<VAR>(P)) {
             uint32_t cap;
             list_region(A, o0 - o_base, len, r, base, cap);
-            cnt = A.force_general ? SD_NOT_FAST : seed_read_fast<0, VAR>(A, T, S.seed, A.bases + o0, (uint32_t)len, base, cap, n_moved, pre, false);
+            cnt = A.force_general ? SD_NOT_FAST : seed_read_fast<0, VAR, Spec>(A, T, S.seed, A.bases + o0, (uint32_t)len, base, cap, n_moved, pre, false);
             if (cnt == SD_NOT_FAST) {
                 n_general++;
                 // a byte other than A C G T (or a candidate on the bound): the read is queued for map_declined_kernel, which seeds it stretch
@@ -607,7 +612,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         uint4 nd = make_uint4(0u, 0u, 0u, 0u);
         if (lane == 0 && rn < n_items) nd = work[rn];  // a vector load by one lane: in flight through the map phase (a scalar load would be waited for at its first LDS wait)
         mq_hit h;
-        map_read<CH, TIMING, VAR>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
+        map_read<CH, TIMING, VAR, Spec>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
         wave_sync();
         const uint32_t r_done = r;
         const uint32_t nw = rdfirst(nd.w);
@@ -639,7 +644,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
 
 // The reads map_kernel queued (the fast seeder declined them): seeded stretch by stretch (seed_read_hybrid), mapped, stored.  Launched behind
 // map_kernel in every launch sequence; its waves leave at once when the queue is empty.
-template <int CH, bool TIMING = false, bool VAR = false>
+template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone>
 __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined_kernel(const SplitArgs A) {
     const uint32_t nq = A.counters[2];
     if (nq == 0) return;
@@ -647,7 +652,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
         SeedTables T;
         MapWaveLds SS[MAP_WAVES];
     } W;
-    build_seed_tables(W.T, A.P.l, var_h32<VAR>(A.P));
+    build_seed_tables(W.T, spec_l<Spec>(A.P), var_h32<VAR>(A.P));
     __syncthreads();
     const uint32_t lane = lane_id();
     const uint32_t wv = rdfirst(threadIdx.x >> 6);
@@ -671,11 +676,11 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
         uint32_t cap;
         list_region(A, o0 - o_base, len, r, base, cap);
         unsigned long long tacc[3] = {0ull, 0ull, 0ull};
-        const uint32_t cnt = seed_read_hybrid<VAR>(A, W.T, S.seed, S.general, A.bases + o0, len, base, cap, n_moved, TIMING ? tacc : nullptr);
+        const uint32_t cnt = seed_read_hybrid<VAR, Spec>(A, W.T, S.seed, S.general, A.bases + o0, len, base, cap, n_moved, TIMING ? tacc : nullptr);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's list stores have reached L2
         wave_sync();
         mq_hit h;
-        map_read<CH, TIMING, VAR>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
+        map_read<CH, TIMING, VAR, Spec>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
         wave_sync();
         store_hit(A, r, h);
         if (TIMING && lane == 0) {  // mq_last_read_cycles: this read's cycles here; in the start word's place bit 63 and the seeding split in

@@ -404,7 +404,10 @@ __device__ __forceinline__ Hash2 window_hash_q(const SeedTables &T, const SeedLd
     return h;
 }
 
+// (a SpecFixed holds the form for its own l and nothing else; l is then Spec::L)
+template <class Spec = SpecNone>
 __device__ __forceinline__ Hash2 window_hash(const SeedTables &T, const SeedLds &S, uint32_t l, uint32_t a) {
+    if constexpr (Spec::FIXED) return window_hash_fixed<Spec::L>(T, S, a);
     if (l == 31u) return window_hash_fixed<31>(T, S, a);  // the reference's default l (src/main.rs: -l 31) and every BASELINE configuration
     // the other window lengths the reference's scripts use (example/run_ecoli.sh:26 -l 16, the second pass's -l 14, the l sweep of
     // experiments/figure-k-l): 12 <= l < 32 by the number of whole quads; anything else through the loop below
@@ -517,14 +520,15 @@ __device__ __forceinline__ uint32_t stage_b_block(const SeedTables &T, uint32_t 
 // The outcome of every step's high-word test goes into the lane's flag words (S.flagw, one 32-step word per store); nothing
 // else is kept (stage R computes a candidate's hashes again).
 // Steps past the last window (only the last active lane has them) may set bits too: stage R masks them.
+template <class Spec = SpecNone>
 __device__ __forceinline__ void seed_stage_b(const SeedTables &T, SeedLds &S, const DevParams &P, uint32_t w_eff) {
     const uint32_t lane = lane_id();
-    const uint32_t l = P.l;
+    const uint32_t l = spec_l<Spec>(P);
     const uint32_t lc = (w_eff + 63u) >> 6;
     const uint32_t s0 = lane * lc;
     const uint32_t bhi = (uint32_t)(P.bound >> 32);
     if (s0 < w_eff) {  // lanes beyond the last window sit out (exec-masked)
-        const Hash2 h0 = window_hash(T, S, l, s0);  // the lane's first window: G_0 = F_0, H_0 = R_0
+        const Hash2 h0 = window_hash<Spec>(T, S, l, s0);  // the lane's first window: G_0 = F_0, H_0 = R_0
         uint32_t glo = h0.flo, ghi = h0.fhi, hlo = h0.rlo, hhi = h0.rhi;
         // nibble m of xe / xo = out | in<<2 for step 2m / 2m+1 of a 16-step block
         auto mk_xe = [](uint32_t ow, uint32_t iw) { return (ow & 0x33333333u) | ((iw & 0x33333333u) << 2); };
@@ -804,7 +808,7 @@ struct GlobalList {  // a region of the minimizer buffers in device memory (entr
 // Every lane first writes the windows of its own candidates to their places in the list (its flags are in registers: lowest
 // set bit, clear, next), so that a candidate's lane afterwards reads ONE value and starts its look-ups -- no search for the owning
 // lane, no bit select in another lane's flags.
-template <bool VIEW = false, class Out = GlobalList, bool VAR = true>
+template <bool VIEW = false, class Out = GlobalList, bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ uint32_t seed_stage_r(const SeedTables &T, SeedLds &S, const DevParams &P, uint32_t w_eff,
                                                  uint32_t n_blocks, uint32_t n_codes, uint32_t raw_base, uint32_t carry_n,
                                                  const Out &out, uint32_t out_base, bool &inexact, const SeedView &V = SeedView()) {
@@ -857,7 +861,7 @@ __device__ __forceinline__ uint32_t seed_stage_r(const SeedTables &T, SeedLds &S
             const uint32_t i = i0 + lane;
             if (i < r1) {
                 const uint32_t j = S.cand[i - r0];
-                const Hash2 wh = window_hash(T, S, P.l, j);
+                const Hash2 wh = window_hash<Spec>(T, S, spec_l<Spec>(P), j);
 #ifdef MQ_STAGE_R_SPLIT
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 asm volatile("" ::"v"(wh.flo), "v"(wh.fhi), "v"(wh.rlo), "v"(wh.rhi));
@@ -873,7 +877,7 @@ __device__ __forceinline__ uint32_t seed_stage_r(const SeedTables &T, SeedLds &S
                 // front of the next run head (l >= 2: code j + 1 is inside the window); 16 adds the window's last compressed base
                 uint32_t rep = pos, lp = 0;
                 if (var_pos_end<VAR>(P)) rep = seed_rawpos_batch(S, raw_base, carry_n, j + 1u) - 1u;
-                if (var_end_compressed<VAR>(P)) lp = seed_rawpos_batch(S, raw_base, carry_n, j + P.l - 1u) + (VIEW ? V.pos_add : 0u);
+                if (var_end_compressed<VAR>(P)) lp = seed_rawpos_batch(S, raw_base, carry_n, j + spec_l<Spec>(P) - 1u) + (VIEW ? V.pos_add : 0u);
                 if (listed) out.put(dest, list_hash<VAR>(P, hv), VIEW ? rep + V.pos_add : rep, lp);
                 if (VIEW) n_listed += (uint32_t)__popcll(__ballot(listed));
             }
@@ -897,17 +901,18 @@ __device__ __forceinline__ bool seed_fast_eligible(uint64_t len) { return len >=
 // pre / pre_valid: the sequence's first super-row already requested by the caller (stage_a_request); else it is requested here.
 // VIEW: seq[0, len) is a window of a longer sequence (SeedView): only the minimizers that start before V.elig_end are listed and
 // counted, positions are shifted by V.pos_add, the base in front of the view decides whether its first base is a run head.
-template <int STOP = 0, bool VIEW = false, class Out = GlobalList, bool VAR = true>
+template <int STOP = 0, bool VIEW = false, class Out = GlobalList, bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ uint32_t seed_sequence_fast_to(const uint8_t *__restrict__ seq, uint32_t len, const DevParams &P, const SeedTables &T,
                                                           SeedLds &S, const Out &out, APre &pre, bool pre_valid, const SeedView &V = SeedView()) {
     const uint32_t lane = lane_id();
+    const uint32_t l = spec_l<Spec>(P);
     uint32_t raw0 = 0, carry_n = 0, carry_prev = VIEW ? (V.first_prev & 3u) : 0u, n_out = 0;
     uint32_t halo_heads = 0, seg_heads = 0;  // VIEW: run heads at or behind V.elig_end / in front of it
     if (!seed_fast_eligible(len)) return SD_NOT_FAST;
     if (!pre_valid) stage_a_request(seq, len, 0, pre);
     while (raw0 < len) {
         uint32_t n_codes = 0, n_blocks = 0, raw_end = 0;
-        const bool ok = seed_stage_a(seq, len, raw0, carry_n, carry_prev, P.use_hpc != 0, P.fold != 0, T, S, n_codes, n_blocks, raw_end, pre,
+        const bool ok = seed_stage_a(seq, len, raw0, carry_n, carry_prev, spec_hpc<Spec>(P), spec_fold<Spec>(P), T, S, n_codes, n_blocks, raw_end, pre,
                                      !VIEW || V.first_prev >= 4u);
         mq_clk(0);
         if (!ok) return SD_NOT_FAST;
@@ -922,14 +927,14 @@ __device__ __forceinline__ uint32_t seed_sequence_fast_to(const uint8_t *__restr
             seg_heads += wave_sum_u32(c0);
         }
         const bool more = raw_end < len;
-        if (STOP != 1 && n_codes >= P.l) {
-            const uint32_t w_eff = n_codes - P.l + 1u;
+        if (STOP != 1 && n_codes >= l) {
+            const uint32_t w_eff = n_codes - l + 1u;
             if (var_h32<VAR>(P)) seed_stage_b32(T, S, P, w_eff);  // seeding variant 4: one word per strand
-            else seed_stage_b(T, S, P, w_eff);
+            else seed_stage_b<Spec>(T, S, P, w_eff);
             mq_clk(1);
             if (STOP != 2) {
                 bool inexact = false;
-                n_out += seed_stage_r<VIEW, Out, VAR>(T, S, P, w_eff, n_blocks, n_codes, raw0, carry_n, out, n_out, inexact, V);
+                n_out += seed_stage_r<VIEW, Out, VAR, Spec>(T, S, P, w_eff, n_blocks, n_codes, raw0, carry_n, out, n_out, inexact, V);
                 mq_clk(2);
                 if (inexact) return SD_NOT_FAST;
             }
@@ -937,7 +942,7 @@ __device__ __forceinline__ uint32_t seed_sequence_fast_to(const uint8_t *__restr
         if (more) {
             // the last l-1 compressed bases (all of them when the tile has fewer: a very long homopolymer run) open the next
             // tile's code stream; their raw positions stay available for windows that start in them
-            const uint32_t new_cn = n_codes < P.l - 1u ? n_codes : P.l - 1u;
+            const uint32_t new_cn = n_codes < l - 1u ? n_codes : l - 1u;
             uint32_t cpos = 0, ccode = 0;
             if (lane < new_cn) cpos = seed_rawpos_batch(S, raw0, carry_n, n_codes - new_cn + lane);
             if (lane < 4u) {
@@ -956,17 +961,17 @@ __device__ __forceinline__ uint32_t seed_sequence_fast_to(const uint8_t *__restr
         mq_clk(3);
     }
     // too few run heads behind elig_end (long homopolymer runs): the general seeder takes the segment -- unless no l-mer starts in it at all
-    if (VIEW && V.more_after && halo_heads + 1u < P.l && seg_heads != 0u) return SD_NOT_FAST;
+    if (VIEW && V.more_after && halo_heads + 1u < l && seg_heads != 0u) return SD_NOT_FAST;
     return n_out;
 }
 // the list in device memory: mz_hash[0, out_cap), mz_pos[0, out_cap)
-template <int STOP = 0, bool VIEW = false, bool VAR = true>
+template <int STOP = 0, bool VIEW = false, bool VAR = true, class Spec = SpecNone>
 __device__ __forceinline__ uint32_t seed_sequence_fast(const uint8_t *__restrict__ seq, uint32_t len, const DevParams &P, const SeedTables &T,
                                                        SeedLds &S, unsigned long long *__restrict__ mz_hash,
                                                        uint32_t *__restrict__ mz_pos, uint32_t out_cap, APre &pre, bool pre_valid,
                                                        const SeedView &V = SeedView(), uint32_t *__restrict__ mz_last = nullptr) {
     const GlobalList out = {mz_hash, mz_pos, out_cap, VAR ? mz_last : nullptr};
-    return seed_sequence_fast_to<STOP, VIEW, GlobalList, VAR>(seq, len, P, T, S, out, pre, pre_valid, V);
+    return seed_sequence_fast_to<STOP, VIEW, GlobalList, VAR, Spec>(seq, len, P, T, S, out, pre, pre_valid, V);
 }
 
 }  // namespace mq
