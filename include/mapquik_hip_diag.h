@@ -51,7 +51,7 @@ int mq_probe_rate(mq_index *idx, uint32_t blocks, uint32_t per_thread, uint32_t 
                   uint64_t *lookups, uint64_t *extra_steps);
 
 /* Diagnostic: shader-clock cycles the waves of the last map launch of the index's default context spent in each of 16 stages
- * (list in mapquik_amd/csrc/mq_device.hpp, mq_clk), summed over waves.  Only a library built with -DMQ_STAGE_CLOCKS fills
+ * (list in mapquik_amd/csrc/mq_wave.hpp, mq_clk), summed over waves.  Only a library built with -DMQ_STAGE_CLOCKS fills
  * them (tools/stage_clocks.py builds one beside the product library); the product build returns zeros. */
 int mq_last_stage_clocks(mq_index *idx, uint64_t *out16);
 

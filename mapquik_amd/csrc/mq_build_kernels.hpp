@@ -23,7 +23,7 @@ struct RefSeedArgs {
     uint32_t cap;
     uint32_t *counts;    // minimizers of segment s (may exceed cap: the list is then incomplete and the host retries with room)
     uint32_t *queue;     // segments the fast seeder declined
-    uint32_t *counters;  // [0] fast work, [1] queue length, [2] general work
+    RefSeedWork *counters;  // the seeders' work cursors (mq_blocks.hpp): points INTO the build's RefBuildInfo, at its `work`
     uint32_t force_general;
 };
 
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_ref_k
     SeedLds &S = W.SS[wv];
     for (;;) {
         uint32_t s = 0;
-        if (lane == 0) s = atomicAdd(&A.counters[0], 1u);
+        if (lane == 0) s = atomicAdd(&A.counters->fast_work, 1u);
         s = rdfirst(s);
         if (s >= A.n_seg) break;
         const uint64_t a = (uint64_t)s * REF_SEG;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_ref_k
                                                                            A.seg_last ? A.seg_last + at : nullptr);
         if (lane == 0) {
             A.counts[s] = cnt;
-            if (cnt == SD_NOT_FAST) A.queue[atomicAdd(&A.counters[1], 1u)] = s;
+            if (cnt == SD_NOT_FAST) A.queue[atomicAdd(&A.counters->queue_len, 1u)] = s;
         }
         wave_sync();
     }
@@ -72,10 +72,10 @@ __global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_ref_k
 __global__ __launch_bounds__(64) void seed_ref_general_kernel(const RefSeedArgs A) {
     __shared__ WaveLds S;
     const uint32_t lane = lane_id();
-    const uint32_t nq = A.counters[1];
+    const uint32_t nq = A.counters->queue_len;
     for (;;) {
         uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(&A.counters[2], 1u);
+        if (lane == 0) i = atomicAdd(&A.counters->general_work, 1u);
         i = rdfirst(i);
         if (i >= nq) break;
         const uint32_t s = A.queue[i];
@@ -92,7 +92,8 @@ __global__ __launch_bounds__(64) void seed_ref_general_kernel(const RefSeedArgs 
 
 // Stage 2: where every segment's list goes in the reference's dense list (exclusive scan of the counts, one workgroup), the total,
 // and the segments whose list outgrew its region (their counts are the true ones: they are seeded again, straight into their place in
-// the dense list, by seed_ref_redo_kernel).  info: [0] total, [1] number of such segments (zeroed by the host); over_queue: their numbers.
+// the dense list, by seed_ref_redo_kernel).  info: the build's RefBuildInfo (mq_blocks.hpp) as 64-bit words: `total`, and `overflowed` = the number of
+// such segments (zeroed by the host); over_queue: their numbers.
 __global__ __launch_bounds__(1024) void scan_counts_kernel(const uint32_t *__restrict__ counts, uint32_t n_seg, uint32_t cap,
                                                            unsigned long long *__restrict__ seg_off, unsigned long long *__restrict__ info,
                                                            uint32_t *__restrict__ over_queue) {
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const uint32_t *__res
     unsigned long long sum = 0;
     for (uint32_t i = lo; i < hi; ++i) {
         const uint32_t c = counts[i];
-        if (c > cap) over_queue[atomicAdd(&info[1], 1ull)] = i;
+        if (c > cap) over_queue[atomicAdd(&info[MQ_WORD64(RefBuildInfo, overflowed)], 1ull)] = i;
         sum += c;
     }
     part[t] = sum;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const uint32_t *__res
     }
     if (t == 1023u) {
         seg_off[n_seg] = part[1023];
-        info[0] = part[1023];
+        info[MQ_WORD64(RefBuildInfo, total)] = part[1023];
     }
 }
 
@@ -185,7 +186,7 @@ __global__ void ref_kminmers_kernel(const unsigned long long *__restrict__ dense
 // src/index.rs:67-69, 94-104 -- an entry whose end is 0 to begin with is born with the bit, the reference cannot tell it from
 // an empty one either).  Every field of the entry is written so that the order of the claimant's stores and a duplicate's flag does
 // not matter: the table starts zeroed and id_rc is only ever OR-ed.  acc (device counters): [0] keys claimed, [1] keys that turned dead.
-// Walks the probe sequence of mq_device.hpp (home slot, other way of the home bucket, following buckets).
+// Walks the probe sequence of mq_device.hpp ("Index table": home slot, other way of the home bucket, following buckets).
 __device__ __forceinline__ void table_insert(Bucket *__restrict__ table, uint64_t mask, unsigned long long key, const Entry &e, uint32_t times,
                                              uint32_t &n_claimed, uint32_t &n_dead) {
     const uint64_t nb = (mask + 1) >> 1;

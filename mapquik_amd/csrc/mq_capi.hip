@@ -22,11 +22,18 @@
 #include <type_traits>
 #include <vector>
 
-#include "mq_device.hpp"
-#include "mq_seed.hpp"
-#include "mq_fastx.hpp"
-#include "mq_join.hpp"
-#include "mq_fastx_lines.hpp"
+// The device parts (each includes what it needs):
+#include "mq_blocks.hpp"         // the word blocks kernels and host share: MapCounters, RefBuildInfo, the scanners' results
+#include "mq_wave.hpp"           // wave helpers, stage clocks, L2-served loads
+#include "mq_device.hpp"         // parameters, Spec, table and Match record types
+#include "mq_hash.hpp"           // ntHash seeds, tuple hashes (SipHash-1-3, KhFast)
+#include "mq_seed.hpp"           // the fast seeder
+#include "mq_seed_general.hpp"   // the general streaming seeder and its list sink
+#include "mq_probe.hpp"          // index probe, MapSink
+#include "mq_chain.hpp"          // chain stage
+#include "mq_fastx.hpp"          // record scanner: one sequence line per record
+#include "mq_join.hpp"           // one line-wrapped reference record joined
+#include "mq_fastx_lines.hpp"    // record scanner: line-wrapped records, found and joined
 
 using namespace mq;
 

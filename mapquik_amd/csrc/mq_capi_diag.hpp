@@ -38,7 +38,7 @@ __global__ void probe_rate_kernel(const Bucket *__restrict__ table, uint64_t mas
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            // the probe sequence of mq_device.hpp: home way, other way, then the following buckets
+            // the probe sequence of mq_device.hpp ("Index table"): home way, other way, then the following buckets
             const uint32_t w0 = (uint32_t)(key[u] & mask) & 1u;
             uint64_t ka = u64_of(kk[u].x, kk[u].y), kb = u64_of(kk[u].z, kk[u].w);
             uint64_t kh = w0 ? kb : ka, kp = w0 ? ka : kb;
@@ -76,6 +76,11 @@ __global__ void probe_rate_kernel(const Bucket *__restrict__ table, uint64_t mas
     }
 }
 
+// one field (or a run of neighbouring fields) of the context's counter block, copied to the host
+static hipError_t counter_field(const mq_ctx *c, void *dst, size_t offset, size_t bytes) {
+    return hipMemcpy(dst, reinterpret_cast<const uint8_t *>(c->d_counter.p) + offset, bytes, hipMemcpyDeviceToHost);
+}
+
 extern "C" {
 
 int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general) {
@@ -87,8 +92,9 @@ int mq_last_map_path_counts(mq_index *idx, uint32_t *n_fast, uint32_t *n_general
         int rc = use_device(idx);
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
-        uint32_t v[2] = {0, 0};
-        HIPCHK(hipMemcpy(v, c->d_counter + 4, 8, hipMemcpyDeviceToHost));
+        uint32_t v[2] = {0, 0};  // n_fast and n_general are neighbours: one copy
+        static_assert(offsetof(MapCounters, n_general) == offsetof(MapCounters, n_fast) + sizeof(MapCounters::n_fast), "n_fast, n_general");
+        HIPCHK(counter_field(c, v, offsetof(MapCounters, n_fast), sizeof(MapCounters::n_fast) + sizeof(MapCounters::n_general)));
         *n_fast = v[0];
         *n_general = v[1];
         return MQ_OK;
@@ -125,7 +131,7 @@ int mq_last_map_order(mq_index *idx, uint32_t *n_flagged, uint32_t *n_first) {
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
         uint32_t v = 0;
-        HIPCHK(hipMemcpy(&v, c->d_counter + WORK_NF, 4, hipMemcpyDeviceToHost));
+        HIPCHK(counter_field(c, &v, offsetof(MapCounters, n_flagged), sizeof(MapCounters::n_flagged)));
         *n_flagged = v;
         *n_first = v < WORK_FRONT_CAP ? v : WORK_FRONT_CAP;
         return MQ_OK;
@@ -162,10 +168,10 @@ int mq_map_probe_stats(mq_index *idx, const uint8_t *d_bases, const uint64_t *d_
         int rc = ctx_map_device(c, d_bases, d_offsets, n, total_bases, d_out, nullptr, true);  // the choice travels with this launch: contexts never see it
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
-        uint64_t v[2];
-        HIPCHK(hipMemcpy(v, c->d_counter + 8, 16, hipMemcpyDeviceToHost));
-        *extra_steps = v[0];
-        *lookups = v[1];
+        ProbeStats v;
+        HIPCHK(counter_field(c, &v, offsetof(MapCounters, probe), sizeof(MapCounters::probe)));
+        *extra_steps = v.steps;
+        *lookups = v.lookups;
         return MQ_OK;
     });
 }
@@ -181,14 +187,14 @@ int mq_last_read_cycles(mq_index *idx, uint32_t n, uint32_t *cycles, uint64_t *s
         int rc = use_device(idx);
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
-        HIPCHK(hipMemcpy(cycles, c->mz_count, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(start_ticks, c->mz_base, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cycles, ctx_read_cycles(c), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(start_ticks, ctx_read_start(c), (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
         return MQ_OK;
     });
 }
 
 // Diagnostic (-DMQ_STAGE_CLOCKS builds; zeros otherwise): shader-clock cycles the waves of the last map_kernel launch of the default
-// context spent per stage, summed over waves (stage list: mq_device.hpp, mq_clk).
+// context spent per stage, summed over waves (stage list: mq_wave.hpp, mq_clk).
 int mq_last_stage_clocks(mq_index *idx, uint64_t *out16) {
     return guarded([&]() -> int {
         if (!idx || !out16) return set_err(MQ_EINVAL, "bad arguments");
@@ -198,7 +204,8 @@ int mq_last_stage_clocks(mq_index *idx, uint64_t *out16) {
         int rc = use_device(idx);
         if (rc) return rc;
         HIPCHK(hipEventSynchronize(c->ev1));
-        HIPCHK(hipMemcpy(out16, c->d_counter + 16, MQ_N_CLK * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        static_assert(MQ_N_CLK == 16, "mq_last_stage_clocks fills 16 words (include/mapquik_hip_diag.h)");
+        HIPCHK(counter_field(c, out16, offsetof(MapCounters, clk), sizeof(MapCounters::clk)));
         return MQ_OK;
     });
 }

@@ -94,7 +94,7 @@ static int plan_ref_seed(mq_index *idx, const uint8_t *d_seq, uint64_t len, RefS
     if ((rc = b.counts.ensure(n_seg))) return rc;
     if ((rc = b.queue.ensure(n_seg))) return rc;
     if ((rc = b.seg_off.ensure((uint64_t)n_seg + 1))) return rc;
-    if (!b.info && (rc = b.info.alloc(8))) return rc;
+    if (!b.info && (rc = b.info.alloc(1))) return rc;
     if (!idx->grid_ref) {
         int occ = 0;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)seed_ref_kernel, 64 * SEED_WAVES, 0));
@@ -103,9 +103,9 @@ static int plan_ref_seed(mq_index *idx, const uint8_t *d_seq, uint64_t len, RefS
     if ((rc = b.seg_hash.ensure((uint64_t)n_seg * cap))) return rc;
     if ((rc = b.seg_pos.ensure((uint64_t)n_seg * cap))) return rc;
     if (with_last && (rc = b.seg_last.ensure((uint64_t)n_seg * cap))) return rc;
-    HIPCHK(hipMemsetAsync(b.info, 0, 64, 0));
+    HIPCHK(hipMemsetAsync(b.info, 0, sizeof(RefBuildInfo), 0));
     *A = RefSeedArgs{d_seq, len, n_seg, idx->dp, b.seg_hash, b.seg_pos, with_last ? b.seg_last.p : nullptr, cap, b.counts, b.queue,
-                     reinterpret_cast<uint32_t *>(b.info + 2), idx->force_general ? 1u : 0u};
+                     &b.info.p->work, idx->force_general ? 1u : 0u};
     return MQ_OK;
 }
 
@@ -118,11 +118,11 @@ static int seed_ref_segments(mq_index *idx, const RefSeedArgs &A, uint64_t *n_mz
     // the queue's length lives on the device: a fixed grid, waves that find the queue empty leave at once
     if ((rc = launch(seed_ref_general_kernel, std::min<uint32_t>((uint32_t)idx->n_cu * 32u, A.n_seg), 64, 0, A))) return rc;
     // (the fast seeder's queue is consumed by now: the same array takes the numbers of the segments whose list outgrew its region)
-    if ((rc = launch(scan_counts_kernel, 1, 1024, 0, b.counts, A.n_seg, A.cap, b.seg_off, b.info, b.queue))) return rc;
-    unsigned long long info[2] = {0, 0};
-    HIPCHK(hipMemcpy(info, b.info, 16, hipMemcpyDeviceToHost));
-    *n_mz = info[0];
-    *n_over = (uint32_t)info[1];
+    if ((rc = launch(scan_counts_kernel, 1, 1024, 0, b.counts, A.n_seg, A.cap, b.seg_off, &b.info.p->total, b.queue))) return rc;
+    RefBuildInfo h = {};  // total and overflowed: what lies in front of the seeders' cursors
+    HIPCHK(hipMemcpy(&h, b.info, offsetof(RefBuildInfo, work), hipMemcpyDeviceToHost));
+    *n_mz = h.total;
+    *n_over = (uint32_t)h.overflowed;
     return MQ_OK;
 }
 

@@ -20,9 +20,9 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
                       const LaunchOpt &o = LaunchOpt()) {
     mq_index *idx = c->idx;
     if (n == 0) return MQ_OK;
-    HIPCHK(hipMemsetAsync(c->d_counter, 0, 256, st));
+    HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(MapCounters), st));
     HIPCHK(hipEventRecord(c->ev0, st));
-    SplitArgs A;
+    MapArgs A;
     A.bases = d_bases;
     A.offsets = d_offsets;
     A.lens = o.d_lens;
@@ -49,7 +49,7 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     A.dump = o.d_dump;
     A.dump_off = o.d_dump_off;
     A.dump_counts = o.d_dump_counts;
-    A.stats64 = reinterpret_cast<unsigned long long *>(c->d_counter + 8);
+    A.stats64 = &c->d_counter.p->probe;
     A.work = c->work;
     A.heavy_first = idx->heavy_first ? 1u : 0u;
     if (!idx->split) {
@@ -302,24 +302,24 @@ static int fx_stage_piece(mq_ctx *c, const uint8_t *buf, uint64_t bytes) {
     return MQ_OK;
 }
 
-// Records of one sequence line in st_bases[b, e) (FASTA: 2 lines, FASTQ: 4): line ends to fx_nl, spans to st_off / st_lens, result words to fx_info
+// Records of one sequence line in st_bases[b, e) (FASTA: 2 lines, FASTQ: 4): line ends to fx_nl, spans to st_off / st_lens, FxRecords to fx_info
 static void fx_find_records(mq_ctx *c, FxKind kind, uint32_t b, uint32_t e, uint32_t n_tiles) {
     const uint32_t cap = fx_line_cap(e), grid = fx_grid(c->idx, n_tiles);
     hipLaunchKernelGGL(count_newlines_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, c->fx_nl, cap, c->fx_info, kind == FxKind::Fastq ? 4u : 2u);
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, c->fx_nl, cap, c->fx_info.p->words, kind == FxKind::Fastq ? 4u : 2u);
     hipLaunchKernelGGL(list_newlines_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_nl, cap);
     const auto spans_kernel = kind == FxKind::Fastq ? fastq_spans_kernel : fasta_spans_kernel;
-    hipLaunchKernelGGL(spans_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, c->st_bases, b, e, c->fx_nl, c->fx_info, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
+    hipLaunchKernelGGL(spans_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, c->st_bases, b, e, c->fx_nl, c->fx_info.p->words, reinterpret_cast<unsigned long long *>(c->st_off.p), c->st_lens, cap / 2);
 }
 
-// MQ_FASTX_FASTA_LINES: joined sequences to fl_joined, header spans to fl_hb / fl_he, their offsets / lengths to st_off / st_lens, result words to fx_info
+// MQ_FASTX_FASTA_LINES: joined sequences to fl_joined, header spans to fl_hb / fl_he, their offsets / lengths to st_off / st_lens, FxJoined to fx_info
 static void fx_join_records(mq_ctx *c, uint32_t b, uint32_t e, uint32_t n_tiles) {
     const uint32_t cap = fx_line_cap(e), grid = fx_grid(c->idx, n_tiles);
     unsigned long long *offs = reinterpret_cast<unsigned long long *>(c->st_off.p);
     hipLaunchKernelGGL(fl_count_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_counts);
-    hipLaunchKernelGGL(fl_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, offs, c->fl_he, cap / 2, c->fx_info);
-    hipLaunchKernelGGL(fl_write_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_info, c->fl_joined, c->fl_hb, c->fl_he, offs, cap / 2);
-    hipLaunchKernelGGL(fl_check_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, offs, c->st_lens, c->fx_info);
+    hipLaunchKernelGGL(fl_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->st_bases, b, e, c->fx_tile_counts, n_tiles, c->fx_tile_off, offs, c->fl_he, cap / 2, c->fx_info.p->words);
+    hipLaunchKernelGGL(fl_write_kernel, dim3(grid), dim3(256), 0, c->stream, c->st_bases, b, e, n_tiles, c->fx_tile_off, c->fx_info.p->words, c->fl_joined, c->fl_hb, c->fl_he, offs, cap / 2);
+    hipLaunchKernelGGL(fl_check_kernel, fx_record_grid(c->idx, cap / 2), dim3(256), 0, c->stream, offs, c->st_lens, c->fx_info.p->words);
 }
 
 static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint64_t bytes, uint32_t format) {
@@ -340,18 +340,18 @@ static int ctx_submit_fasta(mq_ctx *c, const uint8_t *buf, uint64_t begin, uint6
     if ((rc = wrapped ? ctx_ensure_lines(c, bytes) : c->fx_nl.ensure(cap))) return rc;
     if ((rc = c->st_off.ensure((uint64_t)cap / 2 + 1))) return rc;
     if ((rc = c->st_lens.ensure((uint64_t)cap / 2 + 1))) return rc;
-    if ((!c->fx_info && (rc = c->fx_info.alloc(4))) || (!c->h_fx_info && (rc = c->h_fx_info.alloc(4)))) return rc;
+    if ((!c->fx_info && (rc = c->fx_info.alloc(1))) || (!c->h_fx_info && (rc = c->h_fx_info.alloc(1)))) return rc;
     if ((rc = fx_stage_piece(c, buf, bytes))) return rc;
     if (wrapped) fx_join_records(c, b, e, n_tiles);
     else fx_find_records(c, kind, b, e, n_tiles);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fx_info, c->fx_info, sizeof(FxResult), hipMemcpyDeviceToHost, c->stream));
     c->fx_kind = kind;  // (the one place a piece becomes pending)
     c->fx_bytes = e;
     return MQ_OK;
 }
 
-// The piece in flight is finished: its result words are in h_fx_info when this returns MQ_OK
+// The piece in flight is finished: its scanner's result is in h_fx_info when this returns MQ_OK
 static int fx_take_info(mq_ctx *c) {
     c->fx_kind = FxKind::None;
     int rc = use_device(c->idx);
@@ -383,8 +383,9 @@ static int ctx_wait_fasta(mq_ctx *c, uint32_t *n_reads, const uint32_t **line_en
     if (c->fx_kind == FxKind::FastaLines) return set_err(MQ_ESTATE, "the submitted piece is MQ_FASTX_FASTA_LINES: call mq_ctx_wait_fasta_lines");
     int rc = fx_take_info(c);
     if (rc) return rc;
-    const uint32_t lines = c->h_fx_info[0], n = c->h_fx_info[1];
-    *flags = c->h_fx_info[2];
+    const FxRecords &res = c->h_fx_info.p->one;
+    const uint32_t lines = res.lines, n = res.records;
+    *flags = res.flags;
     *n_reads = *n_lines = 0;
     *line_ends = nullptr;
     *hits = nullptr;
@@ -408,8 +409,9 @@ static int ctx_wait_fasta_lines(mq_ctx *c, uint32_t *n_reads, const uint32_t **h
     if (c->fx_kind != FxKind::FastaLines) return set_err(MQ_ESTATE, "no MQ_FASTX_FASTA_LINES piece submitted on this context");
     int rc = fx_take_info(c);
     if (rc) return rc;
-    const uint32_t n = c->h_fx_info[0], joined = c->h_fx_info[1];
-    *flags = c->h_fx_info[2];
+    const FxJoined &res = c->h_fx_info.p->lines;
+    const uint32_t n = res.records, joined = res.joined;
+    *flags = res.flags;
     *n_reads = 0;
     *hdr_begin = *hdr_end = *seq_lens = nullptr;
     *hits = nullptr;

@@ -9,7 +9,8 @@
 //                           does not start with '>' where a header must be -- sets the IRREGULAR flag and the host parses the chunk itself
 // Integer / byte work, HBM-stream bound: a 32-MB chunk is scanned twice (64 MB of reads) in ~30 us.
 #pragma once
-#include "mq_device.hpp"
+#include "mq_blocks.hpp"  // FxRecords: the scan's result
+#include "mq_wave.hpp"    // lane_id, the wave scans
 
 namespace mq {
 
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void count_newlines_kernel(const uint8_t *__re
     }
 }
 
-// info: [0] lines (incl. the virtual end of a last line without '\n'), [1] records, [2] flags, [3] spare
+// info: an FxRecords (mq_blocks.hpp) as 32-bit words
 __global__ __launch_bounds__(1024) void scan_tiles_kernel(const uint8_t *__restrict__ buf, uint32_t begin, uint32_t end, const uint32_t *__restrict__ tile_counts,
                                                           uint32_t n_tiles, uint32_t *__restrict__ tile_off, uint32_t *__restrict__ nl_pos, uint32_t nl_cap,
                                                           uint32_t *__restrict__ info, uint32_t lines_per_record) {
@@ -108,10 +109,10 @@ __global__ __launch_bounds__(1024) void scan_tiles_kernel(const uint8_t *__restr
         // more line ends than nl_pos holds (records shorter than ~32 bytes: primers, barcodes, junk): the piece is IRREGULAR and NO record
         // is reported -- fasta_spans_kernel and the caller index nl_pos[0, lines) and must never see a count beyond its capacity
         const bool over = lines > nl_cap;
-        info[0] = over ? 0u : lines;
-        info[1] = over ? 0u : lines / lines_per_record;  // FASTA: header + sequence line; FASTQ: header, sequence, '+', quality
-        info[2] = (lines % lines_per_record) || over ? FX_IRREGULAR : 0u;
-        info[3] = 0;
+        info[MQ_WORD(FxRecords, lines)] = over ? 0u : lines;
+        info[MQ_WORD(FxRecords, records)] = over ? 0u : lines / lines_per_record;  // FASTA: header + sequence line; FASTQ: header, sequence, '+', quality
+        info[MQ_WORD(FxRecords, flags)] = (lines % lines_per_record) || over ? FX_IRREGULAR : 0u;
+        info[MQ_WORD(FxRecords, spare)] = 0;
     }
 }
 
@@ -140,12 +141,12 @@ __global__ __launch_bounds__(256) void list_newlines_kernel(const uint8_t *__res
     }
 }
 
-// starts[r] / lens[r]: the sequence line of record r; info[2] |= FX_IRREGULAR when the chunk is not "header line, sequence line" all through
+// starts[r] / lens[r]: the sequence line of record r; FxRecords::flags |= FX_IRREGULAR when the chunk is not "header line, sequence line" all through
 __global__ __launch_bounds__(256) void fasta_spans_kernel(const uint8_t *__restrict__ buf, uint32_t begin, uint32_t end, const uint32_t *__restrict__ nl_pos,
                                                           uint32_t *__restrict__ info, unsigned long long *__restrict__ starts, uint32_t *__restrict__ lens,
                                                           uint32_t span_cap) {
-    if (info[2] & FX_IRREGULAR) return;  // decided by the scan already (odd line count / more lines than nl_pos holds): nothing to look at
-    const uint32_t n_rec = info[1];
+    if (info[MQ_WORD(FxRecords, flags)] & FX_IRREGULAR) return;  // decided by the scan already (odd line count / more lines than nl_pos holds): nothing to look at
+    const uint32_t n_rec = info[MQ_WORD(FxRecords, records)];
     bool bad = false;
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += gridDim.x * blockDim.x) {
         const uint32_t hs = r == 0 ? begin : nl_pos[2u * r - 1u] + 1u;  // header line [hs, he), sequence line [he + 1, se)
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void fasta_spans_kernel(const uint8_t *__restr
             bad = true;
         }
     }
-    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[2], FX_IRREGULAR);
+    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[MQ_WORD(FxRecords, flags)], FX_IRREGULAR);
 }
 
 // FASTQ (the reference's default format when the name is not .fa / .fasta / .fna, src/main.rs:196-205; its headline real-data run is an
@@ -173,8 +174,8 @@ __global__ __launch_bounds__(256) void fasta_spans_kernel(const uint8_t *__restr
 __global__ __launch_bounds__(256) void fastq_spans_kernel(const uint8_t *__restrict__ buf, uint32_t begin, uint32_t end, const uint32_t *__restrict__ nl_pos,
                                                           uint32_t *__restrict__ info, unsigned long long *__restrict__ starts, uint32_t *__restrict__ lens,
                                                           uint32_t span_cap) {
-    if (info[2] & FX_IRREGULAR) return;
-    const uint32_t n_rec = info[1];
+    if (info[MQ_WORD(FxRecords, flags)] & FX_IRREGULAR) return;
+    const uint32_t n_rec = info[MQ_WORD(FxRecords, records)];
     bool bad = false;
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += gridDim.x * blockDim.x) {
         const uint32_t hs = r == 0 ? begin : nl_pos[4u * r - 1u] + 1u;
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void fastq_spans_kernel(const uint8_t *__restr
             bad = true;
         }
     }
-    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[2], FX_IRREGULAR);
+    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[MQ_WORD(FxRecords, flags)], FX_IRREGULAR);
 }
 
 }  // namespace mq

@@ -16,7 +16,9 @@
 //   fl_check_kernel   lens[r] = offsets[r + 1] - offsets[r]; a record without a sequence byte makes the piece IRREGULAR
 // Nothing is serial in the number of bytes.  Byte work, HBM-stream bound: the piece is read twice and its sequence bytes written once.
 #pragma once
-#include "mq_join.hpp"
+#include "mq_blocks.hpp"  // FxJoined: the scan's result
+#include "mq_join.hpp"    // store_kept16 and, through it, mq_fastx.hpp's tile helpers
+#include "mq_wave.hpp"
 
 namespace mq {
 
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(256) void fl_count_kernel(const uint8_t *__restrict
 }
 
 // tile_off[3 t ..]: kept bytes in front of tile t, header starts in front of it, the state entering it.
-// info: [0] records, [1] joined length, [2] flags, [3] spare.  offsets[records] = the joined length; hdr_end of a last record whose header
+// info: an FxJoined (mq_blocks.hpp) as 32-bit words.  offsets[records] = the joined length; hdr_end of a last record whose header
 // line the piece ends in = end.  IRREGULAR (no record reported): the piece does not start with '>', or holds more records than span_cap.
 __global__ __launch_bounds__(1024) void fl_scan_kernel(const uint8_t *__restrict__ buf, uint32_t begin, uint32_t end, const uint32_t *__restrict__ tile_counts,
                                                        uint32_t n_tiles, uint32_t *__restrict__ tile_off, unsigned long long *__restrict__ offsets,
@@ -171,10 +173,10 @@ __global__ __launch_bounds__(1024) void fl_scan_kernel(const uint8_t *__restrict
             offsets[n] = joined;
             if (n && (eff[1023] & 1u)) hdr_end[n - 1u] = end;  // the piece ends inside the last header line
         }
-        info[0] = bad ? 0u : n;
-        info[1] = bad ? 0u : joined;
-        info[2] = bad ? FX_IRREGULAR : 0u;
-        info[3] = 0;
+        info[MQ_WORD(FxJoined, records)] = bad ? 0u : n;
+        info[MQ_WORD(FxJoined, joined)] = bad ? 0u : joined;
+        info[MQ_WORD(FxJoined, flags)] = bad ? FX_IRREGULAR : 0u;
+        info[MQ_WORD(FxJoined, spare)] = 0;
     }
 }
 
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void fl_write_kernel(const uint8_t *__restrict
                                                        const uint32_t *__restrict__ tile_off, const uint32_t *__restrict__ info, uint8_t *__restrict__ joined,
                                                        uint32_t *__restrict__ hdr_begin, uint32_t *__restrict__ hdr_end, unsigned long long *__restrict__ offsets,
                                                        uint32_t span_cap) {
-    if (info[2] & FX_IRREGULAR) return;  // decided by the scan already: nothing to write (and no record index beyond span_cap is ever formed)
+    if (info[MQ_WORD(FxJoined, flags)] & FX_IRREGULAR) return;  // decided by the scan already: nothing to write (and no record index beyond span_cap is ever formed)
     const uint32_t lane = lane_id();
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t t = wave; t < n_tiles; t += n_waves) {
@@ -225,15 +227,15 @@ __global__ __launch_bounds__(256) void fl_write_kernel(const uint8_t *__restrict
 // lens[r]: the joined length of record r; a record without a sequence byte makes the piece IRREGULAR (the host parser gives such a
 // record a reading of its own -- the line behind a header is sequence even when it starts with '>' -- which is not restated here)
 __global__ __launch_bounds__(256) void fl_check_kernel(const unsigned long long *__restrict__ offsets, uint32_t *__restrict__ lens, uint32_t *__restrict__ info) {
-    if (info[2] & FX_IRREGULAR) return;
-    const uint32_t n_rec = info[0];
+    if (info[MQ_WORD(FxJoined, flags)] & FX_IRREGULAR) return;
+    const uint32_t n_rec = info[MQ_WORD(FxJoined, records)];
     bool bad = false;
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += gridDim.x * blockDim.x) {
         const uint32_t len = (uint32_t)(offsets[r + 1u] - offsets[r]);
         lens[r] = len;
         if (len == 0u) bad = true;
     }
-    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[2], FX_IRREGULAR);
+    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[MQ_WORD(FxJoined, flags)], FX_IRREGULAR);
 }
 
 }  // namespace mq

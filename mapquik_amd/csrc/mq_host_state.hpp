@@ -36,7 +36,7 @@ struct mq_ctx {
     ScopedEvent ev0, ev1;
     bool ev_valid = false;
     uint32_t last_spec = 0;         // MAP_SPECS id of the pair the last fused launch sequence ran (0: SpecNone)
-    Buf<uint32_t> d_counter;        // 64 words: SplitArgs::counters; [8..11] two 64-bit probe statistics of an instrumented launch
+    Buf<MapCounters> d_counter;     // one block (mq_blocks.hpp): MapArgs::counters, cleared in front of every launch sequence
     Buf<MatchRec> scratch;          // per mapping wave: cap_matches records
     size_t scratch_waves = 0;       // waves it has windows for
     Buf<unsigned long long> mz_hash;
@@ -60,8 +60,8 @@ struct mq_ctx {
     Buf<uint32_t> fx_tile_counts, fx_tile_off;
     Buf<uint32_t> fx_nl;
     PinnedBuf<uint32_t> h_fx_nl;
-    Buf<uint32_t> fx_info;          // lines, records, flags
-    PinnedBuf<uint32_t> h_fx_info;
+    Buf<FxResult> fx_info;          // one block (mq_blocks.hpp): FxRecords or FxJoined, by the scanner that ran (fx_kind)
+    PinnedBuf<FxResult> h_fx_info;
     PinnedBuf<uint8_t> h_fx_tail;   // one page: the piece's bytes behind its last page boundary
     // MQ_FASTX_FASTA_LINES (mq_fastx_lines.hpp): the joined sequence bytes, header spans and their mirrors; the joined lengths come back
     // from st_lens, the offsets of the joined reads live in st_off
@@ -79,6 +79,11 @@ struct mq_ctx {
     uint32_t p_n = 0;
     mq_hit *p_out = nullptr;
 };
+
+// Per-read timing of the instrumented launch (mq_last_read_cycles): the fused pair leaves it in the split pipeline's per-read arrays, which
+// it does not use otherwise -- the host side of read_cycles() / read_start(), mq_map_kernels.hpp
+static const uint32_t *ctx_read_cycles(const mq_ctx *c) { return c->mz_count; }
+static const uint64_t *ctx_read_start(const mq_ctx *c) { return c->mz_base; }
 
 // (the caller has selected the index's device: the context's buffers, events and stream go with it)
 static void ctx_release(mq_ctx *c) {
@@ -106,7 +111,7 @@ struct BuildScratch {
     Buf<uint32_t> seg_last, dense_last;  // seeding variant 16 only
     Buf<uint32_t> counts, queue;
     Buf<unsigned long long> seg_off;
-    Buf<unsigned long long> info;  // [0] total minimizers, [1] overflow flag, [2..3] seed_ref_kernel's work counters
+    Buf<RefBuildInfo> info;  // one block (mq_blocks.hpp): total, overflowed segments, the seeders' work cursors
     // mq_index_add_ref_staged_lines: kept bytes per tile of the region, their exclusive scan, [0] the joined length (mq_join.hpp)
     Buf<uint32_t> join_counts;
     Buf<unsigned long long> join_off, join_total;
@@ -395,7 +400,7 @@ static int alloc_table(mq_index *idx, uint64_t nslots) {
 // Every instantiation of the fused launch sequence's two kernels, by [seeding variant != 0][instrumented][chain chunk 4]: launch_map picks
 // its pair here or from MAP_SPECS below (map_pair_of), and the launch geometry is the minimum over the pairs the index can launch.  (The
 // instrumented launch is built for chunk 64 only.)
-using MapFn = void (*)(SplitArgs);
+using MapFn = void (*)(MapArgs);
 struct MapPair {
     MapFn map, declined;
 };
@@ -511,7 +516,7 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
     mq_index *idx = c->idx;
     int rc = ensure_geometry(idx);
     if (rc) return rc;
-    if (!c->d_counter && (rc = c->d_counter.alloc(64))) return rc;
+    if (!c->d_counter && (rc = c->d_counter.alloc(1))) return rc;
     if (!c->ev0) {
         HIPCHK(hipEventCreate(&c->ev0.h));
         HIPCHK(hipEventCreate(&c->ev1.h));

@@ -10,7 +10,8 @@
 // Tiles start at `begin` rounded down to 16 (never in front of the allocation); loads run to the next multiple of 16 behind `end`.
 // Byte work, HBM-stream bound: the region is read twice and written once.
 #pragma once
-#include "mq_fastx.hpp"
+#include "mq_fastx.hpp"  // the scanners' shared tile helpers
+#include "mq_wave.hpp"
 
 namespace mq {
 

@@ -6,8 +6,8 @@
 
 // The map path.  One wave per read, persistent waves pulling read indices from an atomic counter.  Two phases per read:
 //   seed   read -> ordered minimizer list {hash, raw position} in the read's HBM region     (mq_seed.hpp for ACGT-only reads,
-//          the general streaming seeder seed_segment of mq_device.hpp for the rest)
-//   map    list -> k-min-mers -> index probe -> Match runs -> chain -> mq_hit                (MapSink, chain_stage)
+//          the general streaming seeder seed_segment of mq_seed_general.hpp for the rest)
+//   map    list -> k-min-mers -> index probe -> Match runs -> chain -> mq_hit                (MapSink of mq_probe.hpp, chain_stage of mq_chain.hpp)
 // map_kernel runs both phases back to back in the same wave (default): while one wave waits for its index probes (random
 // 32-B slot reads: ~42 G lookups/s is all the memory system gives, tools/probe_rate.py) the other waves of the SIMD seed.
 // MQ_PIPELINE=split runs the phases as three launches (seed_reads_kernel, seed_general_kernel, map_lists_kernel) so that a
@@ -18,7 +18,7 @@
 // short-period tandem array can be far denser than 2 d) is written again, at its now known size, into an exact-size region
 // taken from a shared pool behind the regular regions.  Only when the pool is exhausted too does the read come back as
 // MQ_HIT_OVERFLOW (the host-buffer entry points then redo it with f16 = 65536).
-struct SplitArgs {
+struct MapArgs {
     const uint8_t *bases;
     const uint64_t *offsets;  // n + 1: read r starts at offsets[r]; offsets[n] = end of the buffer
     const uint32_t *lens;     // null: read r ends at offsets[r + 1]; else its length (raw FASTX buffers: headers and quality lines in between)
@@ -29,11 +29,11 @@ struct SplitArgs {
     uint32_t *mz_last;     // seeding variant 16 only (else nullptr): every minimizer's second position, same regions as mz_pos
     uint32_t *mz_count;    // split pipeline only: list length of read r (or NOT_FAST / LIST_OVERFLOW)
     uint64_t *mz_base;     // split pipeline only: where read r's list starts (its regular region or a pool region)
+                           // (the fused pair's instrumented launch keeps its per-read timing in these two: read_cycles / read_start below)
     uint64_t pool_base, pool_cap;  // the pool: entries [pool_base, pool_base + pool_cap)
     uint32_t f16, slack;
     uint32_t *queue;       // split pipeline only: reads for the general seeder
-    uint32_t *counters;    // [0] seed work, [1] map work, [2] queue length, [3] general work, [4] fast reads, [5] general reads,
-                           // [6] lists moved to the pool, [12..13] 64-bit pool cursor
+    MapCounters *counters; // the launch sequence's counter block (mq_blocks.hpp), cleared by the host
     uint32_t force_general;
     const Bucket *table;
     uint64_t mask;
@@ -44,15 +44,27 @@ struct SplitArgs {
     mq_kminmer *dump;
     const uint64_t *dump_off;
     uint32_t *dump_counts;
-    unsigned long long *stats64;  // instrumented launch only: [0] slots visited beyond the home slot, [1] lookups
+    ProbeStats *stats64;          // instrumented launch only: points INTO the block above, at counters->probe
     uint4 *work;                  // map_kernel's work items in launch order (order_reads_kernel)
     uint32_t heavy_first;         // order_reads_kernel: reads that look like short-period tandem arrays go first
 };
 
+// Per-read timing of the instrumented launch (mq_map_probe_stats -> mq_last_read_cycles).  The two arrays ALIAS the split pipeline's per-read
+// arrays mz_count / mz_base, which a fused launch sequence does not use otherwise (host side: ctx_read_cycles / ctx_read_start).
+//   read_cycles[r]  shader-clock cycles read r cost its wave (saturating at 2^32 - 1): map_kernel's, overwritten by map_declined_kernel's for
+//                   a read the fast seeder declined
+//   read_start[r]   map_kernel: the constant-clock tick at which the wave took read r up.  map_declined_kernel (decoded by tools/read_tail.py):
+//                   bit 63 set -- no tick has it -- and what seed_read_hybrid spent, three fields of 21 bits in units of 256 cycles, each
+//                   saturating at 2^21 - 1: bits 0..20 finding clean stretches | bits 21..41 in the fast seeder | bits 42..62 in the general one
+//                   (encoded in place there: moved into a device function of its own, the instrumented map_declined_kernel instantiations
+//                   come out with two SGPR spill slots exchanged, and the kernels' code is held identical across this kind of change)
+__device__ __forceinline__ uint32_t *read_cycles(const MapArgs &A) { return A.mz_count; }
+__device__ __forceinline__ uint64_t *read_start(const MapArgs &A) { return A.mz_base; }
+
 // ------------------------------------------------------------------- launch order
 // map_kernel takes work item i (an atomic counter) = descriptor work[WORK_FRONT_CAP - nf + i], i < nf + n:
 //   {offset lo, offset hi, length (low 32 bits), read | WORK_SKIP | WORK_TOO_LONG}
-// written per launch by order_reads_kernel (one lane per read): entry WORK_FRONT_CAP + r describes read r, and the nf = counters[7] reads
+// written per launch by order_reads_kernel (one lane per read): entry WORK_FRONT_CAP + r describes read r, and the nf = counters->n_flagged reads
 // that go FIRST sit in front of them (growing downwards; their natural entries carry WORK_SKIP).  One 16-byte load per read instead of
 // two or three dependent on the layout of the caller's arrays -- and a place to decide the order.
 // Which reads go first: those that look like a short-period tandem array.  A read inside an array of period p < l has p distinct l-mers;
@@ -64,7 +76,6 @@ struct SplitArgs {
 // with > 5 x (tools/heavy_study.py).  The order changes nothing but the order: results are stored by read number.
 constexpr uint32_t WORK_FRONT_CAP = 32768;  // reads that can go first (more are flagged: the rest stay where they are)
 constexpr uint32_t WORK_SKIP = 0x80000000u, WORK_TOO_LONG = 0x40000000u, WORK_ID_MASK = 0x3FFFFFFFu;
-constexpr uint32_t WORK_NF = 7;             // counters[WORK_NF]: reads flagged (may exceed WORK_FRONT_CAP)
 
 // 48 bases at p: does some lag 1..16 match in >= 27 of the first 32 positions?
 __device__ __forceinline__ bool window_periodic(const uint8_t *p) {
@@ -88,7 +99,7 @@ __device__ __forceinline__ bool window_periodic(const uint8_t *p) {
     return hit;
 }
 
-__global__ __launch_bounds__(256) void order_reads_kernel(const SplitArgs A) {
+__global__ __launch_bounds__(256) void order_reads_kernel(const MapArgs A) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= A.n) return;
     const uint64_t o0 = A.offsets[r];
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(256) void order_reads_kernel(const SplitArgs A) {
         auto win = [&](uint32_t at) { return A.bases + ((o0 + at) & ~(uint64_t)63); };  // ln >= 512: at >= 85, the window lies inside the read
         const bool p1 = window_periodic(win(ln / 6u)), p2 = window_periodic(win(ln / 2u)), p3 = window_periodic(win((ln / 6u) * 5u));  // (no short cut: the three windows' loads are in flight together)
         if (p1 | p2 | p3) {
-            const uint32_t k = atomicAdd(&A.counters[WORK_NF], 1u);
+            const uint32_t k = atomicAdd(&A.counters->n_flagged, 1u);
             if (k < WORK_FRONT_CAP) {
                 A.work[WORK_FRONT_CAP - 1u - k] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), ln, w);
                 w |= WORK_SKIP;
@@ -111,16 +122,16 @@ __global__ __launch_bounds__(256) void order_reads_kernel(const SplitArgs A) {
     A.work[WORK_FRONT_CAP + r] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)len, w);
 }
 
-__device__ __forceinline__ void list_region(const SplitArgs &A, uint64_t o0_rel, uint64_t len, uint32_t r, uint64_t &base, uint32_t &cap) {
+__device__ __forceinline__ void list_region(const MapArgs &A, uint64_t o0_rel, uint64_t len, uint32_t r, uint64_t &base, uint32_t &cap) {
     base = ((o0_rel * A.f16) >> 16) + (uint64_t)A.slack * r;
     const uint64_t c = ((len * A.f16) >> 16) + A.slack;
     cap = c > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)c;
 }
 constexpr uint32_t LIST_OVERFLOW = 0xFFFFFFFEu;  // list length value: the list fits neither its region nor the pool
 // an exact-size pool region for a list of cnt entries (wave-uniform); false when the pool is exhausted
-__device__ __forceinline__ bool pool_take(const SplitArgs &A, uint32_t cnt, uint64_t &base) {
+__device__ __forceinline__ bool pool_take(const MapArgs &A, uint32_t cnt, uint64_t &base) {
     unsigned long long at = 0;
-    if (lane_id() == 0) at = atomicAdd(reinterpret_cast<unsigned long long *>(A.counters + 12), (unsigned long long)cnt);
+    if (lane_id() == 0) at = atomicAdd(&A.counters->pool_cursor, (unsigned long long)cnt);
     at = rdlane64(at, 0);
     base = A.pool_base + at;
     return at + cnt <= A.pool_cap;
@@ -128,7 +139,7 @@ __device__ __forceinline__ bool pool_take(const SplitArgs &A, uint32_t cnt, uint
 
 // seed phase, fast seeder: list length, SD_NOT_FAST (declined: non-ACGT byte, ...) or LIST_OVERFLOW; base moves with the list
 template <int STOP = 0, bool VAR = true, class Spec = SpecNone>
-__device__ __forceinline__ uint32_t seed_read_fast(const SplitArgs &A, const SeedTables &T, SeedLds &S, const uint8_t *seq,
+__device__ __forceinline__ uint32_t seed_read_fast(const MapArgs &A, const SeedTables &T, SeedLds &S, const uint8_t *seq,
                                                    uint32_t len, uint64_t &base, uint32_t cap, uint32_t &n_moved, APre &pre, bool pre_valid) {
     uint32_t cnt = seed_sequence_fast<STOP, false, VAR, Spec>(seq, len, A.P, T, S, A.mz_hash + base, A.mz_pos + base, cap, pre, pre_valid, SeedView(),
                                                         A.mz_last ? A.mz_last + base : nullptr);
@@ -145,7 +156,7 @@ __device__ __forceinline__ uint32_t seed_read_fast(const SplitArgs &A, const See
 
 // seed phase, general streaming seeder (any bytes, any length)
 template <bool VAR = true>
-__device__ __forceinline__ uint32_t seed_read_general(const SplitArgs &A, WaveLds &S, const uint8_t *seq, uint64_t len, uint64_t &base,
+__device__ __forceinline__ uint32_t seed_read_general(const MapArgs &A, WaveLds &S, const uint8_t *seq, uint64_t len, uint64_t &base,
                                                       uint32_t cap, uint32_t &n_moved) {
     uint32_t cnt;
     {
@@ -281,7 +292,7 @@ __device__ __forceinline__ uint64_t heads_back(const uint8_t *__restrict__ seq, 
 }
 // tacc (instrumented launch only, else nullptr): cycles spent [0] finding stretches, [1] in the fast seeder, [2] in the general seeder
 template <bool VAR = true, class Spec = SpecNone>
-__device__ __forceinline__ uint32_t seed_read_hybrid(const SplitArgs &A, const SeedTables &T, SeedLds &SF, WaveLds &SG, const uint8_t *seq, uint64_t len,
+__device__ __forceinline__ uint32_t seed_read_hybrid(const MapArgs &A, const SeedTables &T, SeedLds &SF, WaveLds &SG, const uint8_t *seq, uint64_t len,
                                                      uint64_t &base, uint32_t cap, uint32_t &n_moved, unsigned long long *tacc = nullptr) {
     const DevParams &P = A.P;
     auto pass = [&](uint64_t base_, uint32_t cap_) __attribute__((always_inline)) -> uint32_t {
@@ -380,7 +391,7 @@ struct MapListLds {
 // map phase of read r: its list (cnt entries at base) -> mq_hit
 // the read's result is left in h (all lanes hold it); store_hit() writes it: the fused kernel does that after it has taken the
 // prefetched descriptor of its next read out of its registers, so that this store's acknowledgement is nothing a wave waits for
-__device__ __forceinline__ void store_hit(const SplitArgs &A, uint32_t r, const mq_hit &h) {
+__device__ __forceinline__ void store_hit(const MapArgs &A, uint32_t r, const mq_hit &h) {
     if (lane_id() == 0) {
         A.out[r] = h;
         if (A.dump_counts) A.dump_counts[r] = h.n_kminmers;
@@ -388,7 +399,7 @@ __device__ __forceinline__ void store_hit(const SplitArgs &A, uint32_t r, const 
 }
 
 template <int CH, bool TIMING, bool VAR = true, class Spec = SpecNone>
-__device__ __forceinline__ void map_read(const SplitArgs &A, MapListLds &S, MatchRec *scratch, uint32_t r, uint64_t len, uint32_t cnt,
+__device__ __forceinline__ void map_read(const MapArgs &A, MapListLds &S, MatchRec *scratch, uint32_t r, uint64_t len, uint32_t cnt,
                                          uint64_t base, unsigned long long &t_steps, unsigned long long &t_lookups, mq_hit &h) {
     const uint32_t lane = lane_id();
     const DevParams &P = A.P;
@@ -507,7 +518,7 @@ union MapWaveLds {
 // Spec: the parameters the pair is compiled for (mq_device.hpp): SpecNone reads k, l, use_hpc, fold and fast_kh from A.P; a SpecFixed pair is
 // launched only for an index whose A.P says the same (MAP_SPECS, mq_host_state.hpp)
 template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone>
-__global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(const SplitArgs A) {
+__global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(const MapArgs A) {
     // one block of LDS with the tables FIRST: T.rot's entries are addressed through the 16-bit immediate offset of ds_read_b128
     __shared__ struct {
         SeedTables T;
@@ -536,7 +547,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
     // the next read's first super-row across the map phase as well was measured at -3 %: a wave's loads return in order, so the
     // map phase's first wait -- an L2 round trip for the list -- then sits behind an HBM one.)
     // work items = order_reads_kernel's descriptors: the reads that go first, then all reads in their own order (those that went first marked)
-    const uint32_t nf = A.counters[WORK_NF] < WORK_FRONT_CAP ? A.counters[WORK_NF] : WORK_FRONT_CAP;
+    const uint32_t nf = A.counters->n_flagged < WORK_FRONT_CAP ? A.counters->n_flagged : WORK_FRONT_CAP;
     const uint4 *work = A.work + (WORK_FRONT_CAP - nf);
     const uint32_t n_items = A.n + nf;
     uint32_t r = 0xFFFFFFFFu;  // the read being worked on; none: the wave is done
@@ -558,7 +569,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
                 own2 = 0xFFFFFFFFu;
             } else {
                 i = 0;
-                if (lane == 0) i = atomicAdd(&A.counters[0], 1u);
+                if (lane == 0) i = atomicAdd(&A.counters->seed_work, 1u);
                 i = rdfirst(i) + 2u * n_waves;
             }
             r = 0xFFFFFFFFu;
@@ -580,7 +591,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         // THE hand-over of work items (one place): the item after this read is the wave's own second item or comes from the counter
         uint32_t rn_v = own2;
         if (own2 == 0xFFFFFFFFu) {
-            if (lane == 0) rn_v = atomicAdd(&A.counters[0], 1u);
+            if (lane == 0) rn_v = atomicAdd(&A.counters->seed_work, 1u);
             rn_v += 2u * n_waves;
         }
         own2 = 0xFFFFFFFFu;
@@ -598,7 +609,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
                 n_general++;
                 // a byte other than A C G T (or a candidate on the bound): the read is queued for map_declined_kernel, which seeds it stretch
                 // by stretch and maps it (what is stored for it here -- an unmapped record -- is overwritten there)
-                if (lane == 0) A.queue[atomicAdd(&A.counters[2], 1u)] = r;
+                if (lane == 0) A.queue[atomicAdd(&A.counters->queue_len, 1u)] = r;
                 cnt = 0;
                 mq_clk(10);
             } else {
@@ -624,20 +635,20 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         if (rn < n_items && (nw & WORK_SKIP)) take_now();  // that read went first
         if (TIMING && lane == 0) {
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_read0;
-            A.mz_count[r_done] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
-            A.mz_base[r_done] = t_real0;
+            read_cycles(A)[r_done] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
+            read_start(A)[r_done] = t_real0;
         }
     }
     if (lane == 0) {
-        if (n_fast) atomicAdd(&A.counters[4], n_fast);
-        if (n_general) atomicAdd(&A.counters[5], n_general);
-        if (n_moved) atomicAdd(&A.counters[6], n_moved);
+        if (n_fast) atomicAdd(&A.counters->n_fast, n_fast);
+        if (n_general) atomicAdd(&A.counters->n_general, n_general);
+        if (n_moved) atomicAdd(&A.counters->n_moved, n_moved);
         if (TIMING) {
-            atomicAdd(&A.stats64[0], t_steps);
-            atomicAdd(&A.stats64[1], t_lookups);
+            atomicAdd(&A.stats64->steps, t_steps);
+            atomicAdd(&A.stats64->lookups, t_lookups);
         }
 #ifdef MQ_STAGE_CLOCKS
-        for (int i = 0; i < MQ_N_CLK; ++i) atomicAdd(reinterpret_cast<unsigned long long *>(A.counters + 16) + i, mq_clk_lds().acc[wv][i]);
+        for (int i = 0; i < MQ_N_CLK; ++i) atomicAdd(&A.counters->clk[i], mq_clk_lds().acc[wv][i]);
 #endif
     }
 }
@@ -645,8 +656,8 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
 // The reads map_kernel queued (the fast seeder declined them): seeded stretch by stretch (seed_read_hybrid), mapped, stored.  Launched behind
 // map_kernel in every launch sequence; its waves leave at once when the queue is empty.
 template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone>
-__global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined_kernel(const SplitArgs A) {
-    const uint32_t nq = A.counters[2];
+__global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined_kernel(const MapArgs A) {
+    const uint32_t nq = A.counters->queue_len;
     if (nq == 0) return;
     __shared__ struct {
         SeedTables T;
@@ -664,7 +675,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
     unsigned long long t_steps = 0, t_lookups = 0;
     for (;;) {
         uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(&A.counters[3], 1u);
+        if (lane == 0) i = atomicAdd(&A.counters->declined_work, 1u);
         i = rdfirst(i);
         if (i >= nq) break;
         const uint32_t r = A.queue[i];
@@ -683,20 +694,19 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
         map_read<CH, TIMING, VAR, Spec>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
         wave_sync();
         store_hit(A, r, h);
-        if (TIMING && lane == 0) {  // mq_last_read_cycles: this read's cycles here; in the start word's place bit 63 and the seeding split in
-            // units of 256 cycles: stretch finder | fast seeder << 21 | general seeder << 42 (tools/read_tail.py)
+        if (TIMING && lane == 0) {  // mq_last_read_cycles: this read's cycles here; in the start word's place the seeding split (format: read_start)
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_read0;
-            A.mz_count[r] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
+            read_cycles(A)[r] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
             auto u21 = [](unsigned long long c) { return (c >> 8) > 0x1FFFFFull ? 0x1FFFFFull : (c >> 8); };
-            A.mz_base[r] = (1ull << 63) | u21(tacc[0]) | (u21(tacc[1]) << 21) | (u21(tacc[2]) << 42);
+            read_start(A)[r] = (1ull << 63) | u21(tacc[0]) | (u21(tacc[1]) << 21) | (u21(tacc[2]) << 42);
             (void)t_real0;
         }
     }
     if (lane == 0) {
-        if (n_moved) atomicAdd(&A.counters[6], n_moved);
+        if (n_moved) atomicAdd(&A.counters->n_moved, n_moved);
         if (TIMING) {
-            atomicAdd(&A.stats64[0], t_steps);
-            atomicAdd(&A.stats64[1], t_lookups);
+            atomicAdd(&A.stats64->steps, t_steps);
+            atomicAdd(&A.stats64->lookups, t_lookups);
         }
     }
 }
@@ -711,7 +721,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
 constexpr int SEED_WAVES = MQ_SEED_WAVES;
 
 template <int STOP = 0>
-__global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_reads_kernel(const SplitArgs A) {
+__global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_reads_kernel(const MapArgs A) {
     __shared__ struct {
         SeedTables T;
         SeedLds SS[SEED_WAVES];
@@ -729,7 +739,7 @@ __global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_reads
     uint32_t n_fast = 0, n_general = 0, n_moved = 0;
     for (;;) {
         uint32_t r = 0;
-        if (lane == 0) r = atomicAdd(&A.counters[0], 1u);
+        if (lane == 0) r = atomicAdd(&A.counters->seed_work, 1u);
         r = rdfirst(r);
         if (r >= A.n) break;
         const uint64_t o0 = A.offsets[r];
@@ -749,27 +759,27 @@ __global__ __launch_bounds__(64 * SEED_WAVES, MQ_SEED_MIN_WAVES) void seed_reads
         if (lane == 0) {
             A.mz_count[r] = cnt;
             A.mz_base[r] = base;
-            if (cnt == SD_NOT_FAST) A.queue[atomicAdd(&A.counters[2], 1u)] = r;
+            if (cnt == SD_NOT_FAST) A.queue[atomicAdd(&A.counters->queue_len, 1u)] = r;
         }
         wave_sync();
     }
     if (lane == 0) {
-        if (n_fast) atomicAdd(&A.counters[4], n_fast);
-        if (n_general) atomicAdd(&A.counters[5], n_general);
-        if (n_moved) atomicAdd(&A.counters[6], n_moved);
+        if (n_fast) atomicAdd(&A.counters->n_fast, n_fast);
+        if (n_general) atomicAdd(&A.counters->n_general, n_general);
+        if (n_moved) atomicAdd(&A.counters->n_moved, n_moved);
     }
 }
 
 // the reads queued by seed_reads_kernel, through the general streaming seeder
-__global__ __launch_bounds__(64) void seed_general_kernel(const SplitArgs A) {
+__global__ __launch_bounds__(64) void seed_general_kernel(const MapArgs A) {
     __shared__ WaveLds S;
     const uint32_t lane = lane_id();
-    const uint32_t nq = A.counters[2];
+    const uint32_t nq = A.counters->queue_len;
     const uint64_t o_base = A.offsets[0];
     uint32_t n_moved = 0;
     for (;;) {
         uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(&A.counters[3], 1u);
+        if (lane == 0) i = atomicAdd(&A.counters->declined_work, 1u);
         i = rdfirst(i);
         if (i >= nq) break;
         const uint32_t r = A.queue[i];
@@ -785,7 +795,7 @@ __global__ __launch_bounds__(64) void seed_general_kernel(const SplitArgs A) {
         }
         wave_sync();
     }
-    if (lane == 0 && n_moved) atomicAdd(&A.counters[6], n_moved);
+    if (lane == 0 && n_moved) atomicAdd(&A.counters->n_moved, n_moved);
 }
 
 #ifndef MQ_ML_MIN_WAVES
@@ -794,7 +804,7 @@ __global__ __launch_bounds__(64) void seed_general_kernel(const SplitArgs A) {
 constexpr int ML_WAVES = 4;
 
 template <int CH, bool TIMING = false>
-__global__ __launch_bounds__(64 * ML_WAVES, MQ_ML_MIN_WAVES) void map_lists_kernel(const SplitArgs A) {
+__global__ __launch_bounds__(64 * ML_WAVES, MQ_ML_MIN_WAVES) void map_lists_kernel(const MapArgs A) {
     __shared__ MapListLds SS[ML_WAVES];
     const uint32_t lane = lane_id();
     const uint32_t wv = rdfirst(threadIdx.x >> 6);  // wave-uniform: per-wave bases stay in SGPRs
@@ -803,7 +813,7 @@ __global__ __launch_bounds__(64 * ML_WAVES, MQ_ML_MIN_WAVES) void map_lists_kern
     unsigned long long t_steps = 0, t_lookups = 0;
     for (;;) {
         uint32_t r = 0;
-        if (lane == 0) r = atomicAdd(&A.counters[1], 1u);
+        if (lane == 0) r = atomicAdd(&A.counters->map_work, 1u);
         r = rdfirst(r);
         if (r >= A.n) break;
         const uint64_t len = A.lens ? (uint64_t)A.lens[r] : A.offsets[r + 1] - A.offsets[r];
@@ -813,7 +823,7 @@ __global__ __launch_bounds__(64 * ML_WAVES, MQ_ML_MIN_WAVES) void map_lists_kern
         wave_sync();
     }
     if (TIMING && lane == 0) {
-        atomicAdd(&A.stats64[0], t_steps);
-        atomicAdd(&A.stats64[1], t_lookups);
+        atomicAdd(&A.stats64->steps, t_steps);
+        atomicAdd(&A.stats64->lookups, t_lookups);
     }
 }

@@ -20,9 +20,11 @@
 //            (per-block counts of three candidate blocks compared at once) + select on its 64-bit head mask; then {hash, pos}
 //            go to the sequence's region of the minimizer buffer.
 // A sequence with a byte other than A C G T (or a candidate that passes the high-word test but not the exact one) is
-// handed to the general streaming seeder (mq_device.hpp) through a queue; both produce the same list.
+// handed to the general streaming seeder (mq_seed_general.hpp) through a queue; both produce the same list.
 #pragma once
 #include "mq_device.hpp"
+#include "mq_hash.hpp"
+#include "mq_wave.hpp"
 
 namespace mq {
 
@@ -129,11 +131,6 @@ __device__ __forceinline__ void build_seed_tables(SeedTables &T, uint32_t l, boo
 
 
 typedef uint4 __attribute__((aligned(1))) uint4_unaligned;
-
-__device__ __forceinline__ uint64_t ld_sc1_u64(const unsigned long long *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // L2-served: never a stale L1 line
-}
-__device__ __forceinline__ uint32_t ld_sc1_u32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // 16 ASCII bases (four dwords masked with 0x06060606: code<<1 in every byte) -> 32 bits, code j at bits 2j..2j+1.
 // Merge the dwords so that byte b holds bases b, 4+b, 8+b, 12+b, then transpose the 4x4 matrix of 2-bit elements.

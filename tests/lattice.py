@@ -9,23 +9,23 @@ import numpy as np
 
 # ---- the sizes the lattice is about (all compile-time constants of the kernels; kept by hand, the headers are not parsed)
 WORD = 16                      # mq_seed.hpp: load_piece, 16 raw bases per piece
-BLOCK = 64                     # mq_seed.hpp:230  one lane's 64-base block
-SD_SR_RAW = 4096               # mq_seed.hpp:29   raw bases per super-row
-SD_TILE_RAW = 12288            # mq_seed.hpp:34   raw bases per tile (the carry into the next one: l - 1 compressed bases)
+BLOCK = 64                     # mq_seed.hpp:227  one lane's 64-base block
+SD_SR_RAW = 4096               # mq_seed.hpp:31   raw bases per super-row
+SD_TILE_RAW = 12288            # mq_seed.hpp:36   raw bases per tile (the carry into the next one: l - 1 compressed bases)
 SD_STEPS_FLAG = 32             # mq_seed.hpp stage B: one flag word per 32 steps
 SD_STEPS_GROUP = 64            # mq_seed.hpp stage B: straight-line groups of 64 steps
-SD_OWNER_CAP = 256             # mq_seed.hpp:43   stage R: candidates listed per round
-GEN_LANE_BYTES = 16            # mq_device.hpp:563 general seeder: 16 bytes per lane
-GEN_STEP = 1024                # mq_device.hpp:563 one step of the general seeder's walk
-GEN_AHEAD = 2                  # mq_device.hpp:556 steps in flight behind the current one
-GEN_RING = 512                 # mq_device.hpp:31  ring entries per wave
-GEN_HASH_HEADS = 64            # mq_device.hpp     hashing per 64 run heads
+SD_OWNER_CAP = 256             # mq_seed.hpp:45   stage R: candidates listed per round
+GEN_LANE_BYTES = 16            # mq_seed_general.hpp:131 general seeder: 16 bytes per lane
+GEN_STEP = 1024                # mq_seed_general.hpp:131 one step of the general seeder's walk
+GEN_AHEAD = 2                  # mq_seed_general.hpp:138 steps in flight behind the current one
+GEN_RING = 512                 # mq_seed_general.hpp:14  ring entries per wave
+GEN_HASH_HEADS = 64            # mq_seed_general.hpp     hashing per 64 run heads
 HYB_MIN_CLEAN = 2048           # mq_map_kernels.hpp:177 clean stretch of a declined read the fast seeder takes (whole 64-byte blocks)
 LANE_BATCH = 64                # mq_map_kernels.hpp:369 k-min-mers of one lane-batch
 ML_NB = 6                      # mq_map_kernels.hpp:367 lane-batches per chunk: a chunk is 64 * ML_NB + k - 1 minimizers, overlap k - 1
 CHUNK_KMM = LANE_BATCH * ML_NB  # 384 k-min-mers per chunk
-MAP_LDS_RECS = 48              # mq_device.hpp:830 Match records kept in LDS
-CHAIN_CH = 64                  # mq_device.hpp     chain chunk
+MAP_LDS_RECS = 48              # mq_probe.hpp:48   Match records kept in LDS
+CHAIN_CH = 64                  # mq_chain.hpp      chain chunk
 REF_HALO = 2048                # mq_build_kernels.hpp:12
 REF_SEG = 2 * SD_TILE_RAW - REF_HALO  # mq_build_kernels.hpp:13  22528
 LIST_SLACK = 64                # mq_host_state.hpp:285 list region of a read: len * f + LIST_SLACK

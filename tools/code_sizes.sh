@@ -22,7 +22,7 @@ for ln in out.splitlines():
     p = ln.split()
     if len(p) >= 8 and re.match(r"^[0-9a-f]+$", p[1]):
         syms.append((int(p[1], 16), int(p[2]) if p[2].isdigit() else 0, p[3], p[7]))
-k = [s for s in syms if s[3] == "_Z10map_kernelILi64ELb0ELb0EEv9SplitArgs" and s[2] == "FUNC"]
+k = [s for s in syms if s[3] == "_Z10map_kernelILi64ELb0ELb0EEv7MapArgs" and s[2] == "FUNC"]
 if not k:
     sys.exit("map_kernel<64, false, false> not found")
 a0, size = k[0][0], k[0][1]
