@@ -205,7 +205,8 @@ int mq_map_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, u
  * (a hipStream_t, may be NULL).  total_bases = d_offsets[n] - d_offsets[0] (the host knows it: it built the offsets); it sizes
  * the per-read minimizer lists.  No allocation happens here once the scratch has grown to the batch shape (mq_map_reserve).
  * A read with more Match runs than the scratch holds (MQ_MATCH_CAP, default 2048) or with a minimizer list denser than
- * 4*density + 1/512 per base gets status MQ_HIT_OVERFLOW here (loud, never a wrong line). */
+ * 4*density + 1/512 per base gets status MQ_HIT_OVERFLOW here (loud, never a wrong line) -- unless a redo arena has been reserved
+ * (mq_map_reserve_redo / mq_ctx_reserve_redo below): then those reads are finished on the device, on the same stream. */
 int mq_map_batch_device(mq_index *idx, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases,
                         mq_hit *d_out, void *stream);
 
@@ -281,6 +282,37 @@ int mq_ctx_reserve(mq_ctx *ctx, uint32_t n_reads, uint64_t total_bytes);
 /* mq_map_batch_device on this context. */
 int mq_ctx_map_batch_device(mq_ctx *ctx, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases,
                             mq_hit *d_out, void *stream);
+
+/* Overflow reads of the device-resident form redone in stream, on the device (opt-in, per context; without a reservation the device form
+ * reports MQ_HIT_OVERFLOW as described above).  mq_ctx_reserve_redo allocates, now, a redo arena for up to max_reads overflow reads of up
+ * to max_read_len bases each.  From then on mq_ctx_map_batch_device queues, behind its launch sequence and on the caller's stream, a
+ * second launch sequence over the arena (worst-case list regions and Match windows, as the host-buffer forms use for their redo): three
+ * small kernels find the records with status MQ_HIT_OVERFLOW, copy those reads' bases into the arena and write the final mq_hit over each
+ * of them.  No host synchronisation, no allocation, no host read of a hit: when the stream reaches the end of the call's work, every
+ * overflow read that fitted the arena holds the record the host-buffer form returns for it, byte for byte.  A read that did not fit
+ * (more overflow reads than max_reads -- which of them get a place is not defined -- or longer than max_read_len) keeps
+ * MQ_HIT_OVERFLOW: loud as before.  The host-buffer, spans and FASTX-piece entry points redo their overflow reads as they always did.
+ *   max_reads == 0                     releases the arena: the feature is off again
+ *   MQ_ESTATE                          the context has a submitted batch
+ *   MQ_ENOMEM                          the context keeps the arena it had (or none)
+ *   MQ_EINVAL                          max_read_len == 0 with max_reads > 0; max_reads >= 2^30 or R * S (below) >= 2^47
+ * Reserve, release and mq_ctx_free only when the stream of the last device-form call has been ordered behind them by the caller, as for
+ * any two calls on one context (the arena itself waits for its last launch before its memory goes).
+ * What the arena costs in device memory, with R = max_reads, L = max_read_len, S = L + 64 rounded up to a multiple of 64:
+ *   R * S                                   the slots
+ *   (R * S + 64 R + 64) * 9/8 * 12          the slots' minimizer lists at one entry per base (* 16 with seeding variant 16)
+ *   G * 8 * L * 32                          Match windows of L records for the 8 waves of each of G workgroups, G = min(resident workgroups,
+ *                                           (R + 3) / 4, 2^30 / (256 L)) but at least 1: at most 1 GB unless L > 2^22
+ *   about (R + 16) * 5/4 * 2048 * 32        the ordinary Match windows of a launch over R reads (MQ_MATCH_CAP records each)
+ *   R * 112 + 0.6 MB                        per-read words, work descriptors, the slots' hits
+ * -- about 14.5 bytes per base of R * (L + 64), plus the windows: 0.5 GB for R = 256, L = 24,000; 1.3 GB for R = 256, L = 65,536.
+ * mq_ctx_redo_counts reports the last device-form call of the context: how many reads were redone and how many kept MQ_HIT_OVERFLOW
+ * (it waits for that call's work on the stream; (0, 0) before the first call; MQ_ESTATE without an arena).
+ * mq_map_reserve_redo / mq_map_redo_counts: the same for the index's default context (mq_map_batch_device). */
+int mq_ctx_reserve_redo(mq_ctx *ctx, uint32_t max_reads, uint32_t max_read_len);
+int mq_ctx_redo_counts(mq_ctx *ctx, uint32_t *redone, uint32_t *left);
+int mq_map_reserve_redo(mq_index *idx, uint32_t max_reads, uint32_t max_read_len);
+int mq_map_redo_counts(mq_index *idx, uint32_t *redone, uint32_t *left);
 
 /* Page-locked host memory for the buffers handed to mq_map_batch / mq_index_add_ref (a feeder that parses FASTX straight
  * into such buffers gets the full PCIe rate on the copy in; pageable buffers work too, at roughly a quarter of it). */

@@ -36,7 +36,8 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_index_add_ref", "mq_index_add_ref_device", "mq_index_finalize", "mq_index_get_stats", "mq_index_ref_info",
            "mq_map_batch", "mq_map_batch_device", "mq_map_reserve", "mq_kminmers_batch", "mq_index_lookup", "mq_format_paf",
            "mq_last_map_ms", "mq_last_map_path_counts", "mq_last_map_order", "mq_host_alloc", "mq_host_free", "mq_index_save", "mq_index_load", "mq_index_clone", "mq_map_probe_stats",
-           "mq_ctx_new", "mq_ctx_free", "mq_ctx_map_batch", "mq_ctx_submit", "mq_ctx_submit_spans", "mq_ctx_wait", "mq_ctx_reserve", "mq_ctx_map_batch_device", "mq_ctx_last_map_ms", "mq_probe_rate", "mq_last_stage_clocks", "mq_last_read_cycles", "mq_map_launch_waves", "mq_index_table_alloc_ms"]
+           "mq_ctx_new", "mq_ctx_free", "mq_ctx_map_batch", "mq_ctx_submit", "mq_ctx_submit_spans", "mq_ctx_wait", "mq_ctx_reserve", "mq_ctx_map_batch_device", "mq_ctx_last_map_ms", "mq_probe_rate", "mq_last_stage_clocks", "mq_last_read_cycles", "mq_map_launch_waves", "mq_index_table_alloc_ms",
+           "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts"]
 
 
 class MapquikError(RuntimeError):
@@ -169,6 +170,11 @@ def load_library(path=None):
     L.mq_host_free.argtypes = [vp]
     L.mq_last_map_path_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.mq_last_map_order.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "mq_ctx_reserve_redo"):
+        L.mq_ctx_reserve_redo.argtypes = [vp, u32, u32]
+        L.mq_map_reserve_redo.argtypes = [vp, u32, u32]
+        L.mq_ctx_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.mq_map_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -397,6 +403,19 @@ class Index:
         if self._L.mq_map_reserve(self._h, n_reads, int(total_bases)) != 0:
             raise _err(self._L, "mq_map_reserve")
 
+    def reserve_redo(self, max_reads, max_read_len):
+        """A redo arena for map_batch_device (the default context): up to max_reads overflow reads of up to max_read_len bases are finished
+        on the device, in stream, instead of coming back with status MQ_HIT_OVERFLOW.  max_reads = 0 releases it."""
+        if self._L.mq_map_reserve_redo(self._h, int(max_reads), int(max_read_len)) != 0:
+            raise _err(self._L, "mq_map_reserve_redo")
+
+    def redo_counts(self):
+        """(reads redone, reads left with MQ_HIT_OVERFLOW) of the last map_batch_device call; waits for its stream."""
+        a, b = C.c_uint32(), C.c_uint32()
+        if self._L.mq_map_redo_counts(self._h, C.byref(a), C.byref(b)) != 0:
+            raise _err(self._L, "mq_map_redo_counts")
+        return a.value, b.value
+
     def context(self):
         """A stream slot (mq_ctx): own stream, scratch and staging; contexts of one finalized index may map concurrently."""
         return Context(self)
@@ -622,6 +641,17 @@ class Context:
         if self._L.mq_ctx_map_batch_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n, int(total_bases), C.c_void_p(d_out),
                                            C.c_void_p(stream)) != 0:
             raise _err(self._L, "mq_ctx_map_batch_device")
+
+    def reserve_redo(self, max_reads, max_read_len):
+        """Index.reserve_redo for this context's map_batch_device."""
+        if self._L.mq_ctx_reserve_redo(self._h, int(max_reads), int(max_read_len)) != 0:
+            raise _err(self._L, "mq_ctx_reserve_redo")
+
+    def redo_counts(self):
+        a, b = C.c_uint32(), C.c_uint32()
+        if self._L.mq_ctx_redo_counts(self._h, C.byref(a), C.byref(b)) != 0:
+            raise _err(self._L, "mq_ctx_redo_counts")
+        return a.value, b.value
 
     def last_map_ms(self):
         ms = C.c_float()

@@ -93,4 +93,14 @@ static_assert(offsetof(FxRecords, lines) == 0 && offsetof(FxRecords, records) ==
               "result words");
 static_assert(offsetof(FxRecords, flags) == 8 && offsetof(FxRecords, flags) == offsetof(FxJoined, flags), "one place for the flags of both scanners");
 
+// ------------------------------------------------------------------ the overflow redo of a device-resident batch (RedoArena::counters)
+// cleared by the host in front of every device-form call on a context with a redo arena; written by redo_collect_kernel (mq_redo.hpp)
+struct RedoCounters {
+    uint32_t claimed;  // overflow reads short enough for a slot: the slot cursor (the first max_reads of them have one and are redone)
+    uint32_t left;     // overflow reads that keep MQ_HIT_OVERFLOW: longer than a slot, or no slot left
+    uint32_t spare[2];
+};
+static_assert(sizeof(RedoCounters) == 16 && offsetof(RedoCounters, claimed) == 0 && offsetof(RedoCounters, left) == 4 && offsetof(RedoCounters, spare) == 8,
+              "redo counters");
+
 }  // namespace mq

@@ -34,6 +34,7 @@
 #include "mq_fastx.hpp"          // record scanner: one sequence line per record
 #include "mq_join.hpp"           // one line-wrapped reference record joined
 #include "mq_fastx_lines.hpp"    // record scanner: line-wrapped records, found and joined
+#include "mq_redo.hpp"           // overflow redo of a device-resident batch: collect, copy, scatter
 
 using namespace mq;
 

@@ -101,6 +101,12 @@ static std::vector<uint32_t> overflow_reads(const mq_hit *out, uint32_t n) {
     return redo;
 }
 
+// The small grid of a redo launch: as many workgroups as have worst-case Match windows (cap records per wave) in 1 GB, at least one
+constexpr uint32_t REDO_WAVES = (uint32_t)std::max(MAP_WAVES, ML_WAVES);  // windows per workgroup, whichever pipeline runs
+static uint32_t redo_grid(const mq_index *idx, uint32_t cap) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min(idx->grid_fused, idx->grid_map), (1ull << 30) / ((uint64_t)cap * sizeof(MatchRec) * REDO_WAVES)));
+}
+
 // The relaunch: read j of the redo list is sb[so[j], so[j + 1]); its hit goes to out[redo[j]]
 static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std::vector<uint8_t> &sb, const std::vector<uint64_t> &so, mq_hit *out) {
     mq_index *idx = c->idx;
@@ -108,8 +114,8 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
     for (size_t j = 0; j < redo.size(); ++j) sub_max = std::max(sub_max, so[j + 1] - so[j]);
     const uint64_t sub_total = so.back();
     const uint32_t cap = (uint32_t)std::max<uint64_t>(sub_max, 1);  // a read cannot have more runs than bases
-    const uint32_t waves = std::max(MAP_WAVES, ML_WAVES);
-    const uint32_t rgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min(idx->grid_fused, idx->grid_map), (1ull << 30) / ((uint64_t)cap * sizeof(MatchRec) * waves)));
+    const uint32_t waves = REDO_WAVES;
+    const uint32_t rgrid = redo_grid(idx, cap);
     int rc = ctx_ensure(c, (uint32_t)redo.size(), sub_total, 65536u);
     if (rc) return rc;
     Buf<MatchRec> big;
@@ -252,6 +258,85 @@ static int ctx_wait(mq_ctx *c) {
     return redo_overflow(c, c->p_bases, c->p_offsets, c->p_lens, c->p_n, c->p_out);
 }
 
+// ---- the overflow redo of the device-resident form, in stream (mq_ctx_reserve_redo): the kernels of mq_redo.hpp around a launch sequence
+// over the context's redo arena.  Everything is allocated at the reservation; a call queues and returns.
+
+// max_reads == 0: the arena goes.  A failure leaves the context with the arena it had.
+static int ctx_reserve_redo(mq_ctx *c, uint32_t max_reads, uint32_t max_read_len) {
+    mq_index *idx = c->idx;
+    int rc = ctx_require_idle(c);
+    if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
+    if (max_reads == 0) {
+        c->redo.reset();
+        return MQ_OK;
+    }
+    if (max_read_len == 0) return set_err(MQ_EINVAL, "max_read_len must be positive");
+    const uint64_t stride = ((uint64_t)max_read_len + 64u + 63u) & ~(uint64_t)63;
+    // (list regions are placed at offset * f16 >> 16 with f16 = 65536: the arena's bytes times 2^16 must fit 64 bits)
+    if (max_reads > WORK_ID_MASK || (uint64_t)max_reads * stride >= (1ull << 47)) return set_err(MQ_EINVAL, "max_reads x max_read_len is too large");
+    if ((rc = ensure_geometry(idx))) return rc;
+    std::unique_ptr<RedoArena> a(new RedoArena());
+    a->max_reads = max_reads;
+    a->max_read_len = max_read_len;
+    a->stride = stride;
+    a->cap = max_read_len;  // a read cannot have more runs than bases
+    // no launch over max_reads reads has more workgroups than this, in either pipeline
+    a->grid = std::min(redo_grid(idx, a->cap), (max_reads + (uint32_t)std::min(MAP_WAVES, ML_WAVES) - 1u) / (uint32_t)std::min(MAP_WAVES, ML_WAVES));
+    a->sub.idx = idx;
+    if ((rc = ctx_ensure(&a->sub, max_reads, (uint64_t)max_reads * stride, 65536u))) return rc;
+    if ((rc = a->bases.alloc((uint64_t)max_reads * stride)) || (rc = a->offsets.alloc((uint64_t)max_reads + 1)) || (rc = a->lens.alloc(max_reads)) ||
+        (rc = a->ids.alloc(max_reads)) || (rc = a->src.alloc(max_reads)) || (rc = a->hits.alloc(max_reads)) ||
+        (rc = a->windows.alloc((uint64_t)a->grid * REDO_WAVES * a->cap)) || (rc = a->counters.alloc(1)))
+        return rc;
+    std::vector<uint64_t> slot_at((size_t)max_reads + 1);
+    for (size_t j = 0; j <= max_reads; ++j) slot_at[j] = j * stride;
+    HIPCHK(hipMemcpy(a->offsets, slot_at.data(), slot_at.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(a->bases, 0, (size_t)max_reads * stride));  // (the seeders look up to 64 bytes past a read's end, never into its result)
+    HIPCHK(hipEventCreateWithFlags(&a->done.h, hipEventDisableTiming));
+    c->redo = std::move(a);  // (the arena it had waits for its last launch and goes)
+    return MQ_OK;
+}
+
+// Queued behind the launch sequence that wrote d_out, on the same stream: no allocation, no synchronisation, no hit read by the host
+static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, mq_hit *d_out, hipStream_t st) {
+    RedoArena &a = *c->redo;
+    a.last_n = n;
+    if (n == 0) return MQ_OK;
+    int rc;
+    HIPCHK(hipMemsetAsync(a.counters, 0, sizeof(RedoCounters), st));
+    HIPCHK(hipMemsetAsync(a.lens, 0, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims is a read of length 0
+    if ((rc = launch(redo_collect_kernel, (n + 255u) / 256u, 256, st, d_out, d_offsets, n, a.max_reads, a.max_read_len, a.counters, a.ids, a.src, a.lens))) return rc;
+    if ((rc = launch(redo_copy_kernel, (a.max_reads + REDO_COPY_WAVES - 1u) / REDO_COPY_WAVES, 64 * REDO_COPY_WAVES, st, d_bases, a.src, a.lens, a.max_reads, a.bases, a.stride))) return rc;
+    LaunchOpt o;
+    o.scratch_override = a.windows;
+    o.cap_override = a.cap;
+    o.grid_override = a.grid;
+    o.f16 = 65536u;
+    o.d_lens = a.lens;
+    if ((rc = launch_map(&a.sub, a.bases, a.offsets, a.max_reads, a.hits, st, o))) return rc;
+    if ((rc = launch(redo_scatter_kernel, (a.max_reads + 255u) / 256u, 256, st, a.hits, a.ids, a.counters, a.max_reads, d_out))) return rc;
+    HIPCHK(hipEventRecord(a.done, st));
+    a.ran = true;
+    return MQ_OK;
+}
+
+// (redone, left) of the context's last device-form call, once its stream has passed the redo
+static int ctx_redo_counts(mq_ctx *c, uint32_t *redone, uint32_t *left) {
+    if (!c->redo) return set_err(MQ_ESTATE, "no redo arena reserved on this context: call mq_ctx_reserve_redo first");
+    RedoArena &a = *c->redo;
+    *redone = *left = 0;
+    if (a.last_n == 0) return MQ_OK;  // no call yet, or one without reads
+    int rc = use_device(c->idx);
+    if (rc) return rc;
+    HIPCHK(hipEventSynchronize(a.done));
+    RedoCounters v;
+    HIPCHK(hipMemcpy(&v, a.counters, sizeof(RedoCounters), hipMemcpyDeviceToHost));
+    *redone = std::min(v.claimed, a.max_reads);
+    *left = v.left;
+    return MQ_OK;
+}
+
 static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases, mq_hit *d_out,
                           hipStream_t st, bool instrumented = false) {
     mq_index *idx = c->idx;
@@ -263,7 +348,9 @@ static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     if ((rc = ctx_ensure(c, n, total_bases, list_f16(idx)))) return rc;
     LaunchOpt o;
     o.instrumented = instrumented;
-    return launch_map(c, d_bases, d_offsets, n, d_out, st, o);
+    if ((rc = launch_map(c, d_bases, d_offsets, n, d_out, st, o))) return rc;
+    // a context with a redo arena finishes its overflow reads behind the launch sequence (never for the instrumented, diagnostic launch)
+    return c->redo && !instrumented ? redo_in_stream(c, d_bases, d_offsets, n, d_out, st) : MQ_OK;
 }
 
 // ---- device-parsed FASTX pieces: the raw bytes go to the device, a record scanner (mq_fastx.hpp, mq_fastx_lines.hpp) finds the records,
@@ -536,6 +623,36 @@ int mq_map_batch_device(mq_index *idx, const uint8_t *d_bases, const uint64_t *d
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
         return ctx_map_device(idx->def_ctx.get(), d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
+    });
+}
+
+int mq_ctx_reserve_redo(mq_ctx *ctx, uint32_t max_reads, uint32_t max_read_len) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        return ctx_reserve_redo(ctx, max_reads, max_read_len);
+    });
+}
+
+int mq_map_reserve_redo(mq_index *idx, uint32_t max_reads, uint32_t max_read_len) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_reserve_redo(idx->def_ctx.get(), max_reads, max_read_len);
+    });
+}
+
+int mq_ctx_redo_counts(mq_ctx *ctx, uint32_t *redone, uint32_t *left) {
+    return guarded([&]() -> int {
+        if (!ctx || !redone || !left) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_redo_counts(ctx, redone, left);
+    });
+}
+
+int mq_map_redo_counts(mq_index *idx, uint32_t *redone, uint32_t *left) {
+    return guarded([&]() -> int {
+        if (!idx || !redone || !left) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_redo_counts(idx->def_ctx.get(), redone, left);
     });
 }
 

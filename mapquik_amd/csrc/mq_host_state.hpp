@@ -26,6 +26,8 @@ static int launch(void (*kernel)(KA...), uint32_t grid, uint32_t block, hipStrea
 // A piece of a FASTX file whose records the device finds (mq_ctx_submit_fastx): none in flight, or its format
 enum class FxKind { None, Fasta, Fastq, FastaLines };
 
+struct RedoArena;  // (below: it holds an mq_ctx of its own)
+
 // One stream slot: everything a map launch sequence writes (work counters, Match scratch, minimizer lists,
 // events) plus the staging buffers of the host-buffer entry points.  Launch sequences of DIFFERENT contexts of one index
 // may be in flight together (the index itself is read-only once finalized); one context runs one sequence at a time.
@@ -78,6 +80,34 @@ struct mq_ctx {
     const uint32_t *p_lens = nullptr;
     uint32_t p_n = 0;
     mq_hit *p_out = nullptr;
+    // mq_ctx_reserve_redo: what the device form needs to redo its overflow reads in stream (none: they come back MQ_HIT_OVERFLOW).  The
+    // last member, so the first to go: it waits for its own last launch, and its buffers go before the context's.
+    std::unique_ptr<RedoArena> redo;
+};
+
+// The redo arena of a context: room for max_reads overflow reads of a device-form call, and everything a launch sequence over them writes.
+// That is a context state of its own (`sub`: lists and per-read arrays from ctx_ensure(max_reads, max_reads * stride, 65536), work
+// descriptors, queue, counter block, events; no stream -- it is launched on the caller's), so the main launch's counters, events and spec id
+// keep describing the main launch.  Slot j is bases[j * stride, (j + 1) * stride): offsets[j] = j * stride is written once, here;
+// lens[j], ids[j], src[j] are redo_collect_kernel's (mq_redo.hpp).  (The owner has selected the index's device when the arena goes.)
+struct RedoArena {
+    uint32_t max_reads = 0, max_read_len = 0;
+    uint64_t stride = 0;           // bytes per slot: max_read_len + 64 rounded up to 64 (what the staging buffers leave behind a batch's last read)
+    uint32_t cap = 0, grid = 0;    // LaunchOpt::cap_override, grid_override of the launch: worst-case Match windows on a small grid
+    mq_ctx sub;
+    Buf<uint8_t> bases;
+    Buf<uint64_t> offsets;         // max_reads + 1
+    Buf<uint32_t> lens, ids;
+    Buf<uint64_t> src;             // where slot j's read begins in the caller's buffer
+    Buf<mq_hit> hits;
+    Buf<MatchRec> windows;         // grid * max(MAP_WAVES, ML_WAVES) windows of cap records
+    Buf<RedoCounters> counters;    // one block (mq_blocks.hpp), cleared in front of every device-form call
+    ScopedEvent done;              // behind redo_scatter_kernel of the last device-form call
+    bool ran = false;              // ... recorded at least once
+    uint32_t last_n = 0;           // reads of the last device-form call (0: none yet, or an empty one: nothing was queued)
+    ~RedoArena() {
+        if (ran) (void)hipEventSynchronize(done);  // the caller's stream has passed the arena's last use
+    }
 };
 
 // Per-read timing of the instrumented launch (mq_last_read_cycles): the fused pair leaves it in the split pipeline's per-read arrays, which
