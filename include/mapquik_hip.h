@@ -189,6 +189,43 @@ mq_index *mq_index_load(const char *path, int device);
 /* A replica of a finalized index on HIP device `device` (device-to-device copy of the table; the multi-GPU drivers build the
  * index once and clone it instead of indexing the reference on every GPU).  Free it with mq_index_free. */
 mq_index *mq_index_clone(const mq_index *src, int device);
+/* A finalized index kept and maintained (the on-disk index is this library's own: the reference re-indexes on every run).
+ * The table is order independent -- a slot is claimed once, and a key that arrives again only ever sets its tombstone bit -- so adding
+ * references to a populated table gives the table that a build from all references at once gives, and a table can be rebuilt at any
+ * other legal size from its own occupied slots.
+ *   mq_index_reopen(idx)     a finalized index (built, loaded or cloned) takes mq_index_add_ref* again, by every route, with reference ids
+ *                            distinct from the ones it has.  Waits for the device first.  Until the next mq_index_finalize every mapping
+ *                            entry point answers MQ_ESTATE, as for any index that is not finalized.  MQ_ESTATE when idx is not finalized.
+ *   mq_index_finalize(idx)   on a reopened index inserts the NEW references' k-min-mers into the existing table: no earlier reference is
+ *                            seeded or inserted again.  The table grows first (on the device, table to table; peak memory: both
+ *                            tables) when all k-min-mers together ask for a larger one than it has, and never shrinks; the counts are
+ *                            brought up to date from the insert's own counters (a new reference may turn an old unique key dead).
+ *                            Contexts made before the reopen stay valid, with their reservations and redo arenas, and map against the
+ *                            new table afterwards.  The growth follows the index's table factor, and a loaded or cloned index has the
+ *                            default (8) whatever size its table has: a caller that wants another calls mq_index_set_table_factor
+ *                            between mq_index_reopen and mq_index_finalize.  A finalize that fails before anything was inserted (no
+ *                            memory for the larger table, say) leaves the index open with its new references: it may be called
+ *                            again.  One that fails later has left part of the new keys in the table, and a second insertion would
+ *                            turn them dead: from then on mq_index_finalize and mq_index_add_ref* answer MQ_ESTATE and the index can
+ *                            only be freed (a build from scratch retries into a new table; an extension has no second table).
+ *   mq_index_resize(idx, table_slots, slots_per_kminmer)   the finalized index's table rebuilt at another size, on the device; waits for
+ *                            the device first.  Contexts stay valid.  Peak memory: the old table plus the new one.
+ *   mq_index_load_sized(path, device, table_slots, slots_per_kminmer)   mq_index_load with the file's slots scattered straight into a
+ *                            table of the chosen size (a table of the file's own size is never allocated).  Every refusal of
+ *                            mq_index_load stays; a size that does not exceed the file's key count is refused too.
+ *   mq_index_clone_sized(src, device, table_slots, slots_per_kminmer)   mq_index_clone with a table of the chosen size on the destination:
+ *                            the occupied slots are packed on the source device and 32 bytes per key cross the link, not the table.
+ * The size arguments, the same in the three sized calls -- at most one of them non-zero:
+ *   table_slots         an exact size: a power of two in [2, 2^40] and greater than n_keys (a table without an empty slot would make a
+ *                       miss walk forever)
+ *   slots_per_kminmer   2..64: the size a build of n_kminmers k-min-mers gets at that factor (mq_index_set_table_factor), raised if need
+ *                       be to the smallest legal size
+ *   both 0              as it is: mq_index_resize does nothing, the other two behave exactly like mq_index_load / mq_index_clone
+ * Anything else is MQ_EINVAL, checked before anything is allocated: the index is then untouched and usable. */
+int mq_index_reopen(mq_index *idx);
+int mq_index_resize(mq_index *idx, uint64_t table_slots, uint32_t slots_per_kminmer);
+mq_index *mq_index_load_sized(const char *path, int device, uint64_t table_slots, uint32_t slots_per_kminmer);
+mq_index *mq_index_clone_sized(const mq_index *src, int device, uint64_t table_slots, uint32_t slots_per_kminmer);
 int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len);
 /* The parameters an index was built with (a loaded file's k, l, density, use_hpc and seeding variant decide its keys), and the ones that
  * act at mapping time only -- Params.c / .s (Chain::get_match, src/chain.rs:147-169), .g (the gap tests, src/chain.rs:132-142) and the

@@ -37,7 +37,8 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_map_batch", "mq_map_batch_device", "mq_map_reserve", "mq_kminmers_batch", "mq_index_lookup", "mq_format_paf",
            "mq_last_map_ms", "mq_last_map_path_counts", "mq_last_map_order", "mq_host_alloc", "mq_host_free", "mq_index_save", "mq_index_load", "mq_index_clone", "mq_map_probe_stats",
            "mq_ctx_new", "mq_ctx_free", "mq_ctx_map_batch", "mq_ctx_submit", "mq_ctx_submit_spans", "mq_ctx_wait", "mq_ctx_reserve", "mq_ctx_map_batch_device", "mq_ctx_last_map_ms", "mq_probe_rate", "mq_last_stage_clocks", "mq_last_read_cycles", "mq_map_launch_waves", "mq_index_table_alloc_ms",
-           "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts"]
+           "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts",
+           "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized"]
 
 
 class MapquikError(RuntimeError):
@@ -175,6 +176,13 @@ def load_library(path=None):
         L.mq_map_reserve_redo.argtypes = [vp, u32, u32]
         L.mq_ctx_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.mq_map_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(L, "mq_index_reopen"):
+        L.mq_index_reopen.argtypes = [vp]
+        L.mq_index_resize.argtypes = [vp, u64, u32]
+        L.mq_index_load_sized.restype = vp
+        L.mq_index_load_sized.argtypes = [C.c_char_p, C.c_int, u64, u32]
+        L.mq_index_clone_sized.restype = vp
+        L.mq_index_clone_sized.argtypes = [vp, C.c_int, u64, u32]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -237,21 +245,42 @@ class Index:
             raise _err(self._L, "mq_index_save")
 
     @classmethod
-    def load(cls, path, device=0):
+    def load(cls, path, device=0, table_slots=0, factor=0):
         """A finalized index read back from Index.save (its parameters: Index.get_params(); the mapping-time ones can be replaced with
-        Index.set_map_params)."""
+        Index.set_map_params).  table_slots / factor (at most one of them, see Index.resize): the file's slots go straight into a table
+        of that size (mq_index_load_sized) instead of one of the size the file records."""
         L = load_library()
-        h = L.mq_index_load(os.fsencode(path), device)
+        if table_slots or factor:
+            h, what = L.mq_index_load_sized(os.fsencode(path), device, int(table_slots), int(factor)), "mq_index_load_sized"
+        else:
+            h, what = L.mq_index_load(os.fsencode(path), device), "mq_index_load"
         if not h:
-            raise _err(L, "mq_index_load")
+            raise _err(L, what)
         return cls(None, device, _handle=h)
 
-    def clone(self, device):
-        """A replica of this finalized index on another device (device-to-device copy, no re-indexing)."""
-        h = self._L.mq_index_clone(self._h, device)
+    def clone(self, device, table_slots=0, factor=0):
+        """A replica of this finalized index on another device (device-to-device copy, no re-indexing).  table_slots / factor (at most
+        one of them, see Index.resize): the replica's table gets that size, and only the occupied slots cross the link
+        (mq_index_clone_sized)."""
+        if table_slots or factor:
+            h, what = self._L.mq_index_clone_sized(self._h, device, int(table_slots), int(factor)), "mq_index_clone_sized"
+        else:
+            h, what = self._L.mq_index_clone(self._h, device), "mq_index_clone"
         if not h:
-            raise _err(self._L, "mq_index_clone")
+            raise _err(self._L, what)
         return Index(self.params, device, _handle=h)
+
+    def reopen(self):
+        """A finalized index takes add_ref* again (ids distinct from the ones it has); finalize() then inserts the new references into
+        the existing table.  Until then the mapping calls fail as on any index that is not finalized."""
+        if self._L.mq_index_reopen(self._h) != 0:
+            raise _err(self._L, "mq_index_reopen")
+
+    def resize(self, table_slots=0, factor=0):
+        """The finalized index's table rebuilt on the device at another size: table_slots exactly (a power of two above n_keys), or what
+        a build of this index's k-min-mers gets at `factor` slots each (2..64).  At most one of the two; neither: nothing happens."""
+        if self._L.mq_index_resize(self._h, int(table_slots), int(factor)) != 0:
+            raise _err(self._L, "mq_index_resize")
 
     def close(self):
         if getattr(self, "_h", None):

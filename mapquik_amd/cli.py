@@ -103,6 +103,11 @@ def build_parser():
                     "reference re-indexes the FASTA on every run, src/closures.rs:24-94)")
     ap.add_argument("--index", dest="load_index", help="map against a saved index instead of indexing --reference; same -k -l -d --nohpc as it was "
                     "built with (extension)")
+    ap.add_argument("--add-reference", dest="add_reference", help="with --index: add this FASTA's records to the loaded index (ids continue behind "
+                    "its largest id), then map; --save-index writes the extended index.  The table grows, when it has to, by --table-factor "
+                    "(default: the library's 8, whatever factor the file was saved at) (extension)")
+    ap.add_argument("--table-factor", type=int, dest="table_factor", help="index table slots per k-min-mer, 2..64 (library default 8); with --index "
+                    "the loaded table gets that size (extension)")
     ap.add_argument("--seeding-variant", type=int, default=0, dest="seeding_variant",
                     help="reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = the frozen "
                          "reading (extension; tools/check_against_upstream.sh finds the value that reproduces the crate)")
@@ -123,7 +128,7 @@ def banner_lines(opt):
     ref_fasta = is_fasta_name(opt.reference) if opt.reference else False
     if reads_fasta:
         out += ["Input file: %s" % opt.reads, "Format: FASTA"]
-    if ref_fasta and not getattr(opt, "load_index", None):
+    if ref_fasta and (not getattr(opt, "load_index", None) or getattr(opt, "add_reference", None)):
         out += ["Reference file: %s" % opt.reference, "Format: FASTA"]
     if opt.k is not None: k = opt.k
     else: out.append("Warning: Using default k value (%d)." % k)
@@ -157,13 +162,20 @@ def banner_lines(opt):
 
 def main(argv=None):
     start = time.time()
-    opt = build_parser().parse_args(argv)
+    ap = build_parser()
+    opt = ap.parse_args(argv)
+    if opt.add_reference and (not opt.load_index or opt.reference):
+        ap.error("--add-reference adds to the index given with --index (and excludes --reference)")  # exit status 2
+    if opt.table_factor is not None and not 2 <= opt.table_factor <= 64:
+        ap.error("--table-factor wants 2..64")
+    if opt.add_reference:
+        opt.reference = opt.add_reference  # from here on the file is this run's reference file
     if not opt.reads:
         raise SystemExit("Please specify an input file.")
     if not opt.reference and not opt.load_index:
         raise SystemExit("Please specify a reference file.")
-    if opt.load_index and opt.save_index:
-        raise SystemExit("error: --index cannot be combined with --save-index")
+    if opt.load_index and opt.save_index and not opt.add_reference:
+        raise SystemExit("error: --index cannot be combined with --save-index (unless --add-reference extends it)")
     lines, st = banner_lines(opt)
     for ln in lines:
         print(ln)
@@ -178,7 +190,7 @@ def main(argv=None):
 
     t0 = time.time()
     if opt.load_index:
-        index = api.Index.load(opt.load_index, device=opt.device)
+        index = api.Index.load(opt.load_index, device=opt.device, factor=opt.table_factor or 0)
         fp = index.get_params()
         if (fp.k, fp.l, fp.density, fp.use_hpc, fp.seeding_variant, fp.fast_kh) != (params.k, params.l, params.density, params.use_hpc, params.seeding_variant,
                                                                                      params.fast_kh):
@@ -189,9 +201,23 @@ def main(argv=None):
         ist = index.stats()
         print("Loaded index %s: %d references, %d k-min-mers." % (opt.load_index, ist["n_refs"], ist["n_kminmers"]))
         unique = ist["n_unique"]
-    else:
+    first_id = 0
+    if opt.add_reference:  # the loaded index takes references again, under ids behind every id it has
+        seen = 0
+        while seen < ist["n_refs"]:
+            try:
+                index.ref_info(first_id)
+                seen += 1
+            except api.MapquikError:
+                pass
+            first_id += 1
+        index.reopen()
+    elif not opt.load_index:
         index = api.Index(params, device=opt.device)
-        for ref_idx, (name, seq) in enumerate(read_fastx(opt.reference, st["ref_fasta"])):
+    if opt.add_reference or not opt.load_index:
+        if opt.table_factor is not None:
+            index.set_table_factor(opt.table_factor)
+        for ref_idx, (name, seq) in enumerate(read_fastx(opt.reference, st["ref_fasta"]), first_id):
             n = index.add_ref(ref_idx, name, np.frombuffer(seq, dtype=np.uint8))
             print("Indexed reference %s: %d k-min-mers." % (name, n))  # src/closures.rs:58
         unique = index.finalize()

@@ -82,6 +82,7 @@ class Index {
 
   private:
     friend class ReadOnlyIndex;
+    Index(mq_index *h, const Params &params) : h_(h), params_(params) {}  // (ReadOnlyIndex::reopen)
     mq_index *h_ = nullptr;
     Params params_;
 };
@@ -94,18 +95,30 @@ class ReadOnlyIndex {
     ~ReadOnlyIndex() { mq_index_free(h_); }
     mq_index *handle() const { return h_; }
     uint64_t unique_count() const { return unique_; }
-    static ReadOnlyIndex load(const std::string &path, int device = 0) {
-        mq_index *h = mq_index_load(path.c_str(), device);
+    // table_slots / slots_per_kminmer (at most one of them non-zero; include/mapquik_hip.h): the table's size, whatever the file records
+    static ReadOnlyIndex load(const std::string &path, int device = 0, uint64_t table_slots = 0, uint32_t slots_per_kminmer = 0) {
+        mq_index *h = table_slots || slots_per_kminmer ? mq_index_load_sized(path.c_str(), device, table_slots, slots_per_kminmer) : mq_index_load(path.c_str(), device);
         if (!h) throw Error("ReadOnlyIndex::load: " + last_error());
         mq_index_stats st;
         mq_index_get_stats(h, &st);
         return ReadOnlyIndex(h, st.n_unique);
     }
-    // a replica on another device (device-to-device copy of the table)
-    ReadOnlyIndex clone_to(int device) const {
-        mq_index *h = mq_index_clone(h_, device);
+    // a replica on another device (device-to-device copy of the table; with a size, of its occupied slots into a table of that size)
+    ReadOnlyIndex clone_to(int device, uint64_t table_slots = 0, uint32_t slots_per_kminmer = 0) const {
+        mq_index *h = table_slots || slots_per_kminmer ? mq_index_clone_sized(h_, device, table_slots, slots_per_kminmer) : mq_index_clone(h_, device);
         if (!h) throw Error("ReadOnlyIndex::clone_to: " + last_error());
         return ReadOnlyIndex(h, unique_);
+    }
+    // the table rebuilt on the device at another size
+    void resize(uint64_t table_slots, uint32_t slots_per_kminmer = 0) {
+        if (mq_index_resize(h_, table_slots, slots_per_kminmer) != MQ_OK) throw Error("ReadOnlyIndex::resize: " + last_error());
+    }
+    // back to an Index that takes references (mq_index_reopen): into_read_only() then inserts the new ones into the existing table
+    Index reopen(const Params &params) && {
+        if (mq_index_reopen(h_) != MQ_OK) throw Error("ReadOnlyIndex::reopen: " + last_error());
+        mq_index *h = h_;
+        h_ = nullptr;
+        return Index(h, params);
     }
     void save(const std::string &path) const {
         if (mq_index_save(h_, path.c_str()) != MQ_OK) throw Error("ReadOnlyIndex::save: " + last_error());

@@ -122,6 +122,8 @@ struct Opt {
     bool reads_join_device = false;  // --reads-join device: a line-wrapped reads FASTA goes to the device unparsed too, its records found and joined there
     bool last_pass = true;  // no second pass follows this one
     int table_factor = 2;  // table slots per inserted k-min-mer: this driver is bound by its host side (mq_index_set_table_factor)
+    bool table_factor_given = false;  // --table-factor on the command line: only then is a loaded index's table given another size
+    std::string add_reference;  // --add-reference (with --index): a FASTA whose records are added to the loaded index; `reference` holds it too, so it takes the routes of --reference
     std::string save_index, load_index;  // --save-index / --index: the on-disk index (the reference has none and re-indexes on every run)
     std::string second;  // "k2,l2,d2"
     long k2 = 0, l2 = 0;
@@ -138,7 +140,7 @@ static void usage() {
          "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with)\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -164,11 +166,12 @@ struct RefPhase {
     int n_parse;                    // host threads
     const std::function<void()> &start_feed;  // starts the read feeder (once)
     bool prefetch;                  // MQ_DRIVER_PREFETCH: the read feeder starts while the reference is still being indexed
+    size_t &first_id;               // id of the file's first record (0; --add-reference: behind the loaded index's largest id)
 };
 
 // --index: the finalized table from a file written by --save-index (occupied slots only; validated against its header on load)
-static std::unique_ptr<ReadOnlyIndex> load_index_file(const Opt &o, const Params &P, int device) {
-    std::unique_ptr<ReadOnlyIndex> loaded(new ReadOnlyIndex(ReadOnlyIndex::load(o.load_index, device)));
+static std::unique_ptr<ReadOnlyIndex> load_index_file(const Opt &o, const Params &P, int device, bool announce = true) {
+    std::unique_ptr<ReadOnlyIndex> loaded(new ReadOnlyIndex(ReadOnlyIndex::load(o.load_index, device, 0, o.table_factor_given ? (uint32_t)o.table_factor : 0u)));
     mq_params fp;
     if (mq_index_get_params(loaded->handle(), &fp) != MQ_OK) throw Error("mq_index_get_params: " + last_error());
     const mq_params want = P.to_abi();
@@ -186,7 +189,7 @@ static std::unique_ptr<ReadOnlyIndex> load_index_file(const Opt &o, const Params
     if (mq_index_set_map_params(loaded->handle(), want.c, want.s, want.g, (want.flags & MQ_FLAG_FOLD_CASE) ? 1 : 0) != MQ_OK) throw Error("mq_index_set_map_params: " + last_error());
     mq_index_stats st;
     mq_index_get_stats(loaded->handle(), &st);
-    printf("Loaded index %s: %llu references, %llu k-min-mers.\n", o.load_index.c_str(), (unsigned long long)st.n_refs, (unsigned long long)st.n_kminmers);
+    if (announce) printf("Loaded index %s: %llu references, %llu k-min-mers.\n", o.load_index.c_str(), (unsigned long long)st.n_refs, (unsigned long long)st.n_kminmers);
     tl("index file loaded");
     return loaded;
 }
@@ -214,8 +217,9 @@ static feeder::RefStreamer::Result stream_reference(const RefPhase &rp) {
     std::vector<std::string> lines;  // printed once the file's shape is known to be regular (else the loader below prints its own)
     const feeder::RefStreamer::Result res = rs.run([&](size_t k, const std::string &id, uint64_t at, uint64_t len) {
         const auto tr0 = Clock::now();
-        const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
-                                     : mq_index_add_ref_staged(h, (uint32_t)k, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
+        const uint32_t rid = (uint32_t)(rp.first_id + k);
+        const int64_t cnt = join_dev ? mq_index_add_ref_staged_lines(h, rid, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED, nullptr)
+                                     : mq_index_add_ref_staged(h, rid, id.c_str(), at, len, MQ_STAGE_ALL_ISSUED);  // index_mers, src/closures.rs:46-51
         if (cnt < 0) throw Error("ref_extract: " + last_error());
         if (g_knobs.timing && join_dev) fprintf(stderr, "[+%.3f s] reference record %zu: %llu bytes handed over, ref_extract returned after %.3f ms\n", secs(g_t_main), k, (unsigned long long)len, secs(tr0) * 1e3);
         lines.push_back("Indexed reference " + id + ": " + std::to_string(cnt) + " k-min-mers.");  // src/closures.rs:58
@@ -280,13 +284,13 @@ static void load_reference_whole(const RefPhase &rp, feeder::RefLoader &rl, bool
                 printf("Indexed reference %s: %lld k-min-mers.\n", j.id.c_str(), (long long)cnt);  // src/closures.rs:58
             }
         });
-    size_t ref_idx = 0;
+    size_t ref_idx = rp.first_id;
     std::string ferr;
     uint64_t last_ticket = 0;
     bool any_ticket = false;
     try {
         rl.for_each([&](const feeder::RefLoader::Record &r, const uint8_t *seq) {
-            if (ref_idx == 0) tl("first reference record ready");
+            if (ref_idx == rp.first_id) tl("first reference record ready");
             if (rp.prefetch) rp.start_feed();  // the whole file has been read by now: the host threads are free
             if (staged) {
                 uint64_t t = 0;
@@ -332,7 +336,7 @@ static void feed_reference_chunked(const RefPhase &rp, bool ref_fasta) {
                          [](void *q) { free(q); }, [](void *, size_t) { return 0; }, [](void *) { return 0; });
     rfeed.start();
     std::map<size_t, Chunk *> held;
-    size_t next = 0, ref_idx = 0;
+    size_t next = 0, ref_idx = rp.first_id;
     std::string name;
     auto flush = [&]() {
         for (auto it = held.find(next); it != held.end(); it = held.find(next)) {
@@ -461,8 +465,9 @@ static Routes describe_routes(const Opt &o, const std::string &reads_path, bool 
     rt.ref_fasta = ref_fasta;
     rt.ref_plain = ref_fasta && !ends_with(o.reference, ".gz") && !ends_with(o.reference, ".lz4");
     rt.ref_preload = g_knobs.ref_preload && !o.low_memory;
-    rt.preload_now = rt.ref_plain && o.load_index.empty() && (rt.ref_preload || g_knobs.ref_host);
-    rt.stream_ref = rt.ref_plain && o.load_index.empty() && !rt.ref_preload && !g_knobs.ref_host;
+    const bool indexes = o.load_index.empty() || !o.add_reference.empty();  // reference records are indexed in this run
+    rt.preload_now = rt.ref_plain && indexes && (rt.ref_preload || g_knobs.ref_host);
+    rt.stream_ref = rt.ref_plain && indexes && !rt.ref_preload && !g_knobs.ref_host;
     rt.on_device = !g_knobs.host_parse && (reads_fasta || g_knobs.fastq_device);
     rt.fx_format = !reads_fasta ? MQ_FASTX_FASTQ : o.reads_join_device ? MQ_FASTX_FASTA_LINES : MQ_FASTX_FASTA;
     return rt;
@@ -528,8 +533,23 @@ static std::unique_ptr<Index> new_index(const Opt &o, const Params &P, int devic
     return index;
 }
 
+// --add-reference: the loaded index opened again (mq_index_reopen); the table grows, if it has to, by this run's factor.  *first_id: the
+// smallest id behind every id the file has (a file of this driver's has 0 .. n_refs - 1; any other is searched id by id).
+static std::unique_ptr<Index> reopen_index_file(const Opt &o, const Params &P, int device, size_t *first_id, bool announce) {
+    std::unique_ptr<ReadOnlyIndex> loaded = load_index_file(o, P, device, announce);
+    mq_index_stats st;
+    mq_index_get_stats(loaded->handle(), &st);
+    size_t next = 0;
+    for (uint64_t seen = 0; seen < st.n_refs; ++next)
+        if (mq_index_ref_info(loaded->handle(), (uint32_t)next, nullptr, nullptr) == MQ_OK) ++seen;
+    *first_id = next;
+    std::unique_ptr<Index> index(new Index(std::move(*loaded).reopen(P)));
+    index->table_factor((uint32_t)o.table_factor);
+    return index;
+}
+
 static void reserve_table(const Opt &o, const Params &P, bool ref_plain, Index &index) {
-    if (!ref_plain || g_knobs.no_reserve) return;
+    if (!ref_plain || g_knobs.no_reserve || !o.add_reference.empty()) return;  // (a reopened index keeps its table)
     // Index::new sizes its map before the first insert (src/index.rs:83: with_capacity(39,821,990), CHM13 at the defaults); here the
     // expected count follows from the reference's size: canonical selection keeps 1 - (1 - d)^2 of the l-mers, homopolymer
     // compression about three quarters of the bases.  The table is allocated in the background while the reference is read and seeded.
@@ -546,11 +566,15 @@ static void reserve_table(const Opt &o, const Params &P, bool ref_plain, Index &
 static void build_or_load_index(const RefPhase &rp, const Routes &rt, int device, std::unique_ptr<feeder::RefLoader> &preload,
                                 std::unique_ptr<ReadOnlyIndex> &loaded, StreamSlots &slots, EarlySetup &early) {
     const Opt &o = rp.o;
-    if (!o.load_index.empty()) {
+    if (!o.load_index.empty() && o.add_reference.empty()) {
         loaded = load_index_file(o, rp.P, device);
         return;
     }
-    rp.index = new_index(o, rp.P, device);
+    // --add-reference: the loaded index, reopened, takes the place of a new one; the file's records follow by the route of --reference.
+    // (again: the rare file the streamer gives back after records were indexed -- those cannot be taken out of a table, so the index
+    // file is read once more, without its log line)
+    auto open_index = [&](bool again) { return o.add_reference.empty() ? new_index(o, rp.P, device) : reopen_index_file(o, rp.P, device, &rp.first_id, !again); };
+    rp.index = open_index(false);
     tl("Index::new returned (HIP runtime up, device chosen)");
     if (rt.stream_ref || (preload && !g_knobs.ref_host)) {
         // the device's staging buffer of the reference FIRST: device allocations queue behind each other, and this one (the file's
@@ -573,7 +597,7 @@ static void build_or_load_index(const RefPhase &rp, const Routes &rt, int device
                 early.join();  // the slots set up so far belong to the index that goes away
                 slots.drop();
                 rp.index.reset();
-                rp.index = new_index(o, rp.P, device);
+                rp.index = open_index(true);
                 index_replaced = true;
                 reserve_table(o, rp.P, rt.ref_plain, *rp.index);
             }
@@ -688,7 +712,8 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
     StreamSlots slots((size_t)(o.gpus * n_sub), rt.batch_bases, feed.bytes_in());
     const int n_buffers = g_knobs.prefetch ? 0 : rt.n_parse + N_SLOTS;  // chunk buffers page-locked ahead of the feeder's start
     EarlySetup early(slots, feed, n_sub, n_buffers);
-    build_or_load_index(RefPhase{o, P, building, rt.n_parse, start_feed, g_knobs.prefetch}, rt, dev.of(0), preload, ro[0], slots, early);
+    size_t first_ref_id = 0;
+    build_or_load_index(RefPhase{o, P, building, rt.n_parse, start_feed, g_knobs.prefetch, first_ref_id}, rt, dev.of(0), preload, ro[0], slots, early);
     tl("every reference record handed to ref_extract");
     finalise_save_clone(o, dev, building, ro);
     finish_slots_and_pool(early, slots, ro, feed, n_buffers);
@@ -745,6 +770,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpus") o.gpus = std::max(1, atoi(val()));
         else if (a == "--batch-bases") o.batch_bases = strtoull(val(), nullptr, 10);
         else if (a == "--table-factor") {
+            o.table_factor_given = true;
             o.table_factor = atoi(val());
             if (o.table_factor < 2 || o.table_factor > 64) { fprintf(stderr, "error: --table-factor wants 2..64\n"); return 2; }
         }
@@ -760,6 +786,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--save-index") o.save_index = val();
         else if (a == "--index") o.load_index = val();
+        else if (a == "--add-reference") o.add_reference = val();
         else if (a == "--seeding-variant") {
             o.seeding_variant = atoi(val());
             if (o.seeding_variant < 0 || o.seeding_variant > 63) { fprintf(stderr, "error: --seeding-variant wants 0..63 (bits 1 2 4 8 16 32)\n"); return 2; }
@@ -776,10 +803,15 @@ int main(int argc, char **argv) {
         else if (!a.empty() && a[0] == '-') { fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", a.c_str()); return 2; }
         else o.reads = a;
     }
+    if (!o.add_reference.empty() && (o.load_index.empty() || !o.reference.empty())) {
+        fprintf(stderr, "error: --add-reference adds to the index given with --index (and excludes --reference)\n");
+        return 2;
+    }
+    if (!o.add_reference.empty()) o.reference = o.add_reference;  // from here on the file is this run's reference file: same routes, same log lines
     if (o.reads.empty()) { fprintf(stderr, "Please specify an input file.\n"); return 101; }          // panic!, src/main.rs:191
     if (o.reference.empty() && o.load_index.empty()) { fprintf(stderr, "Please specify a reference file.\n"); return 101; }   // src/main.rs:192
-    if (!o.load_index.empty() && (!o.save_index.empty() || !o.second.empty())) {
-        fprintf(stderr, "error: --index cannot be combined with --save-index or --second-pass (a second pass builds its own index)\n");
+    if (!o.load_index.empty() && ((!o.save_index.empty() && o.add_reference.empty()) || !o.second.empty())) {
+        fprintf(stderr, "error: --index cannot be combined with --save-index (unless --add-reference extends it) or --second-pass (a second pass builds its own index)\n");
         return 2;
     }
 
@@ -787,7 +819,7 @@ int main(int argc, char **argv) {
     size_t threads = 8;
     const bool reads_fasta = is_fasta_name(o.reads), ref_fasta = is_fasta_name(o.reference);
     if (reads_fasta) printf("Input file: %s\nFormat: FASTA\n", o.reads.c_str());
-    if (ref_fasta && o.load_index.empty()) printf("Reference file: %s\nFormat: FASTA\n", o.reference.c_str());
+    if (ref_fasta && (o.load_index.empty() || !o.add_reference.empty())) printf("Reference file: %s\nFormat: FASTA\n", o.reference.c_str());
     if (o.k >= 0) P.k = (size_t)o.k; else printf("Warning: Using default k value (%zu).\n", P.k);
     if (o.l >= 0) P.l = (size_t)o.l; else printf("Warning: Using default l value (%zu).\n", P.l);
     if (o.b >= 0) P.b = (size_t)o.b; else printf("Warning: Using default buffer size (%zuX).\n", P.b);

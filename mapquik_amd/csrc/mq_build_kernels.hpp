@@ -324,6 +324,55 @@ __global__ void unpack_slots_kernel(const SavedSlot *__restrict__ in, uint64_t n
     }
 }
 
+// mq_index_resize, and the growth of a reopened index at mq_index_finalize: every occupied slot of one table into another (zeroed) table
+// of any legal size on the same device -- table to table in one pass, no packed array in between and no host round trip.  Peak memory is
+// the old table plus the new one; the old one goes once the new one's counts have been checked against the index's (acc: [0] keys
+// claimed, [1] of them dead, as insert_kernel counts).
+// The source is read as a stream: consecutive lanes take consecutive slots -- a lane pair shares a 64-byte bucket (both fetch its 16 key
+// bytes as the probe does, each its own way's payload; `claims` decides for the extra bucket), 2 KB per wave and load.  A lane issues
+// the loads of RETABLE_AHEAD slots, 64 slots apart, before it inserts the first of them: the insert side is a chain of dependent random
+// HBM accesses (CAS, then the payload), so the first insert needs its own slot's loads alone while the loads of the slots behind it are
+// on their way.  The loop is written so that the compiler can wait per counter, and the code as built today does: a counted
+// s_waitcnt vmcnt(n) in front of each slot's first use (10, 9, 8, 6 ... outstanding), except in the one wave that holds the extra
+// bucket's lane, which loads `claims` again and drains.  A CAS's own result comes back behind the loads (memory operations return in
+// order), so from the second insert on they have arrived.  A slot arrives as it was: the payload, ENTRY_DUP (as
+// `times`: table_insert sets the bit again, for an entry born dead with end == 0 too), the key 0 in the extra bucket's way 0.
+constexpr uint32_t RETABLE_AHEAD = 4;
+__global__ __launch_bounds__(256) void retable_kernel(const Bucket *__restrict__ src, uint64_t n_buckets_plus1, Bucket *__restrict__ dst, uint64_t dst_mask,
+                                                      unsigned long long *__restrict__ acc) {
+    uint32_t n_claimed = 0, n_dead = 0;
+    const uint64_t n = 2 * n_buckets_plus1;  // slots of the source, the extra bucket's two included (>= 4)
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x * RETABLE_AHEAD;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) * RETABLE_AHEAD + (threadIdx.x & 63u); i0 < n; i0 += step) {
+        uint4 kk[RETABLE_AHEAD];
+        Entry e[RETABLE_AHEAD];
+        uint32_t claims[RETABLE_AHEAD];
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {  // (a slot past the end reads the last one again: no branch around a load)
+            const uint64_t i = i0 + 64u * u < n ? i0 + 64u * u : n - 1;
+            const Bucket &B = src[i >> 1];
+            kk[u] = ld_u4(B.key);
+            e[u] = B.pay[i & 1u];
+            claims[u] = B.claims;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {
+            const uint64_t i = i0 + 64u * u;
+            const uint32_t w = (uint32_t)i & 1u;
+            const bool extra = (i >> 1) == n_buckets_plus1 - 1;
+            const unsigned long long key = extra ? 0ull : w ? u64_of(kk[u].z, kk[u].w) : u64_of(kk[u].x, kk[u].y);
+            const bool occupied = i < n && (extra ? (w == 0 && claims[u] != 0) : key != 0);
+            if (occupied) {
+                Entry x = e[u];
+                const uint32_t times = (x.id_rc & ENTRY_DUP) ? 2u : 1u;
+                x.id_rc &= ~ENTRY_DUP;
+                table_insert(dst, dst_mask, key, x, times, n_claimed, n_dead);
+            }
+        }
+    }
+    flush_insert_counts(n_claimed, n_dead, acc);
+}
+
 __global__ void lookup_kernel(const Bucket *__restrict__ table, uint64_t mask, const uint64_t *__restrict__ keys, uint32_t n,
                               uint8_t *__restrict__ found, mq_kminmer *__restrict__ entries, uint32_t *__restrict__ ref_ids) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

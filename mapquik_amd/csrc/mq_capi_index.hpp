@@ -68,9 +68,14 @@ void mq_index_free(mq_index *idx) { delete idx; }
 
 // ---- mq_index_add_ref_device in steps (all on the null stream: the next call's kernels, and finalize, are ordered behind them)
 
+// A reopened index whose finalize failed after its first insert launch: the table holds some of the new keys, the counts none of them,
+// and inserting the chunks again would turn every new live key dead.  (A fresh build's retry gets a new table; an extension has none.)
+static const char *const EXTEND_FAILED = "a finalize of this reopened index failed part way: the table is no longer exact, free the index";
+
 // what every mq_index_add_ref* refuses before anything is registered or overwritten
 static int check_new_ref(const mq_index *idx, uint32_t ref_id, uint64_t len) {
     if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
+    if (idx->extend_failed) return set_err(MQ_ESTATE, EXTEND_FAILED);
     if (len >= (1ull << 32)) return set_err(MQ_EINVAL, "sequence length must be < 2^32");
     if (ref_id >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, "ref_id must be < 2^24 (reference lengths are kept in a dense device array)");
     if (idx->refs.count(ref_id)) return set_err(MQ_EINVAL, "duplicate ref_id");
@@ -318,6 +323,31 @@ int64_t mq_index_staged_sequence(mq_index *idx, uint64_t at, uint64_t bytes, uin
     });
 }
 
+}  // extern "C"
+
+// The index's table at another size (mq_index_resize; a reopened index that outgrew it): a cleared table of nslots slots, retable_kernel
+// from the old one into it, and the old one freed -- once the new one holds what the index says it holds; until then the index is as it
+// was.  Peak device memory: both tables.  Everything runs on the null stream, behind the clearing; the counters' read-back is the wait.
+static int retable(mq_index *idx, uint64_t nslots) {
+    Buf<Bucket> table;
+    Buf<unsigned long long> d_acc;
+    int rc;
+    if ((rc = new_table(table, nslots)) || (rc = d_acc.alloc(2))) return rc;
+    HIPCHK(hipMemsetAsync(d_acc, 0, 16, 0));
+    const uint64_t nb1 = idx->nslots / 2 + 1;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((2 * nb1 + 256 * RETABLE_AHEAD - 1) / (256 * RETABLE_AHEAD), 1u << 16);
+    if ((rc = launch(retable_kernel, grid, 256, 0, idx->table, nb1, table, nslots - 1, d_acc))) return rc;
+    unsigned long long acc[2] = {0, 0};
+    HIPCHK(hipMemcpy(acc, d_acc, 16, hipMemcpyDeviceToHost));
+    if (acc[0] != idx->n_keys || acc[0] - acc[1] != idx->n_unique)
+        return set_err(MQ_ESTATE, "the table holds other keys than the index records (internal error): the table keeps its size");
+    idx->table = std::move(table);
+    idx->nslots = nslots;
+    return MQ_OK;
+}
+
+extern "C" {
+
 // Slots of the table per inserted k-min-mer (rounded up to a power of two of slots).  The default, 8 (load <= 1/8: 17 GB for a human
 // genome), is for a kernel fed from HBM: 1130 Gbases/s against 1114 / 1074 at 4 / 2.  A caller that feeds from files is bound by its
 // host side at a thirtieth of that and does better with 2: a quarter of the memory per replica, of the device-to-device copy per clone,
@@ -354,6 +384,7 @@ int64_t mq_index_finalize(mq_index *idx) {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
         if (idx->finalized) return (int64_t)idx->n_unique;
+        if (idx->extend_failed) return set_err(MQ_ESTATE, EXTEND_FAILED);
         int rc = use_device(idx);
         if (rc) return rc;
         const bool timing = env_set("MQ_BUILD_TIMING");  // diagnostic: where the wall time of finalize goes (stderr)
@@ -366,8 +397,18 @@ int64_t mq_index_finalize(mq_index *idx) {
         // the HBM).  ~85 % of a read's lookups miss, a miss walks to the first empty slot, and every extra step is one more dependent
         // random access of a memory system that sustains ~52 G of them per second (tools/probe_rate.py).  Measured on the CHM13-like
         // bench: factor 2: 926, 4: 1000, 8: 1034, 16: 1044, 32: 1051 Gbases/s.
-        const uint64_t nslots = table_slots_for(idx, idx->n_kmm_total);
-        if (Buf<Bucket> reserved = idx->rsv.take(nslots)) {  // the table mq_index_reserve allocated and cleared
+        uint64_t nslots = table_slots_for(idx, idx->n_kmm_total);
+        if (idx->extending) {
+            // a reopened index: the table holds the earlier references' keys and only the new chunks are inserted -- table_insert does
+            // not care in which order, or in how many launches, the k-min-mers of all references arrive.  It grows first when all of
+            // them together ask for a larger table than it has, and never shrinks.  (A reservation made while it was open is not used.)
+            (void)idx->rsv.take(0);
+            if (nslots > idx->nslots) {
+                if ((rc = retable(idx, nslots))) return rc;
+            } else {
+                nslots = idx->nslots;
+            }
+        } else if (Buf<Bucket> reserved = idx->rsv.take(nslots)) {  // the table mq_index_reserve allocated and cleared
             idx->table = std::move(reserved);
             idx->nslots = nslots;
             idx->table_alloc_ms = idx->rsv.ms;
@@ -378,18 +419,23 @@ int64_t mq_index_finalize(mq_index *idx) {
         Buf<unsigned long long> d_acc;
         if ((rc = d_acc.alloc(3))) return rc;
         HIPCHK(hipMemset(d_acc, 0, 24));
+        // (until here a failure leaves a reopened index as it was, open, with its chunks: finalize may be called again.  From the first
+        // insert launch to the end it may not: see EXTEND_FAILED)
+        idx->extend_failed = idx->extending;
         for (auto &c : idx->chunks) {
             if (!c.n) continue;
             const uint32_t nb = (uint32_t)std::min<uint64_t>((c.n + 255) / 256, 1u << 20);
             if ((rc = launch(insert_kernel, nb, 256, 0, c.d, c.n, idx->table, nslots - 1, d_acc))) return rc;
         }
         auto t_2 = tnow();
-        // Index::get_count (src/index.rs:90-92): keys claimed minus keys that turned dead, counted by the insertions themselves
+        // Index::get_count (src/index.rs:90-92): keys claimed minus keys that turned dead, counted by the insertions themselves.  On top
+        // of an earlier finalize's counts: a new reference that repeats an old live key claims nothing and turns one dead.
         unsigned long long acc[3] = {0, 0, 0};
         HIPCHK(hipMemcpy(acc, d_acc, 24, hipMemcpyDeviceToHost));
         d_acc.reset();
-        idx->n_keys = acc[0];
-        idx->n_unique = acc[0] - acc[1];
+        if (!idx->extending) idx->n_keys = idx->n_unique = 0;
+        idx->n_keys += acc[0];
+        idx->n_unique += acc[0] - acc[1];
         auto t_3 = tnow();
         idx->chunks.clear();
         free_build_scratch(idx);
@@ -401,7 +447,39 @@ int64_t mq_index_finalize(mq_index *idx) {
         }
         if ((rc = upload_ref_lens(idx))) return rc;
         idx->finalized = true;
+        idx->extending = idx->extend_failed = false;
         return (int64_t)idx->n_unique;
+    });
+}
+
+// A finalized index opened again for mq_index_add_ref*: see mq_index_finalize.  The device is idle when this returns, so no launch queued
+// on any context reads the table while it changes; until the next finalize the mapping entry points answer MQ_ESTATE.
+int mq_index_reopen(mq_index *idx) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (!idx->finalized) return set_err(MQ_ESTATE, "mq_index_reopen: index not finalized");
+        int rc = use_device(idx);
+        if (rc) return rc;
+        HIPCHK(hipDeviceSynchronize());
+        idx->finalized = false;
+        idx->extending = true;
+        return MQ_OK;
+    });
+}
+
+int mq_index_resize(mq_index *idx, uint64_t table_slots, uint32_t slots_per_kminmer) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
+        uint64_t nslots = 0;
+        int rc = sized_table_slots(table_slots, slots_per_kminmer, idx->n_kmm_total, idx->n_keys, &nslots);
+        if (rc) return rc;
+        if (!nslots || nslots == idx->nslots) return MQ_OK;
+        if ((rc = use_device(idx))) return rc;
+        HIPCHK(hipDeviceSynchronize());  // launches queued on the contexts read the table that is about to go
+        return retable(idx, nslots);
     });
 }
 

@@ -73,10 +73,11 @@ struct JoinedThreads {
 // The table and the dense length array, then the file's slots into the table: file -> page-locked buffer -> device -> scatter kernel,
 // by a few threads at once (each its own buffers and stream; the kernels of different chunks insert into the same table with atomics):
 // the file read, not the copy, is what takes time.  Leaves the file behind the last slot.  d_flags is the caller's, to free.
-static const char *scatter_slots(int fd, const IxHeader &h, mq_index *idx, Buf<uint32_t> &d_flags) {
+// nslots: the table's size -- the header's, or the one mq_index_load_sized asks for (no table of the header's size is made then).
+static const char *scatter_slots(int fd, const IxHeader &h, uint64_t nslots, mq_index *idx, Buf<uint32_t> &d_flags) {
     // the dense length array goes up BEFORE the scatter: a reference of length 0 cannot own a k-min-mer, so a zero in it marks an
     // id the file's (possibly sparse) reference table does not have, and the scatter refuses an entry that names one
-    if (alloc_table(idx, h.w[IX_NSLOTS]) != MQ_OK || upload_ref_lens(idx) != MQ_OK) return IX_TRUNCATED;
+    if (alloc_table(idx, nslots) != MQ_OK || upload_ref_lens(idx) != MQ_OK) return IX_TRUNCATED;
     const size_t total = (size_t)h.w[IX_N_KEYS] * sizeof(SavedSlot);
     if (!total) return nullptr;
     const off_t slots_at = ::lseek(fd, 0, SEEK_CUR);
@@ -107,7 +108,7 @@ static const char *scatter_slots(int fd, const IxHeader &h, mq_index *idx, Buf<u
             }
             const uint64_t ns = n / sizeof(SavedSlot);
             good = got == n && hipMemcpyAsync(d, hb, n, hipMemcpyHostToDevice, st) == hipSuccess &&
-                   launch(unpack_slots_kernel, (uint32_t)std::min<uint64_t>((ns + 255) / 256, 1u << 16), 256, st, (const SavedSlot *)d.p, ns, idx->table, h.w[IX_NSLOTS] - 1, max_id,
+                   launch(unpack_slots_kernel, (uint32_t)std::min<uint64_t>((ns + 255) / 256, 1u << 16), 256, st, (const SavedSlot *)d.p, ns, idx->table, nslots - 1, max_id,
                           (const uint64_t *)idx->d_ref_lens.p, d_flags) == MQ_OK &&
                    hipStreamSynchronize(st) == hipSuccess;
         }
@@ -127,13 +128,76 @@ static const char *scatter_slots(int fd, const IxHeader &h, mq_index *idx, Buf<u
 static const char *verify_counts(const IxHeader &h, mq_index *idx) {
     Buf<unsigned long long> d_acc;
     unsigned long long acc[3] = {0, 0, 0};
-    const uint64_t nb1 = h.w[IX_NSLOTS] / 2 + 1;
+    const uint64_t nb1 = idx->nslots / 2 + 1;
     if (d_acc.try_alloc(3) != hipSuccess || hipMemset(d_acc, 0, 24) != hipSuccess || launch(count_kernel, bucket_walk_grid(nb1), 256, 0, idx->table, nb1, d_acc) != MQ_OK ||
         hipMemcpy(acc, d_acc, 24, hipMemcpyDeviceToHost) != hipSuccess)
         return IX_TRUNCATED;
     if (acc[1] != h.w[IX_N_KEYS] || acc[0] != h.w[IX_N_UNIQUE] || (acc[2] != 0 && acc[2] - 1 > max_ref_id(idx)))
         return "corrupt index file (key counts or reference ids disagree with its header): ";
     return nullptr;
+}
+
+// the occupied slots of a finalized index's table, packed on its device (which the caller has selected): n_keys of them in d_pack
+static int pack_table(const mq_index *idx, const char *who, Buf<SavedSlot> &d_pack) {
+    const uint64_t n_occ = idx->n_keys;
+    Buf<unsigned long long> d_cur;
+    if (d_pack.try_alloc(n_occ + 1) != hipSuccess || d_cur.try_alloc(1) != hipSuccess || hipMemset(d_cur, 0, 8) != hipSuccess)
+        return set_err(MQ_ENOMEM, std::string(who) + ": no device memory for the packed slots");
+    const uint64_t nb1 = idx->nslots / 2 + 1;
+    unsigned long long packed = 0;
+    if (launch(pack_slots_kernel, bucket_walk_grid(nb1), 256, 0, idx->table, nb1, d_pack, d_cur, n_occ) != MQ_OK || hipMemcpy(&packed, d_cur, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(MQ_EHIP, std::string(who) + ": packing the table failed");
+    if (packed != n_occ) return set_err(MQ_ESTATE, std::string(who) + ": the table holds another number of keys than the index records (internal error)");
+    return MQ_OK;
+}
+
+// the dense reference lengths of src on dst's device (one length per reference id up to the largest: upload_ref_lens)
+static bool clone_ref_lens(const mq_index *src, mq_index *dst) {
+    const size_t nl = src->d_ref_lens.cap;
+    return hipSetDevice(dst->device) == hipSuccess && dst->d_ref_lens.try_alloc(nl) == hipSuccess &&
+           hipMemcpyPeer(dst->d_ref_lens, dst->device, src->d_ref_lens, src->device, nl * sizeof(uint64_t)) == hipSuccess;
+}
+
+// mq_index_load / mq_index_load_sized.  The size arguments are refused for their form before the file is opened, and for the file's key
+// count right behind the header's own checks: before an index or a table exists.
+static mq_index *load_index(const char *path, int device, uint64_t table_slots, uint32_t slots_per_kminmer) {
+    return guarded([&]() -> mq_index * {
+        if (!path) {
+            set_err(MQ_EINVAL, "path is NULL");
+            return nullptr;
+        }
+        uint64_t nslots = 0;
+        if (sized_table_slots(table_slots, slots_per_kminmer, 0, 0, &nslots) != MQ_OK) return nullptr;
+        ScopedFd fd(::open(path, O_RDONLY));
+        if (fd < 0) {
+            set_err(MQ_EINVAL, std::string("cannot open: ") + path);
+            return nullptr;
+        }
+        IxHeader h;
+        const char *why = read_header(fd, &h);
+        if (!why && sized_table_slots(table_slots, slots_per_kminmer, h.w[IX_N_KMM], h.w[IX_N_KEYS], &nslots) != MQ_OK) return nullptr;
+        if (!nslots) nslots = h.w[IX_NSLOTS];
+        IndexPtr idx;
+        Buf<uint32_t> d_flags;  // the scatter's error flags (declared behind idx: freed before the index, on a refusal too)
+        if (!why) {
+            idx.reset(mq_index_new(&h.p, device));
+            if (!idx) return nullptr;
+            why = read_refs(fd, h.w[IX_N_REFS], idx.get());
+        }
+        if (!why) why = scatter_slots(fd, h, nslots, idx.get(), d_flags);
+        uint8_t extra = 0;
+        if (!why && ::read(fd, &extra, 1) != 0) why = "corrupt index file (bytes after the last slot): ";
+        if (!why) why = verify_counts(h, idx.get());
+        if (why) {
+            set_err(MQ_EINVAL, std::string(why) + path);
+            return nullptr;
+        }
+        idx->n_kmm_total = h.w[IX_N_KMM];
+        idx->n_keys = h.w[IX_N_KEYS];
+        idx->n_unique = h.w[IX_N_UNIQUE];
+        idx->finalized = true;
+        return idx.release();
+    });
 }
 
 extern "C" {
@@ -147,17 +211,10 @@ int mq_index_save(const mq_index *idx, const char *path) {
         // occupied slots, packed on the device
         const uint64_t n_occ = idx->n_keys;
         Buf<SavedSlot> d_pack;
-        Buf<unsigned long long> d_cur;
         PinnedBuf<uint8_t> h_buf[2];
         ScopedStream st;
         ScopedEvent ev[2];
-        if (d_pack.try_alloc(n_occ + 1) != hipSuccess || d_cur.try_alloc(1) != hipSuccess || hipMemset(d_cur, 0, 8) != hipSuccess)
-            return set_err(MQ_ENOMEM, "mq_index_save: no device memory for the packed slots");
-        const uint64_t nb1 = idx->nslots / 2 + 1;
-        unsigned long long packed = 0;
-        if (launch(pack_slots_kernel, bucket_walk_grid(nb1), 256, 0, idx->table, nb1, d_pack, d_cur, n_occ) != MQ_OK || hipMemcpy(&packed, d_cur, 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return set_err(MQ_EHIP, "mq_index_save: packing the table failed");
-        if (packed != n_occ) return set_err(MQ_ESTATE, "mq_index_save: the table holds another number of keys than the index records (internal error)");
+        if ((rc = pack_table(idx, "mq_index_save", d_pack))) return rc;
         ScopedFd fd(::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644));
         if (fd < 0) return set_err(MQ_EINVAL, std::string("cannot open for writing: ") + path);
         bool ok = write_all(fd, MQ_INDEX_MAGIC, 8);
@@ -193,40 +250,11 @@ int mq_index_save(const mq_index *idx, const char *path) {
     });
 }
 
-mq_index *mq_index_load(const char *path, int device) {
-    return guarded([&]() -> mq_index * {
-        if (!path) {
-            set_err(MQ_EINVAL, "path is NULL");
-            return nullptr;
-        }
-        ScopedFd fd(::open(path, O_RDONLY));
-        if (fd < 0) {
-            set_err(MQ_EINVAL, std::string("cannot open: ") + path);
-            return nullptr;
-        }
-        IxHeader h;
-        const char *why = read_header(fd, &h);
-        IndexPtr idx;
-        Buf<uint32_t> d_flags;  // the scatter's error flags (declared behind idx: freed before the index, on a refusal too)
-        if (!why) {
-            idx.reset(mq_index_new(&h.p, device));
-            if (!idx) return nullptr;
-            why = read_refs(fd, h.w[IX_N_REFS], idx.get());
-        }
-        if (!why) why = scatter_slots(fd, h, idx.get(), d_flags);
-        uint8_t extra = 0;
-        if (!why && ::read(fd, &extra, 1) != 0) why = "corrupt index file (bytes after the last slot): ";
-        if (!why) why = verify_counts(h, idx.get());
-        if (why) {
-            set_err(MQ_EINVAL, std::string(why) + path);
-            return nullptr;
-        }
-        idx->n_kmm_total = h.w[IX_N_KMM];
-        idx->n_keys = h.w[IX_N_KEYS];
-        idx->n_unique = h.w[IX_N_UNIQUE];
-        idx->finalized = true;
-        return idx.release();
-    });
+mq_index *mq_index_load(const char *path, int device) { return load_index(path, device, 0, 0); }
+
+// mq_index_load into a table of the caller's size (sized_table_slots): the file's slots are scattered straight into it.
+mq_index *mq_index_load_sized(const char *path, int device, uint64_t table_slots, uint32_t slots_per_kminmer) {
+    return load_index(path, device, table_slots, slots_per_kminmer);
 }
 
 // A replica of a finalized index on another device: the table travels device to device (xGMI between the GPUs of a node)
@@ -249,12 +277,58 @@ mq_index *mq_index_clone(const mq_index *src, int device) {
         idx->n_unique = src->n_unique;
         bool ok = alloc_table(idx.get(), src->nslots) == MQ_OK;
         if (ok) ok = hipMemcpyPeer(idx->table, device, src->table, src->device, table_bytes_of(src->nslots)) == hipSuccess;
-        const size_t nl = src->d_ref_lens.cap;  // (one length per reference id up to the largest: upload_ref_lens)
-        if (ok) ok = hipSetDevice(device) == hipSuccess && idx->d_ref_lens.try_alloc(nl) == hipSuccess;
-        if (ok) ok = hipMemcpyPeer(idx->d_ref_lens, device, src->d_ref_lens, src->device, nl * sizeof(uint64_t)) == hipSuccess;
+        if (ok) ok = clone_ref_lens(src, idx.get());
         if (ok) ok = hipDeviceSynchronize() == hipSuccess;
         if (!ok) {
             set_err(MQ_EHIP, "mq_index_clone: device-to-device copy failed");
+            return nullptr;
+        }
+        idx->finalized = true;
+        return idx.release();
+    });
+}
+
+// mq_index_clone with a table of the caller's size on the destination: the occupied slots are packed on the source device, the packed
+// array (32 bytes per key) crosses the link, and the destination scatters it into a fresh table -- the table itself never travels.
+mq_index *mq_index_clone_sized(const mq_index *src, int device, uint64_t table_slots, uint32_t slots_per_kminmer) {
+    if (src && !table_slots && !slots_per_kminmer) return mq_index_clone(src, device);
+    return guarded([&]() -> mq_index * {
+        if (!src) {
+            set_err(MQ_EINVAL, "src is NULL");
+            return nullptr;
+        }
+        if (!src->finalized) {
+            set_err(MQ_ESTATE, "index not finalized");
+            return nullptr;
+        }
+        uint64_t nslots = 0;
+        if (sized_table_slots(table_slots, slots_per_kminmer, src->n_kmm_total, src->n_keys, &nslots) != MQ_OK) return nullptr;
+        Buf<SavedSlot> d_pack;
+        if (use_device(src) != MQ_OK || pack_table(src, "mq_index_clone_sized", d_pack) != MQ_OK) return nullptr;
+        IndexPtr idx(mq_index_new(&src->params, device));  // (selects the destination device)
+        if (!idx) return nullptr;
+        idx->refs = src->refs;
+        idx->n_kmm_total = src->n_kmm_total;
+        idx->n_keys = src->n_keys;
+        idx->n_unique = src->n_unique;
+        const uint64_t n = src->n_keys;
+        Buf<SavedSlot> d_in;
+        Buf<uint32_t> d_flags;
+        uint32_t flags = 1;
+        bool ok = alloc_table(idx.get(), nslots) == MQ_OK && clone_ref_lens(src, idx.get()) && d_in.try_alloc(n + 1) == hipSuccess && d_flags.try_alloc(1) == hipSuccess &&
+                  hipMemset(d_flags, 0, 4) == hipSuccess;
+        if (ok && n) ok = hipMemcpyPeer(d_in, device, d_pack, src->device, n * sizeof(SavedSlot)) == hipSuccess;
+        if (ok && n)
+            ok = launch(unpack_slots_kernel, (uint32_t)std::min<uint64_t>((n + 255) / 256, 1u << 16), 256, 0, (const SavedSlot *)d_in.p, n, idx->table, nslots - 1, max_ref_id(idx.get()),
+                        (const uint64_t *)idx->d_ref_lens.p, d_flags) == MQ_OK;
+        if (ok) ok = hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok) ok = hipDeviceSynchronize() == hipSuccess;
+        if (!ok) {
+            set_err(MQ_EHIP, "mq_index_clone_sized: device-to-device copy failed");
+            return nullptr;
+        }
+        if (flags) {
+            set_err(MQ_ESTATE, "mq_index_clone_sized: the source table holds a slot that names no reference of the index (internal error)");
             return nullptr;
         }
         idx->finalized = true;

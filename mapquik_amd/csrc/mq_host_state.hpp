@@ -284,6 +284,8 @@ struct mq_index {
     std::map<uint32_t, std::pair<std::string, uint64_t>> refs;
     uint64_t n_kmm_total = 0;
     bool finalized = false;
+    bool extending = false;     // mq_index_reopen: the table holds the keys of an earlier finalize, the next one inserts into it
+    bool extend_failed = false; // a finalize of a reopened index failed with part of the new keys in the table: no retry could be exact
     uint32_t table_factor = 0;  // mq_index_set_table_factor: slots per inserted k-min-mer (0: the default, 8)
     uint64_t nslots = 0;
     uint64_t n_unique = 0, n_keys = 0;
@@ -316,13 +318,41 @@ struct mq_index {
     }
 };
 
-// slots of the table for n inserted k-min-mers: MQ_TABLE_FACTOR (default 8: load <= 0.125) times n, rounded up to a power of two
+constexpr uint64_t MQ_MAX_TABLE_SLOTS = 1ull << 40;
+// slots of the table for n inserted k-min-mers at `factor` slots each, rounded up to a power of two (a count that no table could hold,
+// a corrupt file's for one, gives twice the largest table: refused where it is used)
+static uint64_t table_slots_at(uint64_t factor, uint64_t n_kmm) {
+    const uint64_t want = n_kmm > MQ_MAX_TABLE_SLOTS ? 2 * MQ_MAX_TABLE_SLOTS : factor * n_kmm;
+    uint64_t nslots = 1024;
+    while (nslots < want && nslots <= MQ_MAX_TABLE_SLOTS) nslots <<= 1;
+    return nslots;
+}
+// ... at the index's own factor: MQ_TABLE_FACTOR (default 8: load <= 0.125)
 static uint64_t table_slots_for(const mq_index *idx, uint64_t n_kmm) {
     const int lf = env_int("MQ_TABLE_FACTOR", 0);  // (test / experiment hook: overrides the caller's choice)
     const uint64_t factor = lf >= 2 ? (uint64_t)lf : idx->table_factor ? (uint64_t)idx->table_factor : 8ull;  // >= 2: a full table would make a miss walk forever
-    uint64_t nslots = 1024;
-    while (nslots < factor * n_kmm) nslots <<= 1;
-    return nslots;
+    return table_slots_at(factor, n_kmm);
+}
+
+// The size arguments of mq_index_resize / mq_index_load_sized / mq_index_clone_sized for an index of n_kmm inserted k-min-mers and n_keys
+// distinct keys; *out: the table's slots, 0 when both arguments are 0 ("as it is").  An exact size must leave an empty slot (a table
+// without one would make a miss walk forever: read_header's rule); a factor gives table_slots_at's size, raised to the smallest legal one.
+static int sized_table_slots(uint64_t table_slots, uint32_t slots_per_kminmer, uint64_t n_kmm, uint64_t n_keys, uint64_t *out) {
+    *out = 0;
+    if (table_slots && slots_per_kminmer) return set_err(MQ_EINVAL, "table size: table_slots or slots_per_kminmer, not both");
+    if (table_slots) {
+        if (table_slots < 2 || (table_slots & (table_slots - 1)) != 0 || table_slots > MQ_MAX_TABLE_SLOTS)
+            return set_err(MQ_EINVAL, "table_slots: a power of two in [2, 2^40]");
+        if (table_slots <= n_keys) return set_err(MQ_EINVAL, "table_slots: more slots than the index has keys (a table needs an empty slot)");
+        *out = table_slots;
+    } else if (slots_per_kminmer) {
+        if (slots_per_kminmer < 2 || slots_per_kminmer > 64) return set_err(MQ_EINVAL, "slots per k-min-mer: 2..64");
+        uint64_t s = table_slots_at(slots_per_kminmer, n_kmm);
+        while (s <= n_keys && s <= MQ_MAX_TABLE_SLOTS) s <<= 1;
+        if (s > MQ_MAX_TABLE_SLOTS) return set_err(MQ_EINVAL, "slots per k-min-mer: the table would pass 2^40 slots");
+        *out = s;
+    }
+    return MQ_OK;
 }
 
 extern "C" {
@@ -415,12 +445,18 @@ static int use_device(const mq_index *idx) {
 // workgroups (of 256 threads) of a kernel that walks the table's nb1 buckets, two slots each
 static uint32_t bucket_walk_grid(uint64_t nb1) { return (uint32_t)std::min<uint64_t>((2 * nb1 + 255) / 256, 1u << 16); }
 
+// a table of nslots slots, its clearing queued on the null stream: kernels launched there afterwards find it zeroed without a wait
+static int new_table(Buf<Bucket> &table, uint64_t nslots) {
+    int rc = table.alloc(table_bytes_of(nslots) / sizeof(Bucket));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(table, 0, table_bytes_of(nslots), 0));
+    return MQ_OK;
+}
 static int alloc_table(mq_index *idx, uint64_t nslots) {
     if (nslots < 2) nslots = 2;  // whole buckets
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = idx->table.alloc(table_bytes_of(nslots) / sizeof(Bucket));
+    int rc = new_table(idx->table, nslots);
     if (rc) return rc;
-    HIPCHK(hipMemset(idx->table, 0, table_bytes_of(nslots)));
     HIPCHK(hipDeviceSynchronize());
     idx->table_alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     idx->nslots = nslots;
