@@ -54,6 +54,14 @@ class DevBuf:
     __del__ = free
 
 
+def copy_in(buf, at, array):
+    """the bytes of a numpy array to buf.ptr + at (blocking); the range lies inside the DevBuf"""
+    a = np.ascontiguousarray(array)
+    assert 0 <= int(at) and int(at) + a.nbytes <= buf.nbytes, (int(at), a.nbytes, buf.nbytes)
+    if a.nbytes:
+        assert hip().hipMemcpy(buf.ptr + int(at), a.ctypes.data, a.nbytes, 1) == 0
+
+
 def memset(buf, byte):
     """every byte of a DevBuf set to `byte` (blocking)"""
     assert hip().hipMemset(buf.ptr, int(byte), buf.nbytes) == 0
