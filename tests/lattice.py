@@ -8,27 +8,27 @@ A point is (name, sequence bytes).  Every constructor is deterministic; one that
 import numpy as np
 
 # ---- the sizes the lattice is about (all compile-time constants of the kernels; kept by hand, the headers are not parsed)
-WORD = 16                      # mq_seed.hpp: load_piece, 16 raw bases per piece
-BLOCK = 64                     # mq_seed.hpp:227  one lane's 64-base block
+WORD = 16                      # mq_seed.hpp:165  load_piece, 16 raw bases per piece
+BLOCK = 64                     # mq_seed.hpp:31   one lane's 64-base block (SD_BLOCKS, mq_seed.hpp:37)
 SD_SR_RAW = 4096               # mq_seed.hpp:31   raw bases per super-row
 SD_TILE_RAW = 12288            # mq_seed.hpp:36   raw bases per tile (the carry into the next one: l - 1 compressed bases)
 SD_STEPS_FLAG = 32             # mq_seed.hpp stage B: one flag word per 32 steps
 SD_STEPS_GROUP = 64            # mq_seed.hpp stage B: straight-line groups of 64 steps
-SD_OWNER_CAP = 256             # mq_seed.hpp:45   stage R: candidates listed per round
-GEN_LANE_BYTES = 16            # mq_seed_general.hpp:131 general seeder: 16 bytes per lane
-GEN_STEP = 1024                # mq_seed_general.hpp:131 one step of the general seeder's walk
+SD_OWNER_CAP = 256             # mq_seed.hpp:54   stage R: candidates listed per round
+GEN_LANE_BYTES = 16            # mq_seed_general.hpp:145 general seeder: 16 bytes per lane
+GEN_STEP = 1024                # mq_seed_general.hpp:146 one step of the general seeder's walk
 GEN_AHEAD = 2                  # mq_seed_general.hpp:138 steps in flight behind the current one
 GEN_RING = 512                 # mq_seed_general.hpp:14  ring entries per wave
 GEN_HASH_HEADS = 64            # mq_seed_general.hpp     hashing per 64 run heads
-HYB_MIN_CLEAN = 2048           # mq_map_kernels.hpp:177 clean stretch of a declined read the fast seeder takes (whole 64-byte blocks)
-LANE_BATCH = 64                # mq_map_kernels.hpp:369 k-min-mers of one lane-batch
-ML_NB = 6                      # mq_map_kernels.hpp:367 lane-batches per chunk: a chunk is 64 * ML_NB + k - 1 minimizers, overlap k - 1
+HYB_MIN_CLEAN = 2048           # mq_map_kernels.hpp:188 clean stretch of a declined read the fast seeder takes (whole 64-byte blocks)
+LANE_BATCH = 64                # mq_map_kernels.hpp:383 k-min-mers of one lane-batch
+ML_NB = 6                      # mq_map_kernels.hpp:382 lane-batches per chunk: a chunk is 64 * ML_NB + k - 1 minimizers, overlap k - 1
 CHUNK_KMM = LANE_BATCH * ML_NB  # 384 k-min-mers per chunk
 MAP_LDS_RECS = 48              # mq_probe.hpp:48   Match records kept in LDS
-CHAIN_CH = 64                  # mq_chain.hpp      chain chunk
+CHAIN_CH = 64                  # mq_chain.hpp:57   chain chunk (the CH of map_pair<CH, ...>, mq_host_state.hpp:473; MQ_CHAIN_CHUNK=4: 4)
 REF_HALO = 2048                # mq_build_kernels.hpp:12
 REF_SEG = 2 * SD_TILE_RAW - REF_HALO  # mq_build_kernels.hpp:13  22528
-LIST_SLACK = 64                # mq_host_state.hpp:285 list region of a read: len * f + LIST_SLACK
+LIST_SLACK = 64                # mq_host_state.hpp:579 list region of a read: (len * f16 >> 16) + LIST_SLACK (list_region, mq_map_kernels.hpp:125)
 
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 _COMP = np.zeros(256, dtype=np.uint8)
@@ -96,14 +96,15 @@ def length_offsets(l):
     return sorted(d)
 
 
-def length_lattice(l, bases=A_BASES):
-    """the lengths B + d of family A, negative ones dropped"""
-    return sorted({B + d for B in bases for d in length_offsets(l) if B + d >= 0})
+def length_lattice(l, bases=A_BASES, offsets=None):
+    """the lengths B + d of family A, negative ones dropped (offsets: the d, length_offsets(l) unless given)"""
+    ds = length_offsets(l) if offsets is None else offsets
+    return sorted({B + d for B in bases for d in ds if B + d >= 0})
 
 
-def raw_length_points(g, l, bases=A_BASES, seed=1):
+def raw_length_points(g, l, bases=A_BASES, seed=1, offsets=None):
     rng = np.random.default_rng(seed * 1000 + l)
-    return [("len=%d" % n, _cut(g, rng, n)) for n in length_lattice(l, bases)]
+    return [("len=%d" % n, _cut(g, rng, n)) for n in length_lattice(l, bases, offsets)]
 
 
 # ------------------------------------------------------------------ B: homopolymer runs on the borders
@@ -308,7 +309,8 @@ E_RUNS = (1, 2, MAP_LDS_RECS - 1, MAP_LDS_RECS, MAP_LDS_RECS + 1, CHAIN_CH - 1, 
 
 def hit_mask(O, ox, seq, po):
     """for every k-min-mer of the read: is its hash in the oracle index (oracle.Index.get)"""
-    return np.array([ox.get(int(h)) is not None for h in kminmers_or_none(O, seq, po)["hash"]], dtype=bool)
+    get, h = O.lib().mqo_index_get, ox.h    # (oracle.Index.get without the copy of the entry: the search asks a million times)
+    return np.array([get(h, int(x)) is not None for x in kminmers_or_none(O, seq, po)["hash"]], dtype=bool)
 
 
 def _substitutions(seq, lo, hi):
@@ -350,13 +352,15 @@ def n_matches(ox, seq, po):
     return int(ox.map_batch_diag(b, np.array([0, b.size], dtype=np.uint64), po)[1]["n_matches"][0])
 
 
-def reads_with_match_runs(O, ox, seq, po, wanted=E_RUNS):
-    """substitutions added one at a time, each kept only if it raises the oracle's Match-run count by exactly one: {M: read with M runs}"""
+def reads_with_match_runs(O, ox, seq, po, wanted=E_RUNS, from_own=False):
+    """substitutions added one at a time, each kept only if it raises the oracle's Match-run count by exactly one: {M: read with M runs}.
+    from_own: the undamaged read may have any count below min(wanted) (dense lists of short l-mers: it misses here and there without
+    any damage); the search starts from that count"""
     out = {}
     cur, m = seq, n_matches(ox, seq, po)
-    if m != 1:
+    if (m >= min(wanted)) if from_own else (m != 1):
         raise LatticeError("the undamaged read has %d Match runs" % m)
-    out[1] = cur
+    out[m] = cur
     km = kminmers_or_none(O, seq, po)
     step = po.k + 3
     at = step
@@ -373,22 +377,62 @@ def reads_with_match_runs(O, ox, seq, po, wanted=E_RUNS):
     return {w: out[w] for w in wanted}
 
 
+E_RETRIES = 4   # other stretches of the genome tried for a point that one substitution cannot make in the first
+
+
 def match_break_points(O, ox, g, ps):
-    """family E from family D's reads of two chunks and of three chunks (+ one k-min-mer), forward and reverse-complemented"""
+    """family E from family D's reads of two chunks and of three chunks (+ one k-min-mer), forward and reverse-complemented.  Where no
+    single substitution makes a point in the read (dense lists of short l-mers: the windows of neighbouring minimizers overlap, and a
+    substitution that ends one lists another), the same read cut E_RETRIES times further along the genome is tried for that point."""
     po = O.params(**ps)
     km1 = O.kminmers(g, O.params(**{**ps, "k": 1}))
-    two, _ = read_with_minimizers(O, g, ps, LANE_BATCH * 12 + po.k - 1 + 1, km1=km1)
-    three, _ = read_with_minimizers(O, g, ps, LANE_BATCH * 18 + po.k - 1 + 1, first=60, km1=km1)
+    made = {}
+
+    def read(chunks, t):
+        if (chunks, t) not in made:
+            made[(chunks, t)] = read_with_minimizers(O, g, ps, LANE_BATCH * 6 * chunks + po.k - 1 + 1, first=(50 if chunks == 2 else 60) + 100 * t, km1=km1)[0]
+        return made[(chunks, t)]
+
+    def point(make, chunks, f, *args):
+        for t in range(E_RETRIES + 1):
+            try:
+                return make(O, ox, f(read(chunks, t)), po, *args)
+            except LatticeError as e:
+                err = e
+        raise err
     pts = []
     for strand, f in (("fwd", lambda s: s), ("rc", revcomp)):
-        for chunks, read in ((2, f(two)), (3, f(three))):
+        for chunks in (2, 3):
             for j in E_BREAKS:
                 if chunks == 2 and j > CHUNK_KMM + 1:   # the breaks at the end of the second chunk are the three-chunk read's
                     continue
-                pts.append(("%s %d chunks: last hit before the break is %d" % (strand, chunks, j), break_after(O, ox, read, po, j), ("after", j)))
-                pts.append(("%s %d chunks: first hit after the break is %d" % (strand, chunks, j), break_before(O, ox, read, po, j), ("before", j)))
-        for M, s in reads_with_match_runs(O, ox, f(three), po).items():
+                pts.append(("%s %d chunks: last hit before the break is %d" % (strand, chunks, j), point(break_after, chunks, f, j), ("after", j)))
+                pts.append(("%s %d chunks: first hit after the break is %d" % (strand, chunks, j), point(break_before, chunks, f, j), ("before", j)))
+        for M, s in point(reads_with_match_runs, 3, f).items():
             pts.append(("%s: %d Match runs" % (strand, M), s, ("runs", M)))
+    return pts
+
+
+CORE_RUNS = (MAP_LDS_RECS - 1, MAP_LDS_RECS, MAP_LDS_RECS + 1, CHAIN_CH - 1, CHAIN_CH, CHAIN_CH + 1)
+
+
+def match_run_points(O, ox, g, ps, wanted=CORE_RUNS):
+    """family E's Match-run reads alone, for a parameter set whose undamaged reads do not hit at every k-min-mer: the read of three
+    chunks, forward and reverse-complemented, damaged from its own count upwards (reads_with_match_runs, from_own).  (name, sequence,
+    ("runs", M))"""
+    po = O.params(**ps)
+    km1 = O.kminmers(g, O.params(**{**ps, "k": 1}))
+    pts = []
+    for strand, f in (("fwd", lambda s: s), ("rc", revcomp)):
+        for t in range(E_RETRIES + 1):
+            try:
+                read = read_with_minimizers(O, g, ps, LANE_BATCH * 18 + po.k - 1 + 1, first=60 + 100 * t, km1=km1)[0]
+                made = reads_with_match_runs(O, ox, f(read), po, wanted, from_own=True)
+                break
+            except LatticeError as e:
+                if t == E_RETRIES:
+                    raise e
+        pts += [("%s: %d Match runs" % (strand, M), s, ("runs", M)) for M, s in made.items()]
     return pts
 
 
@@ -401,11 +445,11 @@ F_HEADS = (63, 64, 65, 511, 512, 513, 1024)
 F_PARAMS = (dict(), dict(k=3, l=12, density=0.05), dict(k=7, l=64, density=0.02))
 
 
-def general_run_points(g, seed=7):
+def general_run_points(g, seed=7, starts=F_RUN_STARTS):
     rng = np.random.default_rng(seed)
     pts = []
     for r in F_RUNS:
-        for st in F_RUN_STARTS:
+        for st in starts:
             s, _ = plant_run(g, rng, st, r, min_len=st + r + 3000)
             pts.append(("general: run of A-like r=%d at %d" % (r, st), s, (st, r)))
             sn = bytearray(s)
@@ -414,13 +458,13 @@ def general_run_points(g, seed=7):
     return pts
 
 
-def declined_stretch_points(g, seed=8):
+def declined_stretch_points(g, seed=8, ds=(-1, 0, 1)):
     """a non-ACGT byte at 192 + d, a clean stretch of c bytes behind it, another non-ACGT byte, sequence: the stretch's whole 64-byte
     blocks number 2048 / 64 or one fewer or more depending on d and c.  (name, sequence, (first clean byte, c))"""
     rng = np.random.default_rng(seed)
     pts = []
     for c in F_CLEAN:
-        for d in (-1, 0, 1):
+        for d in ds:
             a = 3 * BLOCK + d
             pts.append(("declined: N at %d, %d clean bytes" % (a, c), _cut(g, rng, a) + b"N" + _cut(g, rng, c) + b"N" + _cut(g, rng, 3000), (a + 1, c)))
     return pts
@@ -498,4 +542,188 @@ def reference_run_points(g, l, seed=11):
         c2 = _other(post[0], pre[-1])
         mid = heads(rng, hh - 1, pre[-1], c2)
         pts.append(("ref: halo with %d run heads" % hh, pre + mid + bytes([c2]) * (REF_HALO - (hh - 1) + 300) + post, ("halo", hh)))
+    return pts
+
+
+# ------------------------------------------------------------------ core: one batch per parameter set for the instantiation matrix
+CORE_A_BASES = (0, BLOCK, SD_SR_RAW, SD_TILE_RAW, 2 * SD_TILE_RAW)
+CORE_B_RUNS = (WORD - 1, WORD, WORD + 1, BLOCK - 1, BLOCK, BLOCK + 1, SD_SR_RAW - 1, SD_SR_RAW, SD_SR_RAW + 1,
+               SD_TILE_RAW - 1, SD_TILE_RAW, SD_TILE_RAW + 1)
+CORE_B_BASES = (SD_SR_RAW, SD_TILE_RAW)
+CORE_F_START = 2 * GEN_STEP      # the one run start of the core's general-seeder reads (= 0 mod 1024)
+CORE_F_D = -1                    # declined_stretch_points' d at which F_CLEAN gives 2048 - 64, 2048 and 2048 + 64 bytes in whole blocks
+
+
+def core_length_offsets(l):
+    """the d of the core's family A: the size itself, one to either side, the carry of l - 1 codes and one more"""
+    return (-1, 0, 1, -(l - 1), l - 1, l)
+
+
+def core_points(O, ox, g, ps, families="ABDEF"):
+    """A named subset of families A, B, D, E and F that hits every size of the module header exactly and one element to either side
+    (test_lattice_cases.py proves it per constant), small enough that twenty-odd kernel configurations can each map it: (name, sequence,
+    family letter).  Names are prefixed with the family, so they are unique within the batch.  D and E come forward and reverse-complemented.
+    SD_OWNER_CAP and the 32- / 64-step words of stage B are not the core's: family H (list_capacity_points) and family A's full length
+    lattice carry them.
+    families: family E's break search damages a read that hits the index at EVERY k-min-mer; at k = 3, l = 12 an error-free read of two
+    chunks already misses at a dozen of them (short l-mers, dense lists), so CORE_PARAMS gives that set "R" in E's place: the Match-run
+    reads of CORE_RUNS alone (match_run_points), counted up from the undamaged read's own number of runs."""
+    po = O.params(**ps)
+    l = int(po.l)
+    pts = []
+    if "A" in families:
+        pts += [("A " + n, s, "A") for n, s in raw_length_points(g, l, bases=CORE_A_BASES, offsets=core_length_offsets(l))]
+    if "B" in families:
+        pts += [("B " + n, s, "B") for n, s, _ in run_border_points(g, l, runs=CORE_B_RUNS, bases=CORE_B_BASES)]
+    if "D" in families:
+        d = minimizer_count_points(O, g, ps)
+        pts += [("D " + n, s, "D") for n, s in d] + [("D " + n + " rc", revcomp(s), "D") for n, s in d]
+    if "E" in families:
+        pts += [("E " + n, s, "E") for n, s, _ in match_break_points(O, ox, g, ps)]      # (both strands already)
+    if "R" in families:
+        pts += [("E " + n, s, "E") for n, s, _ in match_run_points(O, ox, g, ps)]
+    if "F" in families:
+        pts += [("F " + n, s, "F") for n, s, _ in general_run_points(g, starts=(CORE_F_START,)) + declined_stretch_points(g, ds=(CORE_F_D,))
+                + dense_step_points(g)]
+    return pts
+
+
+# the parameter sets of the matrix and the families each one's core batch holds
+CORE_PARAMS = {"default": (dict(), "ABDEF"), "k3l12": (dict(k=3, l=12, density=0.05), "ABDRF"), "k7": (dict(k=7), "ABDEF")}
+
+
+# ------------------------------------------------------------------ H: the list region's own edge
+H_F16 = 1                                   # MQ_LIST_F16=1: every read below 65,536 bases has cap = LIST_SLACK
+H_COUNTS = (LIST_SLACK - 1, LIST_SLACK, LIST_SLACK + 1, LIST_SLACK + SD_OWNER_CAP - 1, LIST_SLACK + SD_OWNER_CAP, LIST_SLACK + SD_OWNER_CAP + 1)
+H_NEIGHBOUR = 3000                          # bases of the fixed neighbour read
+H_BLOCK = 65536                             # bases per unit of a region's start at f16 = 1
+
+
+def default_f16(density):
+    """list_f16 (mq_host_state.hpp:570): list entries reserved per base, in 1 / 65536"""
+    f = min(1.0, 4.0 * max(0.0, density) + 1.0 / 512.0)
+    return int(np.ceil(f * 65536.0))
+
+
+def list_cap(length, f16):
+    """list_region's cap (mq_map_kernels.hpp:125)"""
+    return ((length * f16) >> 16) + LIST_SLACK
+
+
+def with_one_n(O, seq, po, N, tries=200):
+    """the read with ONE byte replaced by N, chosen near the middle so that the read still lists exactly N minimizers"""
+    mid = len(seq) // 2
+    for t in range(tries):
+        p = mid + t
+        if p >= len(seq):
+            break
+        s = seq[:p] + b"N" + seq[p + 1:]
+        if len(O.minimizers(s, po)) == N and len(kminmers_or_none(O, s, po)) == max(0, N - po.k + 1):
+            return s
+    raise LatticeError("no N keeps %d minimizers" % N)
+
+
+def read_at_default_cap(O, g, ps, km1, first=50, tries=40):
+    """a stretch of the genome whose minimizer count equals its own list capacity at the default f16: (sequence, N)"""
+    po = O.params(**ps)
+    f16 = default_f16(po.density)
+    for i in range(first, first + tries):
+        for N in range(LIST_SLACK + 1, LIST_SLACK + 2 * SD_OWNER_CAP):
+            if i + N >= len(km1):
+                break
+            a, b = int(km1[i]["start"]), int(km1[i + N - 1]["end"]) + 1
+            if list_cap(b - a, f16) != N:   # (the exact read may be a few bases longer: read_with_minimizers grows it, the cap is asked again)
+                continue
+            try:
+                s, _ = read_with_minimizers(O, g, ps, N, first=i, tries=1, km1=km1)
+            except LatticeError:
+                continue
+            if list_cap(len(s), f16) == N:
+                return s, N
+    raise LatticeError("no read whose minimizer count equals its default list capacity (f16 = %d) for %r" % (f16, ps))
+
+
+def list_capacity_points(O, g, ps, tries=40, default_too=True):
+    """family H: for every N of H_COUNTS a read with exactly N minimizers and the same read with one N byte (the declined / general
+    path), each followed by the fixed neighbour read, so that list regions are adjacent: (name, sequence, N or None for a neighbour).
+    default_too: one more pair whose read's count equals its own capacity at the default f16 -- LatticeError if the genome has none."""
+    po = O.params(**ps)
+    km1 = O.kminmers(g, O.params(**{**ps, "k": 1}))
+    rng = np.random.default_rng(12)
+    neighbour = _cut(g, rng, H_NEIGHBOUR)
+    pts, cur = [], 0
+
+    def pair(name, seq, N):
+        # at f16 = 1 a region starts at (offset >> 16) + LIST_SLACK * r: the neighbour's region lies directly behind the read's only if both
+        # start in the same 65,536 bases of the batch (the points are meant to open it).  A padding read moves a pair that would not.
+        nonlocal cur
+        if len(seq) >= H_BLOCK:
+            raise LatticeError("%s: %d bases do not fit one block of %d" % (name, len(seq), H_BLOCK))
+        if (cur + len(seq)) // H_BLOCK != cur // H_BLOCK:
+            fill = -cur % H_BLOCK
+            pts.append(("pad %d in front of %s" % (fill, name), _cut(g, rng, fill), "pad"))
+            cur += fill
+        pts.append((name, seq, N))
+        pts.append(("neighbour of " + name, neighbour, None))
+        cur += len(seq) + len(neighbour)
+    for N in H_COUNTS:
+        s, _ = read_with_minimizers(O, g, ps, N, tries=tries, km1=km1)
+        pair("N=%d" % N, s, N)
+        pair("N=%d with an N" % N, with_one_n(O, s, po, N), N)
+    if default_too:
+        s, N = read_at_default_cap(O, g, ps, km1, tries=tries)
+        pair("N=%d = default cap" % N, s, N)
+    return pts
+
+
+def regions_adjacent(pts, f16=H_F16):
+    """for every (read, neighbour) pair of family H at the head of a batch: does the neighbour's list region begin exactly where the
+    read's ends (list_region, mq_map_kernels.hpp:125)"""
+    _, offs = batch(pts)
+    ok = []
+    for i, p in enumerate(pts):
+        if isinstance(p[2], int):
+            o0, o1 = int(offs[i]), int(offs[i + 1])
+            base0, base1 = ((o0 * f16) >> 16) + LIST_SLACK * i, ((o1 * f16) >> 16) + LIST_SLACK * (i + 1)
+            ok.append(base1 == base0 + list_cap(len(p[1]), f16))
+    return ok
+
+
+# ------------------------------------------------------------------ I: lower case on the borders (fold_case)
+I_BYTES = (WORD - 1, WORD, WORD + 1, BLOCK - 1, BLOCK, BLOCK + 1, SD_SR_RAW - 1, SD_SR_RAW, SD_SR_RAW + 1,
+           SD_TILE_RAW - 1, SD_TILE_RAW, SD_TILE_RAW + 1)
+I_LEN = 3 * SD_TILE_RAW
+I_RUN = 64                     # the mixed-case run: bytes [12288 - 32, 12288 + 32)
+I_N_RUN = 40                   # the lower-case n run of the general seeder's points
+
+
+def _lower_at(seq, positions):
+    s = bytearray(seq)
+    for p in positions:
+        s[p] |= 0x20
+    return bytes(s)
+
+
+def fold_border_points(g, seed=13):
+    """family I: reads of three tiles whose lower-case bytes sit on the seeders' borders: (name, sequence, (lower-case positions, the
+    upper-case read it was made from)).  The oracle gets the upper-case read (the reference folds before it seeds)."""
+    rng = np.random.default_rng(seed)
+    pts = []
+    for p in I_BYTES + (0, I_LEN - 1):
+        up = _cut(g, rng, I_LEN)
+        pts.append(("lower-case byte %d" % p, _lower_at(up, [p]), ([p], up)))
+    st = SD_TILE_RAW - I_RUN // 2
+    up, _ = plant_run(g, rng, st, I_RUN)
+    odd = list(range(st, st + I_RUN, 2))
+    pts.append(("mixed-case run aAaA across %d" % SD_TILE_RAW, _lower_at(up, odd), (odd, up)))
+    for a in (GEN_STEP - 1, GEN_STEP, GEN_STEP + 1):   # general seeder: a lower-case n run
+        s = bytearray(_cut(g, rng, I_LEN))
+        s[a:a + I_N_RUN] = b"N" * I_N_RUN
+        up = bytes(s)
+        where = list(range(a, a + I_N_RUN))
+        pts.append(("lower-case n run starts at %d" % a, _lower_at(up, where), (where, up)))
+    a = 3 * BLOCK        # a stretch of HYB_MIN_CLEAN lower-case bases in whole blocks, an N on either side
+    up = _cut(g, rng, a - 1) + b"N" + _cut(g, rng, HYB_MIN_CLEAN) + b"N" + _cut(g, rng, I_LEN - a - HYB_MIN_CLEAN - 1)
+    where = list(range(a, a + HYB_MIN_CLEAN))
+    pts.append(("%d lower-case bases between two N" % HYB_MIN_CLEAN, _lower_at(up, where), (where, up)))
     return pts

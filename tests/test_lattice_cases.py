@@ -260,3 +260,155 @@ def test_family_g_references(oracle, world):
         assert n_halo == len({1, 2, po.l - 2, po.l - 1, po.l})
         total += len(pts)
     _report("G", total)
+
+
+# ------------------------------------------------------------------ the core batch of the instantiation matrix, families H and I
+def _names(pts, family):
+    return [p[0] for p in pts if p[2] == family]
+
+
+@pytest.mark.parametrize("which", sorted(L.CORE_PARAMS))
+def test_core_points_hit_every_size(oracle, world, ref_index, which):
+    """every size constant of lattice.py's header appears among core_points exactly and one element to either side: from the points' names
+    (which the family proofs above tie to the sequences) and from the oracle's minimizer, k-min-mer and Match-run counts"""
+    import time
+    g = world[0]
+    ps, families = L.CORE_PARAMS[which]
+    ox, po = ref_index(ps)
+    k, l = int(po.k), int(po.l)
+    t0 = time.perf_counter()
+    pts = L.core_points(oracle, ox, g, ps, families)
+    dt = time.perf_counter() - t0
+    assert pts == L.core_points(oracle, ox, g, ps, families)    # deterministic
+    names = [p[0] for p in pts]
+    assert len(set(names)) == len(names) and len(pts) <= 400
+    bases, offs = L.batch(pts)
+    _, diag = ox.map_batch_diag(bases, offs, po, threads=4)
+    # A: every base exactly, one to either side, and the carry of l - 1 codes (and one more) to either side of it
+    lens = {len(p[1]) for p in pts if p[2] == "A"}
+    for B in (0, L.BLOCK, L.SD_SR_RAW, L.SD_TILE_RAW, 2 * L.SD_TILE_RAW):
+        for d in (-1, 0, 1, -(l - 1), l - 1, l):
+            assert B + d < 0 or B + d in lens, (which, B, d)
+    for p in pts:
+        if p[2] == "A":
+            assert p[0] == "A len=%d" % len(p[1])
+    # B: runs of every piece / block / super-row / tile size +- 1, starting and ending on the super-row and the tile border +- 1
+    nb = set(_names(pts, "B"))
+    for c in (L.WORD, L.BLOCK, L.SD_SR_RAW, L.SD_TILE_RAW):
+        for r in (c - 1, c, c + 1):
+            for B in (L.SD_SR_RAW, L.SD_TILE_RAW):
+                for d in (-1, 0, 1):
+                    assert "B run r=%d starts at %d%+d" % (r, B, d) in nb, (which, r, B, d)
+                    assert (B + d - r < 0) != ("B run r=%d ends at %d%+d" % (r, B, d) in nb)
+    for name, s, where in L.run_border_points(g, l, runs=L.CORE_B_RUNS, bases=L.CORE_B_BASES):
+        assert where is None or L.run_is_exact(s, *where), name
+    # D: the lane-batch and the chunk with its k - 1 shared entries, by the oracle's counts, both strands
+    d_idx = [i for i, p in enumerate(pts) if p[2] == "D"]
+    n_mz = [oracle.minimizers(pts[i][1], po).size for i in d_idx]
+    n_kmm = [int(diag["n_kminmers"][i]) for i in d_idx]
+    assert sorted(n_mz) == sorted(L.minimizer_counts(k) * 2)
+    assert n_kmm == [max(0, n - k + 1) for n in n_mz]
+    for c in (L.LANE_BATCH, L.CHUNK_KMM, 2 * L.CHUNK_KMM, 3 * L.CHUNK_KMM):
+        for e in (-1, 0, 1):
+            assert n_kmm.count(c + e) == 2, (which, c, e)
+    # E: the breaks by name (test_family_e_match_run_breaks proves them for E_PARAMS; the same search here), the runs by n_matches
+    if "E" in families:
+        ne = _names(pts, "E")
+        for strand in ("fwd", "rc"):
+            for j in L.E_BREAKS:
+                assert any(n.startswith("E %s " % strand) and n.endswith("last hit before the break is %d" % j) for n in ne), (which, strand, j)
+                assert any(n.startswith("E %s " % strand) and n.endswith("first hit after the break is %d" % j) for n in ne), (which, strand, j)
+        n_breaks = 0
+        for name, s, _ in pts:   # the core's own break points, whatever the parameter set: the hit mask around j
+            if name.startswith("E ") and " break is " in name:
+                j = int(name.split()[-1])
+                m = L.hit_mask(oracle, ox, s, po)
+                assert (m[:j + 1].all() and not m[j + 1]) if "last hit before" in name else (m[j:].all() and not m[j - 1]), (which, name)
+                n_breaks += 1
+        assert n_breaks == 2 * 2 * (len(L.E_BREAKS) + sum(1 for j in L.E_BREAKS if j <= L.CHUNK_KMM + 1))
+    # the Match-run reads, in every parameter set (E's own, or match_run_points counted up from the undamaged read's runs): by n_matches
+    assert "E" in families or "R" in families
+    runs = [(p[0], int(diag["n_matches"][i])) for i, p in enumerate(pts) if p[2] == "E" and p[0].endswith("Match runs")]
+    assert all(name == "E %s: %d Match runs" % (name.split()[1].rstrip(":"), m) for name, m in runs), runs
+    assert sorted(m for _, m in runs) == sorted((L.E_RUNS if "E" in families else L.CORE_RUNS) * 2) and set(L.CORE_RUNS) <= set(L.E_RUNS)
+    for c in (L.MAP_LDS_RECS, L.CHAIN_CH):
+        for e in (-1, 0, 1):
+            assert (diag["n_matches"] == c + e).sum() >= 2, (which, c, e)
+    # F: 1-KB steps, the clean stretch in whole blocks, run heads per step around 64 and the ring's 512
+    nf = set(_names(pts, "F"))
+    for r in L.F_RUNS:
+        assert "F general: run of A-like r=%d at %d" % (r, L.CORE_F_START) in nf and "F general: run of N r=%d at %d" % (r, L.CORE_F_START) in nf
+    assert {L.GEN_STEP - 1, L.GEN_STEP, L.GEN_STEP + 1, 2 * L.GEN_STEP - 1, 2 * L.GEN_STEP, 2 * L.GEN_STEP + 1} <= set(L.F_RUNS) and L.CORE_F_START % L.GEN_STEP == 0
+    dec = L.declined_stretch_points(g, ds=(L.CORE_F_D,))
+    assert all("F " + n in nf for n, _, _ in dec) and len(dec) == len(L.F_CLEAN)
+    assert {L.clean_blocks(a, c) for _, _, (a, c) in dec} == {L.HYB_MIN_CLEAN - L.BLOCK, L.HYB_MIN_CLEAN, L.HYB_MIN_CLEAN + L.BLOCK}
+    for h in L.F_HEADS:
+        assert "F dense: %d run heads per 1-KB step" % h in nf
+    assert {L.GEN_HASH_HEADS - 1, L.GEN_HASH_HEADS, L.GEN_HASH_HEADS + 1, L.GEN_RING - 1, L.GEN_RING, L.GEN_RING + 1, L.GEN_STEP} <= set(L.F_HEADS)
+    print("core batch %s: %d points, %d bases, constructed in %.1f s" % (which, len(pts), bases.size, dt))
+
+
+@pytest.mark.parametrize("which", ["default", "k3l12"])
+def test_family_h_list_capacity(oracle, world, which):
+    """family H's reads list exactly the named counts, under the frozen reading and under the variant the matrix also runs H with (16:
+    END_COMPRESSED moves `end`, not the selection); regions are adjacent (a neighbour behind every read); the point at the default f16
+    does not exist in this genome (a region is 2.6 times the expected list)"""
+    g = world[0]
+    ps = L.CORE_PARAMS[which][0]
+    po = oracle.params(**ps)
+    with pytest.raises(L.LatticeError):
+        L.list_capacity_points(oracle, g, ps)
+    full = L.list_capacity_points(oracle, g, ps, default_too=False)
+    # every neighbour's region begins where its read's ends: both start in the same 65,536 bases of the batch (padding reads see to it)
+    assert L.regions_adjacent(full) == [True] * (2 * len(L.H_COUNTS))
+    assert which != "default" or any(p[2] == "pad" for p in full)       # (the default set's reads of 23 kb would straddle without them)
+    _, offs = L.batch(full)
+    for i, p in enumerate(full):
+        if isinstance(p[2], int):
+            assert int(offs[i]) >> 16 == int(offs[i + 1]) >> 16 and full[i + 1][2] is None, p[0]
+    pts = [p for p in full if p[2] != "pad"]
+    assert [p[2] for p in pts[0::4]] == list(L.H_COUNTS) == [p[2] for p in pts[2::4]]
+    assert L.H_COUNTS == (63, 64, 65, 319, 320, 321)
+    for i, (name, s, N) in enumerate(pts):
+        if N is None:
+            assert i % 2 == 1 and s == pts[1][1] and name == "neighbour of " + pts[i - 1][0]
+            continue
+        assert len(s) < 65536 and L.list_cap(len(s), L.H_F16) == L.LIST_SLACK      # every region is 64 entries at f16 = 1
+        assert L.list_cap(len(s), L.default_f16(po.density)) > N                   # ... and holds the list at the default
+        assert (b"N" in s) == name.endswith("with an N") and s.count(b"N") <= 1
+        for v in (0, 16):
+            oracle.lib().mqo_set_variant(v)
+            try:
+                assert oracle.minimizers(s, po).size == N and L.kminmers_or_none(oracle, s, po).size == N - po.k + 1, (which, name, v)
+            finally:
+                oracle.lib().mqo_set_variant(0)
+    assert min(p[2] for p in pts if p[2]) <= L.LIST_SLACK < max(p[2] for p in pts if p[2])
+    _report("H " + which, len(pts))
+
+
+def test_family_i_lower_case_on_the_borders(oracle, world):
+    g = world[0]
+    pts = L.fold_border_points(g)
+    seen = set()
+    for name, s, (where, up) in pts:
+        a, u = np.frombuffer(s, dtype=np.uint8), np.frombuffer(up, dtype=np.uint8)
+        assert len(s) == 3 * L.SD_TILE_RAW and s.upper() == up and set(up) <= set(b"ACGTN")
+        assert np.flatnonzero(a != u).tolist() == sorted(where), name            # the lower-case bytes sit where they are named
+        assert L.compressed_length(s.upper()) == L.compressed_length(up)          # folding gives the read back: the case changes no run
+        if name.startswith("lower-case byte"):
+            assert where == [int(name.split()[-1])]
+            seen.add(where[0])
+        elif name.startswith("mixed-case run"):
+            st, r = L.SD_TILE_RAW - L.I_RUN // 2, L.I_RUN
+            assert L.run_is_exact(up, st, r) and where == list(range(st, st + r, 2))
+            assert L.compressed_length(s) == L.compressed_length(up) + r - 1     # unfolded, every byte of the run is a run of its own
+        elif name.startswith("lower-case n run"):
+            st = int(name.split()[-1])
+            assert up[st:st + L.I_N_RUN] == b"N" * L.I_N_RUN and s[st:st + L.I_N_RUN] == b"n" * L.I_N_RUN and st - L.GEN_STEP in (-1, 0, 1)
+        else:
+            st = where[0]
+            assert len(where) == L.HYB_MIN_CLEAN == L.clean_blocks(st, len(where)) and up[st - 1] == up[st + len(where)] == ord("N")
+            assert b"N" not in up[st:st + len(where)] and s[st:st + len(where)].islower()
+    assert seen == set(L.I_BYTES) | {0, 3 * L.SD_TILE_RAW - 1}
+    assert {L.WORD, L.BLOCK, L.SD_SR_RAW, L.SD_TILE_RAW} <= seen and all({c - 1, c + 1} <= seen for c in (L.WORD, L.BLOCK, L.SD_SR_RAW, L.SD_TILE_RAW))
+    _report("I", len(pts))
