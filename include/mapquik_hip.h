@@ -114,6 +114,18 @@ typedef struct mq_hit {
     uint32_t q_end_hi;   /* column 4, high 32 bits */
 } mq_hit;
 
+/* The Match runs of a mapped read's winning pseudo-chain (opt-in: mq_ctx_reserve_anchors below) -- what Chain::filter_matches_max leaves
+ * (src/chain.rs:123-129), of which the hit keeps the first and the last.  A Match of src/match.rs as the chain holds it: raw coordinates,
+ * q_end / r_end as Match stores them (get_match subtracts 1), BEFORE find_coords; strand and reference are the hit's (every kept run has the
+ * anchor's strand or equals it field by field). */
+typedef struct mq_anchor {
+    uint32_t q_start, q_end, r_start, r_end, count;
+} mq_anchor; /* 20 bytes */
+typedef struct mq_anchor_span {
+    uint32_t first, count; /* read r's anchors: pool[first .. first + count), in read order */
+} mq_anchor_span;
+#define MQ_ANCHORS_DROPPED 0xFFFFFFFFu /* mq_anchor_span::first of a mapped read whose anchors found no room in the pool (count is still right) */
+
 typedef struct mq_index mq_index; /* opaque: Index / ReadOnlyIndex (src/index.rs:73-128) + ref_map (src/closures.rs:30) */
 
 typedef struct mq_index_stats {
@@ -350,6 +362,39 @@ int mq_ctx_reserve_redo(mq_ctx *ctx, uint32_t max_reads, uint32_t max_read_len);
 int mq_ctx_redo_counts(mq_ctx *ctx, uint32_t *redone, uint32_t *left);
 int mq_map_reserve_redo(mq_index *idx, uint32_t max_reads, uint32_t max_read_len);
 int mq_map_redo_counts(mq_index *idx, uint32_t *redone, uint32_t *left);
+
+/* The winning chain's Match runs ("anchors") with every mapped read (opt-in, per context; a context without a reservation runs exactly the
+ * kernels it always ran).  mq_ctx_reserve_anchors allocates, now, a span per read for batches of up to max_reads reads and a pool of
+ * max_anchors anchors.  From then on every map call on the context -- mq_ctx_map_batch, mq_ctx_submit / _submit_spans + mq_ctx_wait,
+ * mq_ctx_submit_fasta / _fastx + both waits, mq_ctx_map_batch_device with and without a redo arena -- takes the kernel pair that also
+ * writes, for read r of the batch, spans[r] and, for a mapped read, its anchors in read order at pool[first .. first + count): count is the
+ * number of runs of the chain, the sum of their `count` fields is the hit's score.  An unmapped, tied or too short read has span {0, 0}.
+ * A read that is redone (MQ_HIT_OVERFLOW: through the host, or in stream with a redo arena) delivers its anchors from the redo; one that
+ * leaves with MQ_HIT_OVERFLOW has span {0, 0}.  The order in which the reads' lists lie in the pool is not defined.
+ * Pool exhaustion is loud, never wrong: a read whose list found no room has first == MQ_ANCHORS_DROPPED and its count; `dropped_reads`
+ * counts them, `needed` says what the batch asked of the pool (reserve that much and map again: there is no automatic second pass), the
+ * hits are unaffected.  A batch of more than max_reads reads is refused with MQ_EINVAL before anything is queued -- except a FASTX piece,
+ * whose number of records is known only at mq_ctx_wait_fasta[_lines]: that call refuses it, before the map launch, and the piece is
+ * consumed (its copy and its scan have run).  A call that fails leaves mq_ctx_anchors describing the last batch that was launched.  The
+ * instrumented launch of mq_map_probe_stats and mq_kminmers_batch write no anchors.
+ *   (0, 0)        releases the reservation: the feature is off again
+ *   MQ_ESTATE     the context has a submitted batch
+ *   MQ_EINVAL     one of the two 0; max_reads >= 2^30; max_anchors >= 2^32 - 1; the index runs the split pipeline (MQ_PIPELINE=split)
+ *   MQ_ENOMEM     the context keeps the reservation it had (or none)
+ * Device memory: 8 max_reads + 20 max_anchors bytes (+ 4 max_reads for the redo's id map), the same again page-locked on the host.
+ * mq_ctx_anchors finishes the context's last batch (mq_ctx_wait if it was only submitted; the stream of a device-form call is waited for)
+ * and returns host copies: spans[0 .. n_reads), anchors[0 .. stored), stored = min(needed, max_anchors) -- valid until the next map call,
+ * reserve or free on the context.  MQ_ESTATE without a reservation or with a FASTX piece in flight; n_reads = 0 before the first batch.
+ * mq_ctx_anchors_device gives the device arrays themselves and waits for nothing: for mq_ctx_map_batch_device callers that stay on their
+ * stream (valid until the reservation changes).
+ * mq_map_reserve_anchors / mq_map_anchors: the same for the index's default context, as mq_map_reserve_redo. */
+int mq_ctx_reserve_anchors(mq_ctx *ctx, uint32_t max_reads, uint64_t max_anchors);
+int mq_ctx_anchors(mq_ctx *ctx, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                   uint32_t *dropped_reads);
+int mq_ctx_anchors_device(mq_ctx *ctx, const mq_anchor_span **d_spans, const mq_anchor **d_anchors);
+int mq_map_reserve_anchors(mq_index *idx, uint32_t max_reads, uint64_t max_anchors);
+int mq_map_anchors(mq_index *idx, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                   uint32_t *dropped_reads);
 
 /* Page-locked host memory for the buffers handed to mq_map_batch / mq_index_add_ref (a feeder that parses FASTX straight
  * into such buffers gets the full PCIe rate on the copy in; pageable buffers work too, at roughly a quarter of it). */

@@ -21,6 +21,11 @@ hit_dtype = np.dtype([("status", "<u4"), ("ref_id", "<u4"), ("rc", "<u4"), ("map
                       ("r_start", "<u4"), ("r_end", "<u4"), ("score", "<u4"), ("n_kminmers", "<u4"), ("q_start_hi", "<u4"), ("q_end_hi", "<u4")])
 kminmer_dtype = np.dtype([("hash", "<u8"), ("start", "<u4"), ("end", "<u4"), ("offset", "<u4"), ("rev", "<u4")])
 assert hit_dtype.itemsize == 48 and kminmer_dtype.itemsize == 24
+# mq_anchor / mq_anchor_span (Context.reserve_anchors): a Match run of the winning chain; where a read's runs lie in the anchors array
+anchor_dtype = np.dtype([("q_start", "<u4"), ("q_end", "<u4"), ("r_start", "<u4"), ("r_end", "<u4"), ("count", "<u4")])
+anchor_span_dtype = np.dtype([("first", "<u4"), ("count", "<u4")])
+MQ_ANCHORS_DROPPED = 0xFFFFFFFF
+assert anchor_dtype.itemsize == 20 and anchor_span_dtype.itemsize == 8
 
 
 def hit_column(hits, name):
@@ -38,6 +43,7 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_last_map_ms", "mq_last_map_path_counts", "mq_last_map_order", "mq_host_alloc", "mq_host_free", "mq_index_save", "mq_index_load", "mq_index_clone", "mq_map_probe_stats",
            "mq_ctx_new", "mq_ctx_free", "mq_ctx_map_batch", "mq_ctx_submit", "mq_ctx_submit_spans", "mq_ctx_wait", "mq_ctx_reserve", "mq_ctx_map_batch_device", "mq_ctx_last_map_ms", "mq_probe_rate", "mq_last_stage_clocks", "mq_last_read_cycles", "mq_map_launch_waves", "mq_index_table_alloc_ms",
            "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts",
+           "mq_ctx_reserve_anchors", "mq_ctx_anchors", "mq_ctx_anchors_device", "mq_map_reserve_anchors", "mq_map_anchors",
            "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized"]
 
 
@@ -176,6 +182,13 @@ def load_library(path=None):
         L.mq_map_reserve_redo.argtypes = [vp, u32, u32]
         L.mq_ctx_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.mq_map_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(L, "mq_ctx_reserve_anchors"):
+        pp = C.POINTER(vp)
+        L.mq_ctx_reserve_anchors.argtypes = [vp, u32, u64]
+        L.mq_map_reserve_anchors.argtypes = [vp, u32, u64]
+        L.mq_ctx_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+        L.mq_map_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+        L.mq_ctx_anchors_device.argtypes = [vp, pp, pp]
     if hasattr(L, "mq_index_reopen"):
         L.mq_index_reopen.argtypes = [vp]
         L.mq_index_resize.argtypes = [vp, u64, u32]
@@ -193,6 +206,18 @@ def load_library(path=None):
 
 def _err(L, what):
     return MapquikError("%s: %s" % (what, (L.mq_last_error() or b"").decode(errors="replace")))
+
+
+def _anchors(L, fn, what, handle):
+    """(spans, anchors, info) of mq_ctx_anchors / mq_map_anchors: numpy copies of the library's host arrays"""
+    sp, an = C.c_void_p(), C.c_void_p()
+    n, dropped = C.c_uint32(), C.c_uint32()
+    stored, needed = C.c_uint64(), C.c_uint64()
+    if fn(handle, C.byref(sp), C.byref(an), C.byref(n), C.byref(stored), C.byref(needed), C.byref(dropped)) != 0:
+        raise _err(L, what)
+    spans = np.frombuffer(C.string_at(sp.value, n.value * anchor_span_dtype.itemsize), dtype=anchor_span_dtype).copy() if n.value else np.zeros(0, dtype=anchor_span_dtype)
+    anchors = np.frombuffer(C.string_at(an.value, stored.value * anchor_dtype.itemsize), dtype=anchor_dtype).copy() if stored.value else np.zeros(0, dtype=anchor_dtype)
+    return spans, anchors, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
 
 
 class PinnedBuffer:
@@ -445,6 +470,15 @@ class Index:
             raise _err(self._L, "mq_map_redo_counts")
         return a.value, b.value
 
+    def reserve_anchors(self, max_reads, max_anchors):
+        """Context.reserve_anchors for the default context (map_batch, map_batch_device); (0, 0) releases."""
+        if self._L.mq_map_reserve_anchors(self._h, int(max_reads), int(max_anchors)) != 0:
+            raise _err(self._L, "mq_map_reserve_anchors")
+
+    def anchors(self):
+        """Context.anchors for the default context."""
+        return _anchors(self._L, self._L.mq_map_anchors, "mq_map_anchors", self._h)
+
     def context(self):
         """A stream slot (mq_ctx): own stream, scratch and staging; contexts of one finalized index may map concurrently."""
         return Context(self)
@@ -681,6 +715,24 @@ class Context:
         if self._L.mq_ctx_redo_counts(self._h, C.byref(a), C.byref(b)) != 0:
             raise _err(self._L, "mq_ctx_redo_counts")
         return a.value, b.value
+
+    def reserve_anchors(self, max_reads, max_anchors):
+        """From now on every batch of up to max_reads reads mapped on this context also delivers the Match runs of each mapped read's winning
+        chain, from a pool of max_anchors entries (include/mapquik_hip.h: mq_ctx_reserve_anchors).  (0, 0) releases."""
+        if self._L.mq_ctx_reserve_anchors(self._h, int(max_reads), int(max_anchors)) != 0:
+            raise _err(self._L, "mq_ctx_reserve_anchors")
+
+    def anchors(self):
+        """(spans, anchors, info) of the context's last batch, which it finishes: read r's runs are anchors[spans[r]["first"]:][:spans[r]["count"]]
+        in read order (first == MQ_ANCHORS_DROPPED: the pool was too small for them); info = dict(stored, needed, dropped_reads)."""
+        return _anchors(self._L, self._L.mq_ctx_anchors, "mq_ctx_anchors", self._h)
+
+    def anchors_device(self):
+        """(device pointer of the spans, device pointer of the anchors): the arrays a map_batch_device call on this context writes."""
+        sp, an = C.c_void_p(), C.c_void_p()
+        if self._L.mq_ctx_anchors_device(self._h, C.byref(sp), C.byref(an)) != 0:
+            raise _err(self._L, "mq_ctx_anchors_device")
+        return sp.value, an.value
 
     def last_map_ms(self):
         ms = C.c_float()

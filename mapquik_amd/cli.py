@@ -117,7 +117,23 @@ def build_parser():
     ap.add_argument("--unmapped", action="store_true",
                     help="also write <prefix>.unmapped.out with the ids of reads that got no PAF line (extension; the reference "
                          "has this writer commented out, src/closures.rs:38-43; feeds a second pass with other parameters)")
+    ap.add_argument("--anchors", action="store_true",
+                    help="also write <prefix>.anchors: one line per Match run of every mapped read's winning chain, reads in input order, runs in "
+                         "read order: q_id, q_start, q_end, strand, r_name, r_start, r_end, count -- raw coordinates as the chain holds them, "
+                         "before find_coords (extension; the reference's -a path, src/chain.rs:173-237, walks the same list)")
     return ap
+
+
+def anchor_lines(names, hits, spans, anchors, ref_name):
+    """the text of <prefix>.anchors for one batch; ref_name: reference id -> name"""
+    out = []
+    for nm, h, sp in zip(names, hits, spans):
+        if int(h["status"]) != api.MQ_HIT_MAPPED:
+            continue
+        strand, rn = "-" if int(h["rc"]) else "+", ref_name(int(h["ref_id"]))
+        for a in anchors[int(sp["first"]):int(sp["first"]) + int(sp["count"])].tolist():
+            out.append("%s\t%d\t%d\t%s\t%s\t%d\t%d\t%d" % (nm, a[0], a[1], strand, rn, a[2], a[3], a[4]))
+    return out
 
 
 def banner_lines(opt):
@@ -187,6 +203,7 @@ def main(argv=None):
                         seeding_variant=opt.seeding_variant, fast_kh=opt.fast_kh)
     paf = open(st["prefix"] + ".paf", "w")  # src/closures.rs:32
     unm = open(st["prefix"] + ".unmapped.out", "w") if opt.unmapped else None
+    anc = open(st["prefix"] + ".anchors", "w") if opt.anchors else None
 
     t0 = time.time()
     if opt.load_index:
@@ -237,7 +254,19 @@ def main(argv=None):
         offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
         offs[1:] = np.cumsum([len(x) for x in seqs])
         bases = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        if anc is not None:
+            # the reservation of this batch.  A read has no more Match runs than k-min-mers and fewer k-min-mers than minimizers, and the
+            # library's minimizer lists are sized at bytes x (4 density + 1/512) entries: the same bound here.  A batch that needs more
+            # (reads inside dense tandem arrays) ends the run with what it needed.
+            index.reserve_anchors(len(seqs), min(int(bases.size * (4.0 * st["density"] + 1.0 / 512.0)) + 64, (1 << 32) - 2))
         hits = index.map_batch(bases, offs)
+        if anc is not None:
+            spans, anchors, info = index.anchors()
+            if info["dropped_reads"]:
+                raise SystemExit("--anchors: the anchor pool was too small for %d reads of a batch: %d entries needed, %d reserved"
+                                 % (info["dropped_reads"], info["needed"], info["stored"]))
+            for ln in anchor_lines(names, hits, spans, anchors, lambda r: index.ref_info(r)[0]):
+                anc.write(ln + "\n")
         for ln in index.paf_lines(names, offs, hits):  # input order, unmapped reads write nothing (src/closures.rs:117-123)
             paf.write(ln + "\n")
         if unm is not None:
@@ -257,6 +286,8 @@ def main(argv=None):
     paf.close()
     if unm is not None:
         unm.close()
+    if anc is not None:
+        anc.close()
     print("Mapped query sequences in %s." % rust_duration(time.time() - t0))  # src/closures.rs:211
     print("Total execution time: %s" % rust_duration(time.time() - start))  # src/main.rs:270
     rss_gb = np.float32(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss * 1024) / np.float32(1024.0 ** 3)

@@ -39,6 +39,10 @@ struct Chunk {
     std::vector<std::pair<uint64_t, uint64_t>> regions;
     std::vector<mq_hit> hits;
     std::string paf, unmapped, unmapped_fa;  // formatted output of this chunk
+    // --anchors: the chunk's spans and anchors (copies of mq_ctx_anchors' arrays, taken when the chunk's slot was waited for) and their text
+    std::vector<mq_anchor_span> a_spans;
+    std::vector<mq_anchor> a_pool;
+    std::string anchors;
     // set by the whole-member gzip reader: the chunk's bytes still sit in a member's inflate buffer (kept alive by ext_hold);
     // the parser thread that takes the chunk copies them into buf first
     const uint8_t *ext_src = nullptr;
@@ -73,6 +77,9 @@ struct Chunk {
         paf.clear();
         unmapped.clear();
         unmapped_fa.clear();
+        a_spans.clear();
+        a_pool.clear();
+        anchors.clear();
     }
 };
 

@@ -49,15 +49,48 @@ inline bool collect_device_records(mq_ctx *ctx, feeder::Chunk &c, uint32_t fx_fo
     return false;
 }
 
+// --anchors: the spans and anchors of the batch the slot has just finished become the chunk's (the library's host copies last until the
+// slot's next submit).  A pool that was too small for the chunk ends the run, like any other pipeline failure, with what it needed.
+inline void take_anchors(mq_ctx *ctx, feeder::Chunk &c) {
+    c.a_spans.clear();
+    c.a_pool.clear();
+    if (c.hits.empty()) return;  // nothing was mapped for this chunk: the slot's last batch is somebody else's
+    const mq_anchor_span *spans = nullptr;
+    const mq_anchor *pool = nullptr;
+    uint32_t n = 0, dropped = 0;
+    uint64_t stored = 0, needed = 0;
+    if (mq_ctx_anchors(ctx, &spans, &pool, &n, &stored, &needed, &dropped) != MQ_OK) throw Error(std::string("mq_ctx_anchors: ") + last_error());
+    if (n != c.hits.size()) throw Error("mq_ctx_anchors: " + std::to_string(n) + " spans for a chunk of " + std::to_string(c.hits.size()) + " reads");
+    if (dropped)
+        throw Error("--anchors: the anchor pool of a stream slot was too small for " + std::to_string(dropped) + " reads of a chunk: " + std::to_string(needed) +
+                    " entries needed, " + std::to_string(stored) + " reserved");
+    c.a_spans.assign(spans, spans + n);
+    c.a_pool.assign(pool, pool + stored);
+}
+
 // A mapped chunk's output: PAF lines of the mapped reads (src/mers.rs:181), and of the unmapped ones the names (want_unmapped) and the
 // records as FASTA (want_fasta, for a second pass).  Returns the error text for a hit that is neither, "" else.
-inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta) {
+// want_anchors: beside a mapped read's PAF line, one line per Match run of its chain, in read order (take_anchors filled a_spans / a_pool):
+// q_id, q_start, q_end, strand, r_name, r_start, r_end, count
+inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta, bool want_anchors = false) {
     std::string id;
     c.paf.reserve(c.lens.size() * 96);
     for (size_t i = 0; i < c.lens.size(); ++i) {
         const mq_hit &h = c.hits[i];
         if (h.status == MQ_HIT_MAPPED) {
             pw.append(c.paf, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);  // src/mers.rs:181
+            if (want_anchors) {
+                if (i >= c.a_spans.size() || (uint64_t)c.a_spans[i].first + c.a_spans[i].count > c.a_pool.size()) return "--anchors: a mapped read without its anchors";
+                const std::string &rn = pw.ref_name(h.ref_id);
+                char num[128];
+                for (uint32_t j = 0; j < c.a_spans[i].count; ++j) {
+                    const mq_anchor &a = c.a_pool[(size_t)c.a_spans[i].first + j];
+                    c.anchors.append((const char *)c.buf + c.ids[i].off, c.ids[i].len);
+                    c.anchors.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%c\t", a.q_start, a.q_end, h.rc ? '-' : '+'));
+                    c.anchors += rn;
+                    c.anchors.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%u\n", a.r_start, a.r_end, a.count));
+                }
+            }
             continue;
         }
         id.assign((const char *)c.buf + c.ids[i].off, c.ids[i].len);
@@ -81,6 +114,8 @@ class MapPipeline {
         int n_format;        // PAF formatters
         uint32_t fx_format;  // MQ_FASTX_* of the chunks that come unparsed
         long fail_at;        // MQ_DRIVER_FAIL_AT (test hook): the submitter that takes this chunk number reports a failure; -1: none
+        FILE *anchors = nullptr;  // --anchors: <prefix>.anchors, written the way the unmapped names are
+        double density = 0;       // ... and what a slot's reservation is sized with (Ctx::reserve_anchors)
     };
     // slots[w]: the stream slots of submitter w (n_sub submitters per GPU, each over its GPU's index); index: where the formatters look
     // reference names up; paf, unmapped, unmapped_fa: the open output files, the last two may be null
@@ -137,6 +172,8 @@ class MapPipeline {
         }
         void submit(Chunk *c, int sl) {
             const auto ts0 = Clock::now();
+            // --anchors: the slots reserve for the feeder's chunk size when they are made; a chunk that is larger (one very long record) makes its slot reserve again
+            if (p.cfg_.anchors && c->bytes > ctx[sl].anchors_bytes()) ctx[sl].reserve_anchors(c->bytes, p.cfg_.density);
             if (c->unparsed) {
                 if (mq_ctx_submit_fastx(ctx[sl].handle(), c->buf, c->begin, c->bytes, p.cfg_.fx_format) != MQ_OK) throw Error(std::string("mq_ctx_submit_fastx: ") + last_error());
             } else if (mq_ctx_submit_spans(ctx[sl].handle(), c->buf, c->bytes, c->starts.data(), c->lens.data(), (uint32_t)c->starts.size(), c->hits.data()) != MQ_OK) {
@@ -158,6 +195,7 @@ class MapPipeline {
                 } else if (mq_ctx_wait(ctx[sl].handle()) != MQ_OK) {
                     throw Error(std::string("mq_ctx_wait: ") + last_error());
                 }
+                if (p.cfg_.anchors) take_anchors(ctx[sl].handle(), *c);
             } catch (const std::exception &e) { p.fail(e.what()); }
             c->unparsed = false;
             inflight[sl] = nullptr;
@@ -246,7 +284,7 @@ class MapPipeline {
             }
             const auto tm0 = Clock::now();
             try {
-                const std::string err = format_chunk(*c, pw, unm_ != nullptr, ufa_ != nullptr);
+                const std::string err = format_chunk(*c, pw, unm_ != nullptr, ufa_ != nullptr, cfg_.anchors != nullptr);
                 if (!err.empty()) fail(err);
             } catch (const std::exception &e) { fail(e.what()); }
             t_format_us_ += us_since(tm0);
@@ -277,6 +315,7 @@ class MapPipeline {
             if (!c->paf.empty()) fwrite(c->paf.data(), 1, c->paf.size(), paf_);
             if (unm_ && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm_);
             if (ufa_ && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa_);
+            if (cfg_.anchors && !c->anchors.empty()) fwrite(c->anchors.data(), 1, c->anchors.size(), cfg_.anchors);
             feed_.recycle(c);
             t_write_us_ += us_since(tw0);
         }

@@ -5,6 +5,7 @@
 //            . mers::find_matches (src/mers.rs:77) -> std::optional<std::string> for Option<String>.
 // Errors: the reference panics; this layer throws mapquik::Error (never across the C ABI).  No CPU compute path exists.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <optional>
 #include <stdexcept>
@@ -148,16 +149,29 @@ class Ctx {
     }
     Ctx(const Ctx &) = delete;
     Ctx &operator=(const Ctx &) = delete;
-    Ctx(Ctx &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Ctx(Ctx &&o) noexcept : h_(o.h_), anchors_bytes_(o.anchors_bytes_) { o.h_ = nullptr; }
     ~Ctx() { mq_ctx_free(h_); }
     mq_ctx *handle() const { return h_; }
     // room for batches of up to max_reads reads in max_bytes bytes, so that the first batches do not grow the slot
     void reserve(uint32_t max_reads, uint64_t max_bytes) {
         if (mq_ctx_reserve(h_, max_reads, max_bytes) != MQ_OK) throw Error("mq_ctx_reserve: " + last_error());
     }
+    // --anchors: spans and an anchor pool for chunks of up to max_bytes raw bytes.  The bounds: a record takes at least four bytes of a
+    // file (">\nA\n"), so a chunk holds at most max_bytes / 4 + 1 reads; a read has no more Match runs than k-min-mers and fewer k-min-mers
+    // than minimizers, and the library sizes its minimizer lists at bytes x (4 density + 1/512) entries -- the same number of anchors
+    // here.  A chunk that needs more (reads inside dense tandem arrays) reports dropped reads, and the run ends with what it needed.
+    void reserve_anchors(uint64_t max_bytes, double density) {
+        const uint64_t reads = std::min<uint64_t>(max_bytes / 4 + 1, (1u << 30) - 1);
+        const double f = std::min(1.0, 4.0 * (density > 0 ? density : 0.0) + 1.0 / 512.0);
+        const uint64_t anchors = std::min<uint64_t>((uint64_t)((double)max_bytes * f) + 64, 0xFFFFFFFEull - 1);
+        if (mq_ctx_reserve_anchors(h_, (uint32_t)reads, anchors) != MQ_OK) throw Error("mq_ctx_reserve_anchors: " + last_error());
+        anchors_bytes_ = max_bytes;
+    }
+    uint64_t anchors_bytes() const { return anchors_bytes_; }  // the chunk size the slot's anchor reservation was made for (0: none)
 
   private:
     mq_ctx *h_ = nullptr;
+    uint64_t anchors_bytes_ = 0;
 };
 
 // The format! of src/mers.rs:181 for many reads: the same bytes as mq_format_paf, appended to a string, with the reference names and
@@ -194,6 +208,8 @@ class PafWriter {
         *p++ = '\n';
         out.append(num, (size_t)(p - num));
     }
+
+    const std::string &ref_name(uint32_t id) { return ref(id).name; }
 
   private:
     struct Ref {

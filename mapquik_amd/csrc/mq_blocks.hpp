@@ -103,4 +103,16 @@ struct RedoCounters {
 static_assert(sizeof(RedoCounters) == 16 && offsetof(RedoCounters, claimed) == 0 && offsetof(RedoCounters, left) == 4 && offsetof(RedoCounters, spare) == 8,
               "redo counters");
 
+// ------------------------------------------------------------------ the anchor output of a batch (mq_ctx::anch_counters = MapArgs::anchor_counters)
+// cleared by the host once per BATCH, in front of its main launch sequence -- not per launch, as MapCounters is: the batch's redo launches go
+// on claiming from the same cursor.  Written by chain_stage<CH, true> (mq_chain.hpp).
+struct AnchorCounters {
+    unsigned long long cursor;  // pool entries claimed; counts on past the pool's capacity, so it ends as what the batch needed
+    uint32_t dropped_reads;     // mapped reads whose claim did not fit (span first = MQ_ANCHORS_DROPPED)
+    uint32_t spare;
+};
+static_assert(sizeof(AnchorCounters) == 16 && offsetof(AnchorCounters, cursor) == 0 && offsetof(AnchorCounters, dropped_reads) == 8 &&
+                  offsetof(AnchorCounters, spare) == 12,
+              "anchor counters");
+
 }  // namespace mq

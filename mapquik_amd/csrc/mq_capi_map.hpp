@@ -13,13 +13,35 @@ struct LaunchOpt {
     uint32_t f16 = 0;                      // 0 => list_f16(idx)
     const uint32_t *d_lens = nullptr;      // spans form: per-read lengths
     bool instrumented = false;             // mq_map_probe_stats: the launch that counts lookups and probe steps (slower, never timed)
+    // the anchor output (mq_ctx_reserve_anchors) of a batch's redo launch: the batch's cursor goes on, the spans go where the map says
+    bool anchor_redo = false;
+    const uint32_t *d_anchor_ids = nullptr;  // MapArgs::anchor_ids
+    mq_ctx *anchors_of = nullptr;            // the context whose reservation the launch delivers to (nullptr: c itself; the arena's launch: its owner)
 };
+
+// A batch of n reads on a context with an anchor reservation is refused when it has more reads than spans.  The entry points ask before
+// they queue anything (a FASTX piece: before its map launch -- the number of records is known only at the wait); launch_map asks again,
+// where the spans are about to be written.  Nothing of the context changes here: the batch becomes "the last batch" in launch_map.
+static int anchors_admit(const mq_ctx *c, uint32_t n) {
+    if (c->anch_reads && n > c->anch_reads)
+        return set_err(MQ_EINVAL, "more reads in the batch than the context's anchor reservation holds (mq_ctx_reserve_anchors: max_reads)");
+    return MQ_OK;
+}
 
 // One launch sequence on stream `st` using the context's scratch.  ctx_ensure(c, n, total_bases, f16) must have succeeded.
 static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, mq_hit *d_out, hipStream_t st,
                       const LaunchOpt &o = LaunchOpt()) {
     mq_index *idx = c->idx;
     if (n == 0) return MQ_OK;
+    // a context with an anchor reservation takes the anchors pair (never for the instrumented launch, nor for mq_kminmers_batch's)
+    mq_ctx *ac = o.anchors_of ? o.anchors_of : c;
+    const bool anch = ac->anch_reads != 0 && !o.instrumented && !o.d_dump && !idx->split;
+    if (anch && !o.anchor_redo) {
+        int rc = anchors_admit(ac, n);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(ac->anch_counters, 0, sizeof(AnchorCounters), st));  // once per batch: its redo launches claim from the same cursor
+        ac->anch_n = n;  // from here on mq_ctx_anchors describes this batch
+    }
     HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(MapCounters), st));
     HIPCHK(hipEventRecord(c->ev0, st));
     MapArgs A;
@@ -52,15 +74,21 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     A.stats64 = &c->d_counter.p->probe;
     A.work = c->work;
     A.heavy_first = idx->heavy_first ? 1u : 0u;
+    A.anchors.pool = anch ? ac->anch_pool.p : nullptr;
+    A.anchors.cap = anch ? (uint32_t)ac->anch_cap : 0u;
+    A.anchors.counters = anch ? ac->anch_counters.p : nullptr;
+    A.anchor_spans = anch ? ac->anch_spans.p : nullptr;
+    A.anchor_ids = anch ? o.d_anchor_ids : nullptr;
     if (!idx->split) {
         if (n > WORK_ID_MASK) return set_err(MQ_EINVAL, "more than 2^30 - 1 reads in one batch");
         hipLaunchKernelGGL(order_reads_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, A);  // the launch order (and map_kernel's work descriptors)
         uint32_t grid = fused_grid(idx, n);
         if (o.grid_override) grid = std::min(grid, o.grid_override);
+        if (anch) grid = std::min(grid, idx->grid_fused_anchors);
         const dim3 blk(64 * MAP_WAVES);
         // (a seeding variant other than the frozen reading takes the instantiation built with the variants; the frozen reading with the
         // parameters of a MAP_SPECS entry takes the pair compiled for them)
-        const MapPair &kp = map_pair_of(idx, o.instrumented, &c->last_spec);
+        const MapPair &kp = map_pair_of(idx, o.instrumented, &c->last_spec, anch);
         hipLaunchKernelGGL(kp.map, dim3(grid), blk, 0, st, A);
         HIPCHK(hipGetLastError());
         // the reads the fast seeder declined (queue length on the device: map_kernel's grid, its waves leave at once when there are none)
@@ -89,6 +117,10 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     }
     HIPCHK(hipEventRecord(c->ev1, st));
     c->ev_valid = true;
+    if (anch) {
+        HIPCHK(hipEventRecord(ac->anch_done, st));
+        ac->anch_ran = true;
+    }
     return MQ_OK;
 }
 
@@ -136,7 +168,12 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
         o.cap_override = cap;
         o.grid_override = rgrid;
         o.f16 = 65536u;
-        rrc = launch_map(c, d_sb, d_so, (uint32_t)redo.size(), d_sh, c->stream, o);
+        if (c->anch_reads) {  // a read that is redone delivers its anchors from the redo: same pool, same cursor, its span to the batch's read number
+            e = hipMemcpyAsync(c->anch_ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            o.anchor_redo = true;
+            o.d_anchor_ids = c->anch_ids;
+        }
+        if (e == hipSuccess) rrc = launch_map(c, d_sb, d_so, (uint32_t)redo.size(), d_sh, c->stream, o);
     }
     if (e == hipSuccess && rrc == MQ_OK) e = hipMemcpyAsync(sh.data(), d_sh, redo.size() * sizeof(mq_hit), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -205,6 +242,7 @@ static int ctx_submit(mq_ctx *c, const uint8_t *bases, uint64_t buf_bytes, const
     int rc = ctx_require_idle(c);
     if (rc) return rc;
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
+    if ((rc = anchors_admit(c, n))) return rc;
     if (n == 0) return MQ_OK;
     if ((rc = use_device(idx))) return rc;
     if ((rc = c->h_off.ensure((uint64_t)n + 1))) return rc;  // (ahead of the rest: the offsets are checked into it)
@@ -306,6 +344,8 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     int rc;
     HIPCHK(hipMemsetAsync(a.counters, 0, sizeof(RedoCounters), st));
     HIPCHK(hipMemsetAsync(a.lens, 0, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims is a read of length 0
+    const bool anch = c->anch_reads != 0 && !c->idx->split;
+    if (anch) HIPCHK(hipMemsetAsync(a.ids, 0xFF, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims writes no span
     if ((rc = launch(redo_collect_kernel, (n + 255u) / 256u, 256, st, d_out, d_offsets, n, a.max_reads, a.max_read_len, a.counters, a.ids, a.src, a.lens))) return rc;
     if ((rc = launch(redo_copy_kernel, (a.max_reads + REDO_COPY_WAVES - 1u) / REDO_COPY_WAVES, 64 * REDO_COPY_WAVES, st, d_bases, a.src, a.lens, a.max_reads, a.bases, a.stride))) return rc;
     LaunchOpt o;
@@ -314,6 +354,11 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     o.grid_override = a.grid;
     o.f16 = 65536u;
     o.d_lens = a.lens;
+    if (anch) {  // the slot-to-read array is the arena launch's id map; stream order makes the redo's span the read's final one
+        o.anchor_redo = true;
+        o.d_anchor_ids = a.ids;
+        o.anchors_of = c;
+    }
     if ((rc = launch_map(&a.sub, a.bases, a.offsets, a.max_reads, a.hits, st, o))) return rc;
     if ((rc = launch(redo_scatter_kernel, (a.max_reads + 255u) / 256u, 256, st, a.hits, a.ids, a.counters, a.max_reads, d_out))) return rc;
     HIPCHK(hipEventRecord(a.done, st));
@@ -337,6 +382,84 @@ static int ctx_redo_counts(mq_ctx *c, uint32_t *redone, uint32_t *left) {
     return MQ_OK;
 }
 
+// ---- the anchor output (mq_ctx_reserve_anchors): spans, pool, counter block and their host copies belong to the context and are
+// allocated here; a launch only points its MapArgs at them.
+
+// (0, 0): the reservation goes.  A failure leaves the context with the reservation it had.
+static int ctx_reserve_anchors(mq_ctx *c, uint32_t max_reads, uint64_t max_anchors) {
+    mq_index *idx = c->idx;
+    int rc = ctx_require_idle(c);
+    if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
+    const bool release = max_reads == 0 && max_anchors == 0;
+    Buf<mq_anchor> pool;
+    Buf<mq_anchor_span> spans;
+    Buf<AnchorCounters> counters;
+    Buf<uint32_t> ids;
+    PinnedBuf<mq_anchor> h_pool;
+    PinnedBuf<mq_anchor_span> h_spans;
+    PinnedBuf<AnchorCounters> h_counters;
+    hipEvent_t done = nullptr;
+    if (!release) {
+        if (max_reads == 0 || max_anchors == 0) return set_err(MQ_EINVAL, "max_reads and max_anchors must both be positive (or both 0: release)");
+        if (max_reads > WORK_ID_MASK || max_anchors >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and max_anchors below 2^32 - 1");
+        if (idx->split) return set_err(MQ_EINVAL, "the split pipeline (MQ_PIPELINE=split) writes no anchors: reserve them on an index that runs the fused kernels");
+        if ((rc = ensure_anchors_geometry(idx))) return rc;
+        if ((rc = pool.alloc(max_anchors)) || (rc = spans.alloc(max_reads)) || (rc = counters.alloc(1)) || (rc = ids.alloc(max_reads)) ||
+            (rc = h_pool.alloc(max_anchors)) || (rc = h_spans.alloc(max_reads)) || (rc = h_counters.alloc(1)))
+            return rc;
+        if (!c->anch_done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    }
+    if (c->anch_ran) (void)hipEventSynchronize(c->anch_done);  // the stream of the last launch has passed the arrays that go
+    c->anch_pool = std::move(pool);
+    c->anch_spans = std::move(spans);
+    c->anch_counters = std::move(counters);
+    c->anch_ids = std::move(ids);
+    c->h_anch_pool = std::move(h_pool);
+    c->h_anch_spans = std::move(h_spans);
+    c->h_anch_counters = std::move(h_counters);
+    if (done) c->anch_done.h = done;
+    c->anch_reads = max_reads;
+    c->anch_cap = max_anchors;
+    c->anch_ran = false;
+    c->anch_n = 0;
+    return MQ_OK;
+}
+
+// host copies of the last batch's spans, anchors and counters, once everything that writes them is done
+static int ctx_anchors(mq_ctx *c, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                       uint32_t *dropped_reads) {
+    if (!c->anch_reads) return set_err(MQ_ESTATE, "no anchors reserved on this context: call mq_ctx_reserve_anchors first");
+    if (c->fx_kind != FxKind::None) return set_err(MQ_ESTATE, "context has a submitted piece: call mq_ctx_wait_fasta first");
+    int rc;
+    if (c->pending && (rc = ctx_wait(c))) return rc;  // (the host-driven redo, which delivers the redone reads' anchors, runs there)
+    *spans = c->h_anch_spans;
+    *anchors = c->h_anch_pool;
+    *n_reads = 0;
+    *stored = *needed = 0;
+    *dropped_reads = 0;
+    if (!c->anch_ran || c->anch_n == 0) return MQ_OK;  // no batch yet, or one without reads
+    if ((rc = use_device(c->idx))) return rc;
+    HIPCHK(hipEventSynchronize(c->anch_done));
+    HIPCHK(hipMemcpy(c->h_anch_counters, c->anch_counters, sizeof(AnchorCounters), hipMemcpyDeviceToHost));
+    const AnchorCounters &v = *c->h_anch_counters.p;
+    const uint64_t have = std::min<uint64_t>(v.cursor, c->anch_cap);
+    HIPCHK(hipMemcpy(c->h_anch_spans, c->anch_spans, (size_t)c->anch_n * sizeof(mq_anchor_span), hipMemcpyDeviceToHost));
+    if (have) HIPCHK(hipMemcpy(c->h_anch_pool, c->anch_pool, (size_t)have * sizeof(mq_anchor), hipMemcpyDeviceToHost));
+    *n_reads = c->anch_n;
+    *stored = have;
+    *needed = v.cursor;
+    *dropped_reads = v.dropped_reads;
+    return MQ_OK;
+}
+
+static int ctx_anchors_device(mq_ctx *c, const mq_anchor_span **d_spans, const mq_anchor **d_anchors) {
+    if (!c->anch_reads) return set_err(MQ_ESTATE, "no anchors reserved on this context: call mq_ctx_reserve_anchors first");
+    *d_spans = c->anch_spans;
+    *d_anchors = c->anch_pool;
+    return MQ_OK;
+}
+
 static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases, mq_hit *d_out,
                           hipStream_t st, bool instrumented = false) {
     mq_index *idx = c->idx;
@@ -345,6 +468,7 @@ static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     int rc = ctx_require_idle(c);
     if (rc) return rc;
     if ((rc = use_device(idx))) return rc;
+    if (!instrumented && (rc = anchors_admit(c, n))) return rc;
     if ((rc = ctx_ensure(c, n, total_bases, list_f16(idx)))) return rc;
     LaunchOpt o;
     o.instrumented = instrumented;
@@ -452,6 +576,7 @@ static int fx_take_info(mq_ctx *c) {
 template <typename F>
 static int fx_map_found(mq_ctx *c, const uint8_t *d_bytes, const uint64_t *d_offsets, const uint32_t *d_lens, uint32_t n, uint64_t total_bytes, F side_copies) {
     int rc;
+    if ((rc = anchors_admit(c, n))) return rc;
     if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
     if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
     if ((rc = ctx_ensure(c, n, total_bytes, list_f16(c->idx)))) return rc;
@@ -653,6 +778,45 @@ int mq_map_redo_counts(mq_index *idx, uint32_t *redone, uint32_t *left) {
         if (!idx || !redone || !left) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
         return ctx_redo_counts(idx->def_ctx.get(), redone, left);
+    });
+}
+
+int mq_ctx_reserve_anchors(mq_ctx *ctx, uint32_t max_reads, uint64_t max_anchors) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        return ctx_reserve_anchors(ctx, max_reads, max_anchors);
+    });
+}
+
+int mq_map_reserve_anchors(mq_index *idx, uint32_t max_reads, uint64_t max_anchors) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_reserve_anchors(idx->def_ctx.get(), max_reads, max_anchors);
+    });
+}
+
+int mq_ctx_anchors(mq_ctx *ctx, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                   uint32_t *dropped_reads) {
+    return guarded([&]() -> int {
+        if (!ctx || !spans || !anchors || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_anchors(ctx, spans, anchors, n_reads, stored, needed, dropped_reads);
+    });
+}
+
+int mq_map_anchors(mq_index *idx, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                   uint32_t *dropped_reads) {
+    return guarded([&]() -> int {
+        if (!idx || !spans || !anchors || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_anchors(idx->def_ctx.get(), spans, anchors, n_reads, stored, needed, dropped_reads);
+    });
+}
+
+int mq_ctx_anchors_device(mq_ctx *ctx, const mq_anchor_span **d_spans, const mq_anchor **d_anchors) {
+    return guarded([&]() -> int {
+        if (!ctx || !d_spans || !d_anchors) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_anchors_device(ctx, d_spans, d_anchors);
     });
 }
 

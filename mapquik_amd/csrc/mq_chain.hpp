@@ -51,17 +51,30 @@ __device__ __forceinline__ MatchRec rd_match(const MatchRec &m, int l) {
     return r;
 }
 
+// The anchor output of a launch (ANCH instantiations only: mq_ctx_reserve_anchors): the pool the winning chains' runs go to, and the
+// batch's counters (mq_blocks.hpp)
+struct AnchorOut {
+    mq_anchor *pool;
+    uint32_t cap;  // entries of the pool
+    AnchorCounters *counters;
+};
+
 // Per-reference Chain::get_match + best-of + find_coords.  CH = lanes used per chunk (64; smaller only in tests
 // so that ordinary inputs exercise the multi-chunk path).
 // first: lane i's record i already in a register (the caller read the first chunk itself); with nm <= CH nothing is read here then
-template <int CH>
+// ANCH: the runs of the winning chain -- the list filter_matches_max leaves, src/chain.rs:123-129 -- go to ao's pool as well, and `span`
+// says where ({0, 0} for a read that is not mapped).  Every line of that sits under `if constexpr (ANCH)`: the instantiations without it
+// are the code they were.
+template <int CH, bool ANCH = false>
 __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint32_t nm, const DevParams &P, uint64_t q_len,
-                                            const uint64_t *__restrict__ ref_lens, mq_hit &out, const MatchRec *first = nullptr) {
+                                            const uint64_t *__restrict__ ref_lens, mq_hit &out, const MatchRec *first = nullptr,
+                                            const AnchorOut *ao = nullptr, mq_anchor_span *span = nullptr) {
     const uint32_t lane = lane_id();
     // find_largest_two_chains state (src/mers.rs:110-129)
     uint32_t max_count = 0, second_count = 0, n_cand = 0;
     MatchRec bfirst = {}, blast = {};
     uint32_t b_ref = 0, b_score = 0, b_mapq = 0, b_len = 0;
+    MatchRec b_anchor = {};  // (ANCH) the anchor of the reference that becomes b_ref: wave-uniform, like bfirst / blast
     for (uint32_t c0 = 0; c0 < nm; c0 += CH) {
         const bool v0 = lane < (uint32_t)CH && c0 + lane < nm;
         MatchRec m = {};
@@ -130,6 +143,7 @@ __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint
                 b_ref = r;
                 b_score = score;
                 b_len = nkept;
+                if constexpr (ANCH) b_anchor = anchor;
                 b_mapq = ((P.s != 0 && P.c != 0) && (nkept >= P.c || score >= P.s)) ? 60u : 0u;
             } else if (score > second_count) {
                 second_count = score;
@@ -184,6 +198,46 @@ __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint
     out.r_start = (uint32_t)frs;
     out.r_end = (uint32_t)fre;
     out.score = b_score;
+    if constexpr (ANCH) {
+        // pass C, for a mapped read only: the winner's kept runs once more, in read order.  The records are loaded again (the `done` flags
+        // no longer matter; one chunk in LDS: lane i still holds record i in *first); a run stays by pass B's test against the winner's
+        // anchor, so the list has b_len entries -- for a reference with a single run that run equals the anchor.
+        // The claim first: ONE atomic add of b_len on the pool cursor, in front of the first store.  The cursor counts on past the capacity.
+        unsigned long long at = 0;
+        if (lane == 0) at = atomicAdd(&ao->counters->cursor, (unsigned long long)b_len);
+        at = rdlane64(at, 0);
+        const bool fits = at + b_len <= (unsigned long long)ao->cap;
+        if (!fits) {
+            if (lane == 0) atomicAdd(&ao->counters->dropped_reads, 1u);
+            span->first = MQ_ANCHORS_DROPPED;
+            span->count = b_len;
+            return;
+        }
+        mq_anchor *dst = ao->pool + at;
+        uint32_t running = 0;
+        for (uint32_t c = 0; c < nm; c += CH) {
+            const bool v = lane < (uint32_t)CH && c + lane < nm;
+            MatchRec x = {};
+            if (first && c == 0) x = *first;
+            else if (v) x = scratch[c + lane];
+            const bool keep = v && x.ref == b_ref && match_compatible(b_anchor, x, P.g);
+            const uint64_t km = __ballot(keep);
+            if (!km) continue;
+            const uint32_t rank = running + mbcnt64(km);  // kept runs in front of this lane's: earlier chunks, lower lanes
+            if (keep && rank < b_len) {  // (rank < b_len always: pass B counted the same runs)
+                mq_anchor a;
+                a.q_start = x.q_start;
+                a.q_end = x.q_end;
+                a.r_start = x.r_start;
+                a.r_end = x.r_end;
+                a.count = x.count;
+                dst[rank] = a;
+            }
+            running += (uint32_t)__popcll(km);
+        }
+        span->first = (uint32_t)at;
+        span->count = b_len;
+    }
 }
 
 }  // namespace mq

@@ -80,6 +80,20 @@ struct mq_ctx {
     const uint32_t *p_lens = nullptr;
     uint32_t p_n = 0;
     mq_hit *p_out = nullptr;
+    // mq_ctx_reserve_anchors: the anchor output of the context's batches (anch_reads == 0: no reservation -- the context runs the kernels it
+    // always ran).  Allocated at the reservation, never by a launch.
+    uint32_t anch_reads = 0;              // max_reads
+    uint64_t anch_cap = 0;                // max_anchors (< 2^32 - 1)
+    Buf<mq_anchor> anch_pool;
+    Buf<mq_anchor_span> anch_spans;
+    Buf<AnchorCounters> anch_counters;    // one block (mq_blocks.hpp), cleared in front of every batch's main launch
+    Buf<uint32_t> anch_ids;               // the host-driven redo's read numbers (MapArgs::anchor_ids of redo_relaunch)
+    PinnedBuf<mq_anchor> h_anch_pool;     // mq_ctx_anchors' host copies
+    PinnedBuf<mq_anchor_span> h_anch_spans;
+    PinnedBuf<AnchorCounters> h_anch_counters;
+    ScopedEvent anch_done;                // behind the last launch sequence that wrote anchors (recorded on ITS stream: the context's, or the caller's)
+    bool anch_ran = false;                // ... recorded at least once
+    uint32_t anch_n = 0;                  // reads of the last batch that delivered anchors
     // mq_ctx_reserve_redo: what the device form needs to redo its overflow reads in stream (none: they come back MQ_HIT_OVERFLOW).  The
     // last member, so the first to go: it waits for its own last launch, and its buffers go before the context's.
     std::unique_ptr<RedoArena> redo;
@@ -292,6 +306,11 @@ struct mq_index {
     int grid_ref = 0;                        // workgroups of seed_ref_kernel that stay resident
     // launch geometry (workgroups) and scratch sizes, fixed at the first map call
     uint32_t grid_fused = 0, grid_seed = 0, grid_map = 0;  // map_kernel; seed_reads_kernel, map_lists_kernel (split)
+    // ... of the launches of contexts with an anchor reservation: the minimum over grid_fused and the index's anchors pair, worked out at the
+    // first reservation (an index nobody reserves anchors on keeps its launch geometry)
+    std::once_flag anchors_geometry_once;
+    int anchors_geometry_rc = MQ_OK;
+    uint32_t grid_fused_anchors = 0;
     uint32_t cap_matches = 0;
     bool split = false;             // diagnostic MQ_PIPELINE=split: the two phases as separate launches (a profiler then prices each)
     bool force_general = false;     // test hook MQ_FORCE_GENERAL=1: never take the fast seeding path
@@ -470,12 +489,16 @@ using MapFn = void (*)(MapArgs);
 struct MapPair {
     MapFn map, declined;
 };
-template <int CH, bool TIMING, bool VAR, class Spec = SpecNone>
+template <int CH, bool TIMING, bool VAR, class Spec = SpecNone, bool ANCH = false>
 constexpr MapPair map_pair() {
-    return {map_kernel<CH, TIMING, VAR, Spec>, map_declined_kernel<CH, TIMING, VAR, Spec>};
+    return {map_kernel<CH, TIMING, VAR, Spec, ANCH>, map_declined_kernel<CH, TIMING, VAR, Spec, ANCH>};
 }
 static const MapPair MAP_KERNELS[2][2][2] = {{{map_pair<64, false, false>(), map_pair<4, false, false>()}, {map_pair<64, true, false>(), map_pair<64, true, false>()}},
                                              {{map_pair<64, false, true>(), map_pair<4, false, true>()}, {map_pair<64, true, true>(), map_pair<64, true, true>()}}};
+// The anchors dimension: the SpecNone, non-instrumented pairs once more with the anchor output (a context with a reservation:
+// mq_ctx_reserve_anchors), by [seeding variant != 0][chain chunk 4].  MAP_SPECS has no such dimension: a reserving context launches SpecNone.
+static const MapPair MAP_KERNELS_ANCHORS[2][2] = {{map_pair<64, false, false, SpecNone, true>(), map_pair<4, false, false, SpecNone, true>()},
+                                                  {map_pair<64, false, true, SpecNone, true>(), map_pair<4, false, true, SpecNone, true>()}};
 
 // The spec dimension of the table: the product pair (chunk 64, not instrumented, frozen reading) compiled for the parameters nearly
 // every run uses -- the reference's defaults -k 5 -l 31 with homopolymer compression and SipHash, the -k 7 of its real-data runs, and the
@@ -507,7 +530,12 @@ static uint32_t map_spec_of(const mq_index *idx) {
     return 0;
 }
 // the pair of a fused launch sequence, and the spec id it carries
-static const MapPair &map_pair_of(const mq_index *idx, bool instrumented, uint32_t *spec_id = nullptr) {
+// anchors: the launching context has an anchor reservation and the launch delivers (never the instrumented one)
+static const MapPair &map_pair_of(const mq_index *idx, bool instrumented, uint32_t *spec_id = nullptr, bool anchors = false) {
+    if (anchors && !instrumented) {
+        if (spec_id) *spec_id = 0;
+        return MAP_KERNELS_ANCHORS[idx->dp.variant != 0][idx->chain_chunk == 4];
+    }
     const uint32_t sid = instrumented ? 0u : idx->map_spec;
     if (spec_id) *spec_id = sid;
     return sid ? MAP_SPECS[sid - 1].pair : MAP_KERNELS[idx->dp.variant != 0][instrumented][idx->chain_chunk == 4];
@@ -519,15 +547,15 @@ static void set_dev_params(mq_index *idx, const DevParams &dp) {
 }
 
 // launch geometry: persistent waves, as many workgroups as stay resident
+static int occ_of(const void *fn, int threads, int &occ) {
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, 0));
+    if (occ < 1) occ = 1;
+    if (occ > 8) occ = 8;
+    const int oe = env_int("MQ_OCC", 0);  // diagnostic: cap workgroups per CU
+    if (oe >= 1 && oe < occ) occ = oe;
+    return MQ_OK;
+}
 static int ensure_geometry_once(mq_index *idx) {
-    auto occ_of = [&](const void *fn, int threads, int &occ) -> int {
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, 0));
-        if (occ < 1) occ = 1;
-        if (occ > 8) occ = 8;
-        const int oe = env_int("MQ_OCC", 0);  // diagnostic: cap workgroups per CU
-        if (oe >= 1 && oe < occ) occ = oe;
-        return MQ_OK;
-    };
     int occ = 0, occ_min = INT_MAX, rc;
     // the grid of a launch sequence = the workgroups that are RESIDENT together, for every instantiation launched on it: wave w's first two
     // work items are its own (items w and n_waves + w, among them the heavy reads that go first), so a workgroup that has to wait for a
@@ -563,6 +591,23 @@ static uint32_t fx_grid(const mq_index *idx, uint32_t n_tiles) { return std::max
 static int ensure_geometry(mq_index *idx) {
     std::call_once(idx->geometry_once, [idx] { idx->geometry_rc = ensure_geometry_once(idx); });  // contexts of one index start concurrently
     return idx->geometry_rc;
+}
+
+// ... of a context that reserves anchors: the index's anchors pair (its seeding variant and chain chunk are fixed at mq_index_new) joins the
+// occupancy minimum -- for the launches of such contexts only, in a second grid
+static int ensure_anchors_geometry(mq_index *idx) {
+    int rc = ensure_geometry(idx);
+    if (rc) return rc;
+    std::call_once(idx->anchors_geometry_once, [idx] {
+        const MapPair &kp = map_pair_of(idx, false, nullptr, true);
+        int occ = 0, occ_min = INT_MAX;
+        for (const MapFn fn : {kp.map, kp.declined}) {
+            if ((idx->anchors_geometry_rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return;
+            occ_min = std::min(occ_min, occ);
+        }
+        idx->grid_fused_anchors = std::min(idx->grid_fused, (uint32_t)(occ_min * idx->n_cu));
+    });
+    return idx->anchors_geometry_rc;
 }
 
 // list entries reserved per base, in 1/65536: 4 d + 1/512 -- canonical selection keeps 1-(1-d)^2 ~ 2 d of the l-mers, so this
