@@ -126,6 +126,28 @@ typedef struct mq_anchor_span {
 } mq_anchor_span;
 #define MQ_ANCHORS_DROPPED 0xFFFFFFFFu /* mq_anchor_span::first of a mapped read whose anchors found no room in the pool (count is still right) */
 
+/* Every candidate pseudo-chain of a read (opt-in: mq_ctx_reserve_chains below): one per reference that has at least one Match run in
+ * the read -- what find_matches builds and find_largest_two_chains looks through (src/mers.rs:77-129), of which the hit is the strictly
+ * largest.  48 bytes, field for field the layout of mq_hit: the unique top chain of a mapped read equals the read's mq_hit in every word
+ * but word 9 (n_runs here, n_kminmers there), and its flags == MQ_CHAIN_TOP == MQ_HIT_MAPPED.
+ * Order: a read's chains are listed in the order of each reference's first run in the read.  The reference keeps its chains in a HashMap,
+ * whose order is unspecified: this is one of its legal orders.
+ * Ties: a read is mapped <=> exactly one of its chains has MQ_CHAIN_TOP (find_largest_two_chains + determine_best_match: a tie <=> the top
+ * score occurs twice); a tied read has status MQ_HIT_UNMAPPED and two or more TOP chains. */
+#define MQ_CHAIN_TOP 1u /* mq_chain::flags: no chain of this read scores higher */
+typedef struct mq_chain {
+    uint32_t flags;
+    uint32_t ref_id, rc, mapq; /* mapq by get_match's own rule for THIS chain (c, s; src/chain.rs:158-161) */
+    uint32_t q_start, q_end, r_start, r_end; /* after find_coords against THIS chain's reference length (low words of columns 3 and 4) */
+    uint32_t score;            /* sum of the kept runs' counts */
+    uint32_t n_runs;           /* len_f: runs filter_matches_max left */
+    uint32_t q_start_hi, q_end_hi; /* high words of columns 3 and 4, as in mq_hit */
+} mq_chain;
+typedef struct mq_chain_span {
+    uint32_t first, count; /* read r's chains: pool[first .. first + count) */
+} mq_chain_span;
+#define MQ_CHAINS_DROPPED 0xFFFFFFFFu /* mq_chain_span::first of a read whose chains found no room in the pool (count is still right) */
+
 typedef struct mq_index mq_index; /* opaque: Index / ReadOnlyIndex (src/index.rs:73-128) + ref_map (src/closures.rs:30) */
 
 typedef struct mq_index_stats {
@@ -396,6 +418,41 @@ int mq_map_reserve_anchors(mq_index *idx, uint32_t max_reads, uint64_t max_ancho
 int mq_map_anchors(mq_index *idx, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
                    uint32_t *dropped_reads);
 
+/* Every candidate chain of every read (opt-in, per context; a context without a reservation runs exactly the kernels it always ran).
+ * mq_ctx_reserve_chains allocates, now, a span per read for batches of up to max_reads reads, a pool of max_chains chains, and a staging
+ * window per mapping wave beside its Match window.  From then on every map call on the context -- mq_ctx_map_batch, mq_ctx_submit /
+ * _submit_spans + mq_ctx_wait, mq_ctx_submit_fasta / _fastx + both waits, mq_ctx_map_batch_device with and without a redo arena -- takes
+ * the kernel pair that also writes, for read r of the batch, spans[r] and its chains at pool[first .. first + count), in the order of each
+ * reference's first run in the read.  A read with no run, or shorter than l + k - 1, has span {0, 0}.  A read that is redone
+ * (MQ_HIT_OVERFLOW: through the host, or in stream with a redo arena) delivers its chains from the redo; one that leaves with
+ * MQ_HIT_OVERFLOW has span {0, 0}.  The order in which the reads' lists lie in the pool is not defined.
+ * A context may hold an anchors reservation and a chains reservation at once: both outputs are written then.
+ * Pool exhaustion is loud, never wrong: a read whose list found no room has first == MQ_CHAINS_DROPPED and its true count;
+ * `dropped_reads` counts them, `needed` says what the batch asked of the pool (reserve that much and map again: there is no automatic
+ * second pass), the hits are unaffected.  A batch of more than max_reads reads is refused with MQ_EINVAL before anything is queued --
+ * except a FASTX piece, whose number of records is known only at mq_ctx_wait_fasta[_lines]: that call refuses it, before the map launch,
+ * and the piece is consumed (its copy and its scan have run).  A call that fails leaves mq_ctx_chains describing the last batch that was
+ * launched.  The instrumented launch of mq_map_probe_stats and mq_kminmers_batch write no chains.
+ *   (0, 0)        releases the reservation: the feature is off again
+ *   MQ_ESTATE     the context has a submitted batch
+ *   MQ_EINVAL     one of the two 0; max_reads >= 2^30; max_chains >= 2^32 - 1; the index runs the split pipeline (MQ_PIPELINE=split)
+ *   MQ_ENOMEM     the context keeps the reservation it had (or none)
+ * Device memory: 8 max_reads + 48 max_chains bytes (+ 4 max_reads for the redo's id map), the same again page-locked on the host, and 32
+ * bytes per Match record of the windows the context's launches use.
+ * mq_ctx_chains finishes the context's last batch (mq_ctx_wait if it was only submitted; the stream of a device-form call is waited for)
+ * and returns host copies: spans[0 .. n_reads), chains[0 .. stored), stored = min(needed, max_chains) -- valid until the next map call,
+ * reserve or free on the context.  MQ_ESTATE without a reservation or with a FASTX piece in flight; n_reads = 0 before the first batch.
+ * mq_ctx_chains_device gives the device arrays themselves and waits for nothing: for mq_ctx_map_batch_device callers that stay on their
+ * stream (valid until the reservation changes).
+ * mq_map_reserve_chains / mq_map_chains: the same for the index's default context, as mq_map_reserve_redo. */
+int mq_ctx_reserve_chains(mq_ctx *ctx, uint32_t max_reads, uint64_t max_chains);
+int mq_ctx_chains(mq_ctx *ctx, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                  uint32_t *dropped_reads);
+int mq_ctx_chains_device(mq_ctx *ctx, const mq_chain_span **d_spans, const mq_chain **d_chains);
+int mq_map_reserve_chains(mq_index *idx, uint32_t max_reads, uint64_t max_chains);
+int mq_map_chains(mq_index *idx, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                  uint32_t *dropped_reads);
+
 /* Page-locked host memory for the buffers handed to mq_map_batch / mq_index_add_ref (a feeder that parses FASTX straight
  * into such buffers gets the full PCIe rate on the copy in; pageable buffers work too, at roughly a quarter of it). */
 void *mq_host_alloc(size_t bytes);
@@ -420,6 +477,10 @@ int mq_index_lookup(mq_index *idx, const uint64_t *hashes, uint32_t n, uint8_t *
 
 /* The format! of src/mers.rs:181 (no newline).  Returns the length or <0. */
 int mq_format_paf(const mq_index *idx, const char *q_id, uint64_t q_len, const mq_hit *hit, char *buf, size_t cap);
+
+/* The twelve columns of mq_format_paf for any chain of mq_ctx_chains, TOP or not (no newline): for the unique top chain of a mapped read
+ * the bytes are those of mq_format_paf on the read's hit.  Returns the length or <0. */
+int mq_format_paf_chain(const mq_index *idx, const char *q_id, uint64_t q_len, const mq_chain *chain, char *buf, size_t cap);
 
 /* Measurement and diagnostic entry points (probe statistics, stage clocks, launch timers): include/mapquik_hip_diag.h. */
 

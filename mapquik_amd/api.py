@@ -26,6 +26,13 @@ anchor_dtype = np.dtype([("q_start", "<u4"), ("q_end", "<u4"), ("r_start", "<u4"
 anchor_span_dtype = np.dtype([("first", "<u4"), ("count", "<u4")])
 MQ_ANCHORS_DROPPED = 0xFFFFFFFF
 assert anchor_dtype.itemsize == 20 and anchor_span_dtype.itemsize == 8
+# mq_chain / mq_chain_span (Context.reserve_chains): a candidate chain of a read, field for field the layout of a hit; where a read's chains lie
+chain_dtype = np.dtype([("flags", "<u4"), ("ref_id", "<u4"), ("rc", "<u4"), ("mapq", "<u4"), ("q_start", "<u4"), ("q_end", "<u4"),
+                        ("r_start", "<u4"), ("r_end", "<u4"), ("score", "<u4"), ("n_runs", "<u4"), ("q_start_hi", "<u4"), ("q_end_hi", "<u4")])
+chain_span_dtype = np.dtype([("first", "<u4"), ("count", "<u4")])
+MQ_CHAIN_TOP = 1
+MQ_CHAINS_DROPPED = 0xFFFFFFFF
+assert chain_dtype.itemsize == 48 and chain_span_dtype.itemsize == 8
 
 
 def hit_column(hits, name):
@@ -44,6 +51,7 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_ctx_new", "mq_ctx_free", "mq_ctx_map_batch", "mq_ctx_submit", "mq_ctx_submit_spans", "mq_ctx_wait", "mq_ctx_reserve", "mq_ctx_map_batch_device", "mq_ctx_last_map_ms", "mq_probe_rate", "mq_last_stage_clocks", "mq_last_read_cycles", "mq_map_launch_waves", "mq_index_table_alloc_ms",
            "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts",
            "mq_ctx_reserve_anchors", "mq_ctx_anchors", "mq_ctx_anchors_device", "mq_map_reserve_anchors", "mq_map_anchors",
+           "mq_ctx_reserve_chains", "mq_ctx_chains", "mq_ctx_chains_device", "mq_map_reserve_chains", "mq_map_chains", "mq_format_paf_chain",
            "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized"]
 
 
@@ -189,6 +197,14 @@ def load_library(path=None):
         L.mq_ctx_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
         L.mq_map_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
         L.mq_ctx_anchors_device.argtypes = [vp, pp, pp]
+    if hasattr(L, "mq_ctx_reserve_chains"):
+        pp = C.POINTER(vp)
+        L.mq_ctx_reserve_chains.argtypes = [vp, u32, u64]
+        L.mq_map_reserve_chains.argtypes = [vp, u32, u64]
+        L.mq_ctx_chains.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+        L.mq_map_chains.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+        L.mq_ctx_chains_device.argtypes = [vp, pp, pp]
+        L.mq_format_paf_chain.argtypes = [vp, C.c_char_p, u64, vp, C.c_char_p, C.c_size_t]
     if hasattr(L, "mq_index_reopen"):
         L.mq_index_reopen.argtypes = [vp]
         L.mq_index_resize.argtypes = [vp, u64, u32]
@@ -218,6 +234,18 @@ def _anchors(L, fn, what, handle):
     spans = np.frombuffer(C.string_at(sp.value, n.value * anchor_span_dtype.itemsize), dtype=anchor_span_dtype).copy() if n.value else np.zeros(0, dtype=anchor_span_dtype)
     anchors = np.frombuffer(C.string_at(an.value, stored.value * anchor_dtype.itemsize), dtype=anchor_dtype).copy() if stored.value else np.zeros(0, dtype=anchor_dtype)
     return spans, anchors, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
+
+
+def _chains(L, fn, what, handle):
+    """(spans, chains, info) of mq_ctx_chains / mq_map_chains: numpy copies of the library's host arrays"""
+    sp, ch = C.c_void_p(), C.c_void_p()
+    n, dropped = C.c_uint32(), C.c_uint32()
+    stored, needed = C.c_uint64(), C.c_uint64()
+    if fn(handle, C.byref(sp), C.byref(ch), C.byref(n), C.byref(stored), C.byref(needed), C.byref(dropped)) != 0:
+        raise _err(L, what)
+    spans = np.frombuffer(C.string_at(sp.value, n.value * chain_span_dtype.itemsize), dtype=chain_span_dtype).copy() if n.value else np.zeros(0, dtype=chain_span_dtype)
+    chains = np.frombuffer(C.string_at(ch.value, stored.value * chain_dtype.itemsize), dtype=chain_dtype).copy() if stored.value else np.zeros(0, dtype=chain_dtype)
+    return spans, chains, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
 
 
 class PinnedBuffer:
@@ -479,6 +507,29 @@ class Index:
         """Context.anchors for the default context."""
         return _anchors(self._L, self._L.mq_map_anchors, "mq_map_anchors", self._h)
 
+    def reserve_chains(self, max_reads, max_chains):
+        """Context.reserve_chains for the default context (map_batch, map_batch_device); (0, 0) releases."""
+        if self._L.mq_map_reserve_chains(self._h, int(max_reads), int(max_chains)) != 0:
+            raise _err(self._L, "mq_map_reserve_chains")
+
+    def chains(self):
+        """Context.chains for the default context."""
+        return _chains(self._L, self._L.mq_map_chains, "mq_map_chains", self._h)
+
+    def format_paf_chain(self, q_id, q_len, chain):
+        """The twelve PAF columns of any chain of chains() (mq_format_paf_chain)."""
+        rec = np.zeros(1, dtype=chain_dtype)
+        rec[0] = chain
+        cap = 4096
+        while True:
+            buf = C.create_string_buffer(cap)
+            w = self._L.mq_format_paf_chain(self._h, q_id.encode(), int(q_len), _p(rec), buf, cap)
+            if w < 0:
+                raise _err(self._L, "mq_format_paf_chain")
+            if w < cap:
+                return buf.value.decode()
+            cap = w + 1
+
     def context(self):
         """A stream slot (mq_ctx): own stream, scratch and staging; contexts of one finalized index may map concurrently."""
         return Context(self)
@@ -726,6 +777,26 @@ class Context:
         """(spans, anchors, info) of the context's last batch, which it finishes: read r's runs are anchors[spans[r]["first"]:][:spans[r]["count"]]
         in read order (first == MQ_ANCHORS_DROPPED: the pool was too small for them); info = dict(stored, needed, dropped_reads)."""
         return _anchors(self._L, self._L.mq_ctx_anchors, "mq_ctx_anchors", self._h)
+
+    def reserve_chains(self, max_reads, max_chains):
+        """From now on every batch of up to max_reads reads mapped on this context also delivers every candidate chain of every read -- one per
+        reference with a Match run in the read, ties included -- from a pool of max_chains entries (include/mapquik_hip.h:
+        mq_ctx_reserve_chains).  (0, 0) releases."""
+        if self._L.mq_ctx_reserve_chains(self._h, int(max_reads), int(max_chains)) != 0:
+            raise _err(self._L, "mq_ctx_reserve_chains")
+
+    def chains(self):
+        """(spans, chains, info) of the context's last batch, which it finishes: read r's chains are chains[spans[r]["first"]:][:spans[r]["count"]]
+        in the order of each reference's first run in the read (first == MQ_CHAINS_DROPPED: the pool was too small for them); info =
+        dict(stored, needed, dropped_reads).  A read is mapped exactly when one of its chains has flags == MQ_CHAIN_TOP."""
+        return _chains(self._L, self._L.mq_ctx_chains, "mq_ctx_chains", self._h)
+
+    def chains_device(self):
+        """(device pointer of the spans, device pointer of the chains): the arrays a map_batch_device call on this context writes."""
+        sp, ch = C.c_void_p(), C.c_void_p()
+        if self._L.mq_ctx_chains_device(self._h, C.byref(sp), C.byref(ch)) != 0:
+            raise _err(self._L, "mq_ctx_chains_device")
+        return sp.value, ch.value
 
     def anchors_device(self):
         """(device pointer of the spans, device pointer of the anchors): the arrays a map_batch_device call on this context writes."""

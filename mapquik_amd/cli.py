@@ -121,7 +121,24 @@ def build_parser():
                     help="also write <prefix>.anchors: one line per Match run of every mapped read's winning chain, reads in input order, runs in "
                          "read order: q_id, q_start, q_end, strand, r_name, r_start, r_end, count -- raw coordinates as the chain holds them, "
                          "before find_coords (extension; the reference's -a path, src/chain.rs:173-237, walks the same list)")
+    ap.add_argument("--chains", action="store_true",
+                    help="also write <prefix>.chains: one line per candidate chain of every read (one per reference with a Match run in the read, ties "
+                         "included), reads in input order: the twelve PAF columns of the chain, tp:A:P for the read's unique top chain and tp:A:S "
+                         "for every other, cn:i:<runs kept>, and tie:i:1 on the top chains of a tied read (extension)")
     return ap
+
+
+def chain_lines(index, names, offs, spans, chains):
+    """the text of <prefix>.chains for one batch"""
+    out = []
+    for i, (nm, sp) in enumerate(zip(names, spans)):
+        mine = chains[int(sp["first"]):int(sp["first"]) + int(sp["count"])]
+        tops = int((mine["flags"] & api.MQ_CHAIN_TOP != 0).sum())
+        for ch in mine:
+            top = bool(int(ch["flags"]) & api.MQ_CHAIN_TOP)
+            out.append("%s\ttp:A:%s\tcn:i:%d%s" % (index.format_paf_chain(nm, int(offs[i + 1] - offs[i]), ch), "P" if top and tops == 1 else "S", int(ch["n_runs"]),
+                                                 "\ttie:i:1" if top and tops > 1 else ""))
+    return out
 
 
 def anchor_lines(names, hits, spans, anchors, ref_name):
@@ -204,6 +221,7 @@ def main(argv=None):
     paf = open(st["prefix"] + ".paf", "w")  # src/closures.rs:32
     unm = open(st["prefix"] + ".unmapped.out", "w") if opt.unmapped else None
     anc = open(st["prefix"] + ".anchors", "w") if opt.anchors else None
+    chn = open(st["prefix"] + ".chains", "w") if opt.chains else None
 
     t0 = time.time()
     if opt.load_index:
@@ -259,7 +277,16 @@ def main(argv=None):
             # library's minimizer lists are sized at bytes x (4 density + 1/512) entries: the same bound here.  A batch that needs more
             # (reads inside dense tandem arrays) ends the run with what it needed.
             index.reserve_anchors(len(seqs), min(int(bases.size * (4.0 * st["density"] + 1.0 / 512.0)) + 64, (1 << 32) - 2))
+        if chn is not None:  # (a read has no more chains than runs: the anchors' bound)
+            index.reserve_chains(len(seqs), min(int(bases.size * (4.0 * st["density"] + 1.0 / 512.0)) + 64, (1 << 32) - 2))
         hits = index.map_batch(bases, offs)
+        if chn is not None:
+            spans, chains, info = index.chains()
+            if info["dropped_reads"]:
+                raise SystemExit("--chains: the chain pool was too small for %d reads of a batch: %d entries needed, %d reserved"
+                                 % (info["dropped_reads"], info["needed"], info["stored"]))
+            for ln in chain_lines(index, names, offs, spans, chains):
+                chn.write(ln + "\n")
         if anc is not None:
             spans, anchors, info = index.anchors()
             if info["dropped_reads"]:
@@ -288,6 +315,8 @@ def main(argv=None):
         unm.close()
     if anc is not None:
         anc.close()
+    if chn is not None:
+        chn.close()
     print("Mapped query sequences in %s." % rust_duration(time.time() - t0))  # src/closures.rs:211
     print("Total execution time: %s" % rust_duration(time.time() - start))  # src/main.rs:270
     rss_gb = np.float32(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss * 1024) / np.float32(1024.0 ** 3)

@@ -43,6 +43,10 @@ struct Chunk {
     std::vector<mq_anchor_span> a_spans;
     std::vector<mq_anchor> a_pool;
     std::string anchors;
+    // --chains: the same for the chunk's chain spans and chains (mq_ctx_chains)
+    std::vector<mq_chain_span> c_spans;
+    std::vector<mq_chain> c_pool;
+    std::string chains;
     // set by the whole-member gzip reader: the chunk's bytes still sit in a member's inflate buffer (kept alive by ext_hold);
     // the parser thread that takes the chunk copies them into buf first
     const uint8_t *ext_src = nullptr;
@@ -80,6 +84,9 @@ struct Chunk {
         a_spans.clear();
         a_pool.clear();
         anchors.clear();
+        c_spans.clear();
+        c_pool.clear();
+        chains.clear();
     }
 };
 

@@ -68,15 +68,59 @@ inline void take_anchors(mq_ctx *ctx, feeder::Chunk &c) {
     c.a_pool.assign(pool, pool + stored);
 }
 
+// --chains: the same for the chunk's chain spans and chains
+inline void take_chains(mq_ctx *ctx, feeder::Chunk &c) {
+    c.c_spans.clear();
+    c.c_pool.clear();
+    if (c.hits.empty()) return;
+    const mq_chain_span *spans = nullptr;
+    const mq_chain *pool = nullptr;
+    uint32_t n = 0, dropped = 0;
+    uint64_t stored = 0, needed = 0;
+    if (mq_ctx_chains(ctx, &spans, &pool, &n, &stored, &needed, &dropped) != MQ_OK) throw Error(std::string("mq_ctx_chains: ") + last_error());
+    if (n != c.hits.size()) throw Error("mq_ctx_chains: " + std::to_string(n) + " spans for a chunk of " + std::to_string(c.hits.size()) + " reads");
+    if (dropped)
+        throw Error("--chains: the chain pool of a stream slot was too small for " + std::to_string(dropped) + " reads of a chunk: " + std::to_string(needed) +
+                    " entries needed, " + std::to_string(stored) + " reserved");
+    c.c_spans.assign(spans, spans + n);
+    c.c_pool.assign(pool, pool + stored);
+}
+
+// --chains: the lines of read i -- one per chain, in span order: the twelve PAF columns of the chain (mq_format_paf_chain's bytes), tp:A:P
+// for the read's unique top chain and tp:A:S for every other, cn:i:<n_runs>, and tie:i:1 on a top chain of a tied read (tp S: no primary)
+inline std::string format_chains(feeder::Chunk &c, PafWriter &pw, size_t i) {
+    if (i >= c.c_spans.size() || (uint64_t)c.c_spans[i].first + c.c_spans[i].count > c.c_pool.size()) return "--chains: a read without its chains";
+    const mq_chain *ch = c.c_pool.data() + c.c_spans[i].first;
+    const uint32_t n = c.c_spans[i].count;
+    uint32_t tops = 0;
+    for (uint32_t j = 0; j < n; ++j) tops += (ch[j].flags & MQ_CHAIN_TOP) ? 1u : 0u;
+    char tag[64];
+    for (uint32_t j = 0; j < n; ++j) {
+        mq_hit h;  // field for field the chain's layout: the columns are where the PAF writer reads them
+        static_assert(sizeof(mq_hit) == sizeof(mq_chain), "mq_chain has the layout of mq_hit");
+        memcpy(&h, &ch[j], sizeof(h));
+        pw.append(c.chains, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);
+        c.chains.pop_back();  // (the writer's newline)
+        const bool top = (ch[j].flags & MQ_CHAIN_TOP) != 0;
+        c.chains.append(tag, (size_t)snprintf(tag, sizeof(tag), "\ttp:A:%c\tcn:i:%u%s\n", top && tops == 1 ? 'P' : 'S', ch[j].n_runs, top && tops > 1 ? "\ttie:i:1" : ""));
+    }
+    return "";
+}
+
 // A mapped chunk's output: PAF lines of the mapped reads (src/mers.rs:181), and of the unmapped ones the names (want_unmapped) and the
 // records as FASTA (want_fasta, for a second pass).  Returns the error text for a hit that is neither, "" else.
 // want_anchors: beside a mapped read's PAF line, one line per Match run of its chain, in read order (take_anchors filled a_spans / a_pool):
 // q_id, q_start, q_end, strand, r_name, r_start, r_end, count
-inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta, bool want_anchors = false) {
+// want_chains: one line per candidate chain of EVERY read, mapped or tied (format_chains)
+inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta, bool want_anchors = false, bool want_chains = false) {
     std::string id;
     c.paf.reserve(c.lens.size() * 96);
     for (size_t i = 0; i < c.lens.size(); ++i) {
         const mq_hit &h = c.hits[i];
+        if (want_chains && (h.status == MQ_HIT_MAPPED || h.status == MQ_HIT_UNMAPPED)) {
+            const std::string err = format_chains(c, pw, i);
+            if (!err.empty()) return err;
+        }
         if (h.status == MQ_HIT_MAPPED) {
             pw.append(c.paf, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);  // src/mers.rs:181
             if (want_anchors) {
@@ -116,6 +160,7 @@ class MapPipeline {
         long fail_at;        // MQ_DRIVER_FAIL_AT (test hook): the submitter that takes this chunk number reports a failure; -1: none
         FILE *anchors = nullptr;  // --anchors: <prefix>.anchors, written the way the unmapped names are
         double density = 0;       // ... and what a slot's reservation is sized with (Ctx::reserve_anchors)
+        FILE *chains = nullptr;   // --chains: <prefix>.chains, the same way
     };
     // slots[w]: the stream slots of submitter w (n_sub submitters per GPU, each over its GPU's index); index: where the formatters look
     // reference names up; paf, unmapped, unmapped_fa: the open output files, the last two may be null
@@ -174,6 +219,7 @@ class MapPipeline {
             const auto ts0 = Clock::now();
             // --anchors: the slots reserve for the feeder's chunk size when they are made; a chunk that is larger (one very long record) makes its slot reserve again
             if (p.cfg_.anchors && c->bytes > ctx[sl].anchors_bytes()) ctx[sl].reserve_anchors(c->bytes, p.cfg_.density);
+            if (p.cfg_.chains && c->bytes > ctx[sl].chains_bytes()) ctx[sl].reserve_chains(c->bytes, p.cfg_.density);
             if (c->unparsed) {
                 if (mq_ctx_submit_fastx(ctx[sl].handle(), c->buf, c->begin, c->bytes, p.cfg_.fx_format) != MQ_OK) throw Error(std::string("mq_ctx_submit_fastx: ") + last_error());
             } else if (mq_ctx_submit_spans(ctx[sl].handle(), c->buf, c->bytes, c->starts.data(), c->lens.data(), (uint32_t)c->starts.size(), c->hits.data()) != MQ_OK) {
@@ -196,6 +242,7 @@ class MapPipeline {
                     throw Error(std::string("mq_ctx_wait: ") + last_error());
                 }
                 if (p.cfg_.anchors) take_anchors(ctx[sl].handle(), *c);
+                if (p.cfg_.chains) take_chains(ctx[sl].handle(), *c);
             } catch (const std::exception &e) { p.fail(e.what()); }
             c->unparsed = false;
             inflight[sl] = nullptr;
@@ -284,7 +331,7 @@ class MapPipeline {
             }
             const auto tm0 = Clock::now();
             try {
-                const std::string err = format_chunk(*c, pw, unm_ != nullptr, ufa_ != nullptr, cfg_.anchors != nullptr);
+                const std::string err = format_chunk(*c, pw, unm_ != nullptr, ufa_ != nullptr, cfg_.anchors != nullptr, cfg_.chains != nullptr);
                 if (!err.empty()) fail(err);
             } catch (const std::exception &e) { fail(e.what()); }
             t_format_us_ += us_since(tm0);
@@ -316,6 +363,7 @@ class MapPipeline {
             if (unm_ && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm_);
             if (ufa_ && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa_);
             if (cfg_.anchors && !c->anchors.empty()) fwrite(c->anchors.data(), 1, c->anchors.size(), cfg_.anchors);
+            if (cfg_.chains && !c->chains.empty()) fwrite(c->chains.data(), 1, c->chains.size(), cfg_.chains);
             feed_.recycle(c);
             t_write_us_ += us_since(tw0);
         }

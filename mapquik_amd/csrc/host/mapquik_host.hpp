@@ -149,7 +149,7 @@ class Ctx {
     }
     Ctx(const Ctx &) = delete;
     Ctx &operator=(const Ctx &) = delete;
-    Ctx(Ctx &&o) noexcept : h_(o.h_), anchors_bytes_(o.anchors_bytes_) { o.h_ = nullptr; }
+    Ctx(Ctx &&o) noexcept : h_(o.h_), anchors_bytes_(o.anchors_bytes_), chains_bytes_(o.chains_bytes_) { o.h_ = nullptr; }
     ~Ctx() { mq_ctx_free(h_); }
     mq_ctx *handle() const { return h_; }
     // room for batches of up to max_reads reads in max_bytes bytes, so that the first batches do not grow the slot
@@ -168,10 +168,20 @@ class Ctx {
         anchors_bytes_ = max_bytes;
     }
     uint64_t anchors_bytes() const { return anchors_bytes_; }  // the chunk size the slot's anchor reservation was made for (0: none)
+    // --chains: spans and a chain pool for chunks of up to max_bytes raw bytes, by the same bounds: a read has no more chains than runs, and
+    // no more runs than k-min-mers
+    void reserve_chains(uint64_t max_bytes, double density) {
+        const uint64_t reads = std::min<uint64_t>(max_bytes / 4 + 1, (1u << 30) - 1);
+        const double f = std::min(1.0, 4.0 * (density > 0 ? density : 0.0) + 1.0 / 512.0);
+        const uint64_t chains = std::min<uint64_t>((uint64_t)((double)max_bytes * f) + 64, 0xFFFFFFFEull - 1);
+        if (mq_ctx_reserve_chains(h_, (uint32_t)reads, chains) != MQ_OK) throw Error("mq_ctx_reserve_chains: " + last_error());
+        chains_bytes_ = max_bytes;
+    }
+    uint64_t chains_bytes() const { return chains_bytes_; }
 
   private:
     mq_ctx *h_ = nullptr;
-    uint64_t anchors_bytes_ = 0;
+    uint64_t anchors_bytes_ = 0, chains_bytes_ = 0;
 };
 
 // The format! of src/mers.rs:181 for many reads: the same bytes as mq_format_paf, appended to a string, with the reference names and

@@ -111,7 +111,7 @@ static bool is_fasta_name(const std::string &n) {
 
 struct Opt {
     std::string reads, reference, prefix;
-    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false;
+    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false;
     long k = -1, l = -1, c = -1, s = -1, g = -1, threads = -1, b = -1, q = -1;
     double density = -1;
     int device = 0;
@@ -137,7 +137,7 @@ struct Opt {
 static void usage() {
     puts("mapquik 0.1.0 (HIP backend)\nOriginal implementation of mapquik, a fast HiFi read mapper.\n\n"
          "USAGE:\n    mapquik [FLAGS] [OPTIONS] [reads]\n\nFLAGS:\n        --debug\n        --low-memory\n        --nohpc\n        --nosimd\n"
-         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n\nOPTIONS:\n"
+         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
          "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
@@ -394,17 +394,18 @@ static void run_all(const std::vector<std::function<void()>> &tasks) {
 // that closes them.
 struct OutputFiles {
     const std::string paf_path;
-    FILE *paf, *unm = nullptr, *ufa = nullptr, *anc = nullptr;
-    OutputFiles(const std::string &prefix, bool unmapped, const std::string &second_fa, bool anchors = false) : paf_path(prefix + ".paf"), paf(fopen(paf_path.c_str(), "w")) {
+    FILE *paf, *unm = nullptr, *ufa = nullptr, *anc = nullptr, *chn = nullptr;
+    OutputFiles(const std::string &prefix, bool unmapped, const std::string &second_fa, bool anchors = false, bool chains = false) : paf_path(prefix + ".paf"), paf(fopen(paf_path.c_str(), "w")) {
         if (!paf) return;
         if (anchors) anc = fopen((prefix + ".anchors").c_str(), "w");
+        if (chains) chn = fopen((prefix + ".chains").c_str(), "w");
         if (unmapped) unm = fopen((prefix + ".unmapped.out").c_str(), "w");
         if (!second_fa.empty()) ufa = fopen(second_fa.c_str(), "w");
     }
     OutputFiles(const OutputFiles &) = delete;
     ~OutputFiles() { close(); }
     void close() {
-        for (FILE **f : {&paf, &unm, &ufa, &anc}) {
+        for (FILE **f : {&paf, &unm, &ufa, &anc, &chn}) {
             if (*f) fclose(*f);
             *f = nullptr;
         }
@@ -481,8 +482,9 @@ struct StreamSlots {
     const uint64_t chunk_bytes;  // what a slot has room for from the start
     const bool anchors;          // --anchors: every slot reserves spans and an anchor pool for chunk_bytes (Ctx::reserve_anchors states the bound)
     const double density;
-    StreamSlots(size_t n_submitters, uint64_t batch_bases, uint64_t bytes_in, bool anchors_ = false, double density_ = 0)
-        : of(n_submitters), chunk_bytes(std::min<uint64_t>(batch_bases + batch_bases / 8 + (1u << 20), bytes_in + 64)), anchors(anchors_), density(density_) {
+    const bool chains;           // --chains: the same for spans and a chain pool (Ctx::reserve_chains)
+    StreamSlots(size_t n_submitters, uint64_t batch_bases, uint64_t bytes_in, bool anchors_ = false, double density_ = 0, bool chains_ = false)
+        : of(n_submitters), chunk_bytes(std::min<uint64_t>(batch_bases + batch_bases / 8 + (1u << 20), bytes_in + 64)), anchors(anchors_), density(density_), chains(chains_) {
         for (auto &v : of) v.reserve((size_t)N_SLOTS);
     }
     bool complete(size_t w) const { return of[w].size() == (size_t)N_SLOTS; }
@@ -492,6 +494,7 @@ struct StreamSlots {
             of[w].emplace_back(h);
             of[w].back().reserve((uint32_t)std::min<uint64_t>(chunk_bytes / 16000 + 512, 1u << 24), chunk_bytes);  // (sized for long reads; a chunk of short reads makes its slot grow once)
             if (anchors) of[w].back().reserve_anchors(chunk_bytes, density);
+            if (chains) of[w].back().reserve_chains(chunk_bytes, density);
         }
     }
     void drop() {
@@ -675,7 +678,8 @@ static void teardown(const Opt &o, StreamSlots &slots, std::vector<std::unique_p
 // order.  second_fa != "": the reads left unmapped also go to that FASTA file (for the second pass).
 static int run_pass(const Opt &o, const Params &P, const std::string &reads_path, bool reads_fasta, bool ref_fasta, const std::string &prefix,
                     size_t threads, const std::string &second_fa) {
-    OutputFiles out(prefix, o.unmapped || !o.second.empty(), second_fa, o.anchors);
+    OutputFiles out(prefix, o.unmapped || !o.second.empty(), second_fa, o.anchors, o.chains);
+    if (o.chains && out.paf && !out.chn) { fprintf(stderr, "Couldn't create %s.chains\n", prefix.c_str()); return 101; }
     if (o.anchors && out.paf && !out.anc) { fprintf(stderr, "Couldn't create %s.anchors\n", prefix.c_str()); return 101; }
     if (!out.paf) { fprintf(stderr, "Couldn't create %s.paf\n", prefix.c_str()); return 101; }
 
@@ -714,7 +718,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
     // Submitting threads per GPU.  Chunks that are views of the mapped file are copied to the device from pageable memory: that
     // copy occupies the thread that asks for it, hence two (experimental path, MQ_FEEDER_MAPPED_FASTA=1; see Feeder::premap).
     const int n_sub = feed.mapped_views() ? 2 : 1;
-    StreamSlots slots((size_t)(o.gpus * n_sub), rt.batch_bases, feed.bytes_in(), o.anchors, P.density);
+    StreamSlots slots((size_t)(o.gpus * n_sub), rt.batch_bases, feed.bytes_in(), o.anchors, P.density, o.chains);
     const int n_buffers = g_knobs.prefetch ? 0 : rt.n_parse + N_SLOTS;  // chunk buffers page-locked ahead of the feeder's start
     EarlySetup early(slots, feed, n_sub, n_buffers);
     size_t first_ref_id = 0;
@@ -728,7 +732,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
     t0 = Clock::now();
     if (P.use_pfx && !ends_with(reads_path, ".gz") && !ends_with(reads_path, ".lz4")) puts("Warning: using experimental rust-parallelfastx (exciting!)");
     start_feed();
-    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density});
+    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density, out.chn});
     try {
         pipeline.run();
     } catch (...) {
@@ -761,6 +765,7 @@ int main(int argc, char **argv) {
         else if (a == "--parallelfastx") o.parallelfastx = true;
         else if (a == "--unmapped") o.unmapped = true;
         else if (a == "--anchors") o.anchors = true;
+        else if (a == "--chains") o.chains = true;
         else if (a == "-p" || a == "--prefix") { o.prefix = val(); o.has_prefix = true; }
         else if (a == "-k") o.k = atol(val());
         else if (a == "-l") o.l = atol(val());

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/mapquik_hip.h"
+
 namespace mq {
 
 // index of a 32-bit / 64-bit field in its block seen as an array of such words
@@ -20,6 +22,20 @@ constexpr int MQ_N_CLK = 16;  // stage clocks of a -DMQ_STAGE_CLOCKS build (the 
 struct ProbeStats {
     unsigned long long steps;    // slots visited beyond the home slot
     unsigned long long lookups;  // index lookups
+};
+// The chains output of a launch (mq_ctx_reserve_chains): what the CHN instantiations of the map kernels need beyond MapArgs.  It rides in
+// the launch sequence's counter block, in what used to be spare words, so that MapArgs -- the kernel arguments of EVERY instantiation -- stays
+// the size it was.  Written by the host behind the block's clearing, in stream order; all zero for a launch without the output.
+struct ChainRec;
+struct ChainCounters;
+struct ChainLaunch {
+    mq_chain *pool;
+    uint32_t cap;      // entries of the pool
+    uint32_t win_cap;  // records of a wave's chain window: at least the launch's Match window AND the records the LDS path chains (MAP_LDS_RECS)
+    ChainCounters *counters;  // the BATCH's block (below): not cleared per launch
+    ChainRec *windows; // per mapping wave: win_cap records, beside the wave's Match window (never IN it: pass C of the anchors reads that again)
+    mq_chain_span *spans;     // read r's span goes to spans[ids ? ids[r] : r], as the anchors' does
+    const uint32_t *ids;
 };
 // cleared by the host in front of every launch sequence
 struct MapCounters {
@@ -35,7 +51,8 @@ struct MapCounters {
     unsigned long long pool_cursor;  // entries of the pool handed out (pool_take)
     unsigned long long spare0;
     unsigned long long clk[MQ_N_CLK];  // -DMQ_STAGE_CLOCKS builds: cycles per stage, summed over waves (mq_last_stage_clocks)
-    unsigned long long spare1[8];
+    ChainLaunch chains;  // CHN instantiations only
+    unsigned long long spare1[2];
 };
 static_assert(sizeof(MapCounters) == 256, "the counter block of a launch sequence");
 static_assert(offsetof(MapCounters, seed_work) == 0 && offsetof(MapCounters, map_work) == 4 && offsetof(MapCounters, queue_len) == 8 &&
@@ -47,7 +64,8 @@ static_assert(offsetof(MapCounters, n_fast) == 16 && offsetof(MapCounters, n_gen
 static_assert(offsetof(MapCounters, probe) == 32 && offsetof(ProbeStats, steps) == 0 && offsetof(ProbeStats, lookups) == 8 && sizeof(ProbeStats) == 16,
               "probe statistics");
 static_assert(offsetof(MapCounters, pool_cursor) == 48, "pool cursor");
-static_assert(offsetof(MapCounters, clk) == 64 && offsetof(MapCounters, spare1) == 64 + 8 * MQ_N_CLK, "stage clocks");
+static_assert(offsetof(MapCounters, clk) == 64 && offsetof(MapCounters, chains) == 64 + 8 * MQ_N_CLK, "stage clocks");
+static_assert(sizeof(ChainLaunch) == 48 && offsetof(MapCounters, spare1) == 240, "the chains output's launch arguments");
 
 // ------------------------------------------------------------------ the index build's seeders (BuildScratch::info)
 // work cursors of seed_ref_kernel / seed_ref_general_kernel: RefSeedArgs::counters points at RefBuildInfo::work
@@ -114,5 +132,17 @@ struct AnchorCounters {
 static_assert(sizeof(AnchorCounters) == 16 && offsetof(AnchorCounters, cursor) == 0 && offsetof(AnchorCounters, dropped_reads) == 8 &&
                   offsetof(AnchorCounters, spare) == 12,
               "anchor counters");
+
+// ------------------------------------------------------------------ the chains output of a batch (mq_ctx::chn_counters = ChainLaunch::counters)
+// cleared by the host once per BATCH, in front of its main launch sequence -- not per launch, as MapCounters is: the batch's redo launches go
+// on claiming from the same cursor.  Written by chain_stage<CH, ANCH, true> (mq_chain.hpp).
+struct ChainCounters {
+    unsigned long long cursor;  // pool entries claimed; counts on past the pool's capacity, so it ends as what the batch needed
+    uint32_t dropped_reads;     // reads whose claim did not fit (span first = MQ_CHAINS_DROPPED)
+    uint32_t spare;
+};
+static_assert(sizeof(ChainCounters) == 16 && offsetof(ChainCounters, cursor) == 0 && offsetof(ChainCounters, dropped_reads) == 8 &&
+                  offsetof(ChainCounters, spare) == 12,
+              "chain counters");
 
 }  // namespace mq

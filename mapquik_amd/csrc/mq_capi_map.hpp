@@ -16,7 +16,11 @@ struct LaunchOpt {
     // the anchor output (mq_ctx_reserve_anchors) of a batch's redo launch: the batch's cursor goes on, the spans go where the map says
     bool anchor_redo = false;
     const uint32_t *d_anchor_ids = nullptr;  // MapArgs::anchor_ids
-    mq_ctx *anchors_of = nullptr;            // the context whose reservation the launch delivers to (nullptr: c itself; the arena's launch: its owner)
+    mq_ctx *anchors_of = nullptr;            // the context whose reservations (anchors, chains) the launch delivers to (nullptr: c itself; the arena's launch: its owner)
+    // the chains output (mq_ctx_reserve_chains) of a batch's redo launch, the same way; and the chain windows that go with scratch_override
+    bool chain_redo = false;
+    const uint32_t *d_chain_ids = nullptr;   // ChainLaunch::ids
+    ChainRec *chain_windows_override = nullptr;  // as many windows as scratch_override has, of chain_win_cap(cap_override) records
 };
 
 // A batch of n reads on a context with an anchor reservation is refused when it has more reads than spans.  The entry points ask before
@@ -26,6 +30,16 @@ static int anchors_admit(const mq_ctx *c, uint32_t n) {
     if (c->anch_reads && n > c->anch_reads)
         return set_err(MQ_EINVAL, "more reads in the batch than the context's anchor reservation holds (mq_ctx_reserve_anchors: max_reads)");
     return MQ_OK;
+}
+// ... the same for a chains reservation
+static int chains_admit(const mq_ctx *c, uint32_t n) {
+    if (c->chn_reads && n > c->chn_reads)
+        return set_err(MQ_EINVAL, "more reads in the batch than the context's chains reservation holds (mq_ctx_reserve_chains: max_reads)");
+    return MQ_OK;
+}
+static int outputs_admit(const mq_ctx *c, uint32_t n) {
+    int rc = anchors_admit(c, n);
+    return rc ? rc : chains_admit(c, n);
 }
 
 // One launch sequence on stream `st` using the context's scratch.  ctx_ensure(c, n, total_bases, f16) must have succeeded.
@@ -41,6 +55,17 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(ac->anch_counters, 0, sizeof(AnchorCounters), st));  // once per batch: its redo launches claim from the same cursor
         ac->anch_n = n;  // from here on mq_ctx_anchors describes this batch
+    }
+    // ... and one with a chains reservation the chains pair (both: the pair that writes both)
+    const bool chn = ac->chn_reads != 0 && !o.instrumented && !o.d_dump && !idx->split;
+    if (chn) {
+        if (o.scratch_override && !o.chain_windows_override) return set_err(MQ_ESTATE, "a redo launch of a chains context without chain windows");
+        if (!o.chain_redo) {
+            int rc = chains_admit(ac, n);
+            if (rc) return rc;
+            HIPCHK(hipMemsetAsync(ac->chn_counters, 0, sizeof(ChainCounters), st));  // once per batch, as the anchors'
+            ac->chn_n = n;  // from here on mq_ctx_chains describes this batch
+        }
     }
     HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(MapCounters), st));
     HIPCHK(hipEventRecord(c->ev0, st));
@@ -79,16 +104,28 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     A.anchors.counters = anch ? ac->anch_counters.p : nullptr;
     A.anchor_spans = anch ? ac->anch_spans.p : nullptr;
     A.anchor_ids = anch ? o.d_anchor_ids : nullptr;
+    if (chn) {
+        // the chains output's launch arguments: into the counter block, behind its clearing (from pageable memory: the bytes are taken now)
+        ChainLaunch cl;
+        cl.pool = ac->chn_pool.p;
+        cl.cap = (uint32_t)ac->chn_cap;
+        cl.win_cap = chain_win_cap(A.cap_matches);
+        cl.counters = ac->chn_counters.p;
+        cl.windows = o.scratch_override ? o.chain_windows_override : ac->chn_windows.p;
+        cl.spans = ac->chn_spans.p;
+        cl.ids = o.d_chain_ids;
+        HIPCHK(hipMemcpyAsync(&c->d_counter.p->chains, &cl, sizeof(ChainLaunch), hipMemcpyHostToDevice, st));
+    }
     if (!idx->split) {
         if (n > WORK_ID_MASK) return set_err(MQ_EINVAL, "more than 2^30 - 1 reads in one batch");
         hipLaunchKernelGGL(order_reads_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, A);  // the launch order (and map_kernel's work descriptors)
         uint32_t grid = fused_grid(idx, n);
         if (o.grid_override) grid = std::min(grid, o.grid_override);
-        if (anch) grid = std::min(grid, idx->grid_fused_anchors);
+        if (anch || chn) grid = std::min(grid, idx->grid_fused_outputs);
         const dim3 blk(64 * MAP_WAVES);
         // (a seeding variant other than the frozen reading takes the instantiation built with the variants; the frozen reading with the
         // parameters of a MAP_SPECS entry takes the pair compiled for them)
-        const MapPair &kp = map_pair_of(idx, o.instrumented, &c->last_spec, anch);
+        const MapPair &kp = map_pair_of(idx, o.instrumented, &c->last_spec, anch, chn);
         hipLaunchKernelGGL(kp.map, dim3(grid), blk, 0, st, A);
         HIPCHK(hipGetLastError());
         // the reads the fast seeder declined (queue length on the device: map_kernel's grid, its waves leave at once when there are none)
@@ -121,6 +158,10 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
         HIPCHK(hipEventRecord(ac->anch_done, st));
         ac->anch_ran = true;
     }
+    if (chn) {
+        HIPCHK(hipEventRecord(ac->chn_done, st));
+        ac->chn_ran = true;
+    }
     return MQ_OK;
 }
 
@@ -151,10 +192,12 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
     int rc = ctx_ensure(c, (uint32_t)redo.size(), sub_total, 65536u);
     if (rc) return rc;
     Buf<MatchRec> big;
+    Buf<ChainRec> big_chains;  // (a context with a chains reservation) the redo's chain windows, beside its Match windows
     Buf<uint8_t> d_sb;
     Buf<uint64_t> d_so;
     Buf<mq_hit> d_sh;
     hipError_t e = big.try_alloc((uint64_t)rgrid * waves * cap);
+    if (e == hipSuccess && c->chn_reads) e = big_chains.try_alloc((uint64_t)rgrid * waves * chain_win_cap(cap));
     if (e == hipSuccess) e = d_sb.try_alloc(sub_total + 1);
     if (e == hipSuccess) e = d_so.try_alloc(so.size());
     if (e == hipSuccess) e = d_sh.try_alloc(redo.size());
@@ -172,6 +215,12 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
             e = hipMemcpyAsync(c->anch_ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
             o.anchor_redo = true;
             o.d_anchor_ids = c->anch_ids;
+        }
+        if (c->chn_reads && e == hipSuccess) {  // ... and its chains
+            e = hipMemcpyAsync(c->chn_ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            o.chain_redo = true;
+            o.d_chain_ids = c->chn_ids;
+            o.chain_windows_override = big_chains;
         }
         if (e == hipSuccess) rrc = launch_map(c, d_sb, d_so, (uint32_t)redo.size(), d_sh, c->stream, o);
     }
@@ -242,7 +291,7 @@ static int ctx_submit(mq_ctx *c, const uint8_t *bases, uint64_t buf_bytes, const
     int rc = ctx_require_idle(c);
     if (rc) return rc;
     if (!idx->finalized) return set_err(MQ_ESTATE, "index not finalized");
-    if ((rc = anchors_admit(c, n))) return rc;
+    if ((rc = outputs_admit(c, n))) return rc;
     if (n == 0) return MQ_OK;
     if ((rc = use_device(idx))) return rc;
     if ((rc = c->h_off.ensure((uint64_t)n + 1))) return rc;  // (ahead of the rest: the offsets are checked into it)
@@ -325,7 +374,8 @@ static int ctx_reserve_redo(mq_ctx *c, uint32_t max_reads, uint32_t max_read_len
     if ((rc = ctx_ensure(&a->sub, max_reads, (uint64_t)max_reads * stride, 65536u))) return rc;
     if ((rc = a->bases.alloc((uint64_t)max_reads * stride)) || (rc = a->offsets.alloc((uint64_t)max_reads + 1)) || (rc = a->lens.alloc(max_reads)) ||
         (rc = a->ids.alloc(max_reads)) || (rc = a->src.alloc(max_reads)) || (rc = a->hits.alloc(max_reads)) ||
-        (rc = a->windows.alloc((uint64_t)a->grid * REDO_WAVES * a->cap)) || (rc = a->counters.alloc(1)))
+        (rc = a->windows.alloc((uint64_t)a->grid * REDO_WAVES * a->cap)) || (rc = a->counters.alloc(1)) ||
+        (c->chn_reads && (rc = a->chain_windows.alloc((uint64_t)a->grid * REDO_WAVES * chain_win_cap(a->cap)))))
         return rc;
     std::vector<uint64_t> slot_at((size_t)max_reads + 1);
     for (size_t j = 0; j <= max_reads; ++j) slot_at[j] = j * stride;
@@ -345,7 +395,8 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     HIPCHK(hipMemsetAsync(a.counters, 0, sizeof(RedoCounters), st));
     HIPCHK(hipMemsetAsync(a.lens, 0, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims is a read of length 0
     const bool anch = c->anch_reads != 0 && !c->idx->split;
-    if (anch) HIPCHK(hipMemsetAsync(a.ids, 0xFF, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims writes no span
+    const bool chn = c->chn_reads != 0 && !c->idx->split;
+    if (anch || chn) HIPCHK(hipMemsetAsync(a.ids, 0xFF, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims writes no span
     if ((rc = launch(redo_collect_kernel, (n + 255u) / 256u, 256, st, d_out, d_offsets, n, a.max_reads, a.max_read_len, a.counters, a.ids, a.src, a.lens))) return rc;
     if ((rc = launch(redo_copy_kernel, (a.max_reads + REDO_COPY_WAVES - 1u) / REDO_COPY_WAVES, 64 * REDO_COPY_WAVES, st, d_bases, a.src, a.lens, a.max_reads, a.bases, a.stride))) return rc;
     LaunchOpt o;
@@ -358,6 +409,12 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
         o.anchor_redo = true;
         o.d_anchor_ids = a.ids;
         o.anchors_of = c;
+    }
+    if (chn) {
+        o.chain_redo = true;
+        o.d_chain_ids = a.ids;
+        o.anchors_of = c;
+        o.chain_windows_override = a.chain_windows;
     }
     if ((rc = launch_map(&a.sub, a.bases, a.offsets, a.max_reads, a.hits, st, o))) return rc;
     if ((rc = launch(redo_scatter_kernel, (a.max_reads + 255u) / 256u, 256, st, a.hits, a.ids, a.counters, a.max_reads, d_out))) return rc;
@@ -404,7 +461,7 @@ static int ctx_reserve_anchors(mq_ctx *c, uint32_t max_reads, uint64_t max_ancho
         if (max_reads == 0 || max_anchors == 0) return set_err(MQ_EINVAL, "max_reads and max_anchors must both be positive (or both 0: release)");
         if (max_reads > WORK_ID_MASK || max_anchors >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and max_anchors below 2^32 - 1");
         if (idx->split) return set_err(MQ_EINVAL, "the split pipeline (MQ_PIPELINE=split) writes no anchors: reserve them on an index that runs the fused kernels");
-        if ((rc = ensure_anchors_geometry(idx))) return rc;
+        if ((rc = ensure_outputs_geometry(idx))) return rc;
         if ((rc = pool.alloc(max_anchors)) || (rc = spans.alloc(max_reads)) || (rc = counters.alloc(1)) || (rc = ids.alloc(max_reads)) ||
             (rc = h_pool.alloc(max_anchors)) || (rc = h_spans.alloc(max_reads)) || (rc = h_counters.alloc(1)))
             return rc;
@@ -460,6 +517,89 @@ static int ctx_anchors_device(mq_ctx *c, const mq_anchor_span **d_spans, const m
     return MQ_OK;
 }
 
+// ---- the chains output (mq_ctx_reserve_chains): the anchors' plumbing once more, plus the chain windows -- the context's, and its redo
+// arena's when it has one (an arena reserved later allocates its own: ctx_reserve_redo)
+
+// (0, 0): the reservation goes.  A failure leaves the context with the reservation it had.
+static int ctx_reserve_chains(mq_ctx *c, uint32_t max_reads, uint64_t max_chains) {
+    mq_index *idx = c->idx;
+    int rc = ctx_require_idle(c);
+    if (rc) return rc;
+    if ((rc = use_device(idx))) return rc;
+    const bool release = max_reads == 0 && max_chains == 0;
+    Buf<mq_chain> pool;
+    Buf<mq_chain_span> spans;
+    Buf<ChainCounters> counters;
+    Buf<uint32_t> ids;
+    Buf<ChainRec> windows, arena_windows;
+    PinnedBuf<mq_chain> h_pool;
+    PinnedBuf<mq_chain_span> h_spans;
+    PinnedBuf<ChainCounters> h_counters;
+    hipEvent_t done = nullptr;
+    if (!release) {
+        if (max_reads == 0 || max_chains == 0) return set_err(MQ_EINVAL, "max_reads and max_chains must both be positive (or both 0: release)");
+        if (max_reads > WORK_ID_MASK || max_chains >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and max_chains below 2^32 - 1");
+        if (idx->split) return set_err(MQ_EINVAL, "the split pipeline (MQ_PIPELINE=split) writes no chains: reserve them on an index that runs the fused kernels");
+        if ((rc = ensure_outputs_geometry(idx))) return rc;
+        if ((rc = pool.alloc(max_chains)) || (rc = spans.alloc(max_reads)) || (rc = counters.alloc(1)) || (rc = ids.alloc(max_reads)) ||
+            (rc = windows.alloc((uint64_t)map_waves_for(idx, max_reads) * chain_win_cap(idx->cap_matches))) ||
+            (c->redo && (rc = arena_windows.alloc((uint64_t)c->redo->grid * REDO_WAVES * chain_win_cap(c->redo->cap)))) ||
+            (rc = h_pool.alloc(max_chains)) || (rc = h_spans.alloc(max_reads)) || (rc = h_counters.alloc(1)))
+            return rc;
+        if (!c->chn_done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    }
+    if (c->chn_ran) (void)hipEventSynchronize(c->chn_done);  // the stream of the last launch has passed the arrays that go
+    c->chn_pool = std::move(pool);
+    c->chn_spans = std::move(spans);
+    c->chn_counters = std::move(counters);
+    c->chn_ids = std::move(ids);
+    c->chn_windows = std::move(windows);
+    if (c->redo) c->redo->chain_windows = std::move(arena_windows);
+    c->h_chn_pool = std::move(h_pool);
+    c->h_chn_spans = std::move(h_spans);
+    c->h_chn_counters = std::move(h_counters);
+    if (done) c->chn_done.h = done;
+    c->chn_reads = max_reads;
+    c->chn_cap = max_chains;
+    c->chn_ran = false;
+    c->chn_n = 0;
+    return MQ_OK;
+}
+
+// host copies of the last batch's spans, chains and counters, once everything that writes them is done
+static int ctx_chains(mq_ctx *c, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                      uint32_t *dropped_reads) {
+    if (!c->chn_reads) return set_err(MQ_ESTATE, "no chains reserved on this context: call mq_ctx_reserve_chains first");
+    if (c->fx_kind != FxKind::None) return set_err(MQ_ESTATE, "context has a submitted piece: call mq_ctx_wait_fasta first");
+    int rc;
+    if (c->pending && (rc = ctx_wait(c))) return rc;  // (the host-driven redo, which delivers the redone reads' chains, runs there)
+    *spans = c->h_chn_spans;
+    *chains = c->h_chn_pool;
+    *n_reads = 0;
+    *stored = *needed = 0;
+    *dropped_reads = 0;
+    if (!c->chn_ran || c->chn_n == 0) return MQ_OK;  // no batch yet, or one without reads
+    if ((rc = use_device(c->idx))) return rc;
+    HIPCHK(hipEventSynchronize(c->chn_done));
+    HIPCHK(hipMemcpy(c->h_chn_counters, c->chn_counters, sizeof(ChainCounters), hipMemcpyDeviceToHost));
+    const ChainCounters &v = *c->h_chn_counters.p;
+    const uint64_t have = std::min<uint64_t>(v.cursor, c->chn_cap);
+    HIPCHK(hipMemcpy(c->h_chn_spans, c->chn_spans, (size_t)c->chn_n * sizeof(mq_chain_span), hipMemcpyDeviceToHost));
+    if (have) HIPCHK(hipMemcpy(c->h_chn_pool, c->chn_pool, (size_t)have * sizeof(mq_chain), hipMemcpyDeviceToHost));
+    *n_reads = c->chn_n;
+    *stored = have;
+    *needed = v.cursor;
+    *dropped_reads = v.dropped_reads;
+    return MQ_OK;
+}
+
+static int ctx_chains_device(mq_ctx *c, const mq_chain_span **d_spans, const mq_chain **d_chains) {
+    if (!c->chn_reads) return set_err(MQ_ESTATE, "no chains reserved on this context: call mq_ctx_reserve_chains first");
+    *d_spans = c->chn_spans;
+    *d_chains = c->chn_pool;
+    return MQ_OK;
+}
+
 static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases, mq_hit *d_out,
                           hipStream_t st, bool instrumented = false) {
     mq_index *idx = c->idx;
@@ -468,7 +608,7 @@ static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     int rc = ctx_require_idle(c);
     if (rc) return rc;
     if ((rc = use_device(idx))) return rc;
-    if (!instrumented && (rc = anchors_admit(c, n))) return rc;
+    if (!instrumented && (rc = outputs_admit(c, n))) return rc;
     if ((rc = ctx_ensure(c, n, total_bases, list_f16(idx)))) return rc;
     LaunchOpt o;
     o.instrumented = instrumented;
@@ -576,7 +716,7 @@ static int fx_take_info(mq_ctx *c) {
 template <typename F>
 static int fx_map_found(mq_ctx *c, const uint8_t *d_bytes, const uint64_t *d_offsets, const uint32_t *d_lens, uint32_t n, uint64_t total_bytes, F side_copies) {
     int rc;
-    if ((rc = anchors_admit(c, n))) return rc;
+    if ((rc = outputs_admit(c, n))) return rc;
     if ((rc = c->h_out.ensure((uint64_t)n))) return rc;
     if ((rc = c->st_out.ensure((uint64_t)n))) return rc;
     if ((rc = ctx_ensure(c, n, total_bytes, list_f16(c->idx)))) return rc;
@@ -820,6 +960,45 @@ int mq_ctx_anchors_device(mq_ctx *ctx, const mq_anchor_span **d_spans, const mq_
     });
 }
 
+int mq_ctx_reserve_chains(mq_ctx *ctx, uint32_t max_reads, uint64_t max_chains) {
+    return guarded([&]() -> int {
+        if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
+        return ctx_reserve_chains(ctx, max_reads, max_chains);
+    });
+}
+
+int mq_map_reserve_chains(mq_index *idx, uint32_t max_reads, uint64_t max_chains) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_reserve_chains(idx->def_ctx.get(), max_reads, max_chains);
+    });
+}
+
+int mq_ctx_chains(mq_ctx *ctx, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                  uint32_t *dropped_reads) {
+    return guarded([&]() -> int {
+        if (!ctx || !spans || !chains || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_chains(ctx, spans, chains, n_reads, stored, needed, dropped_reads);
+    });
+}
+
+int mq_map_chains(mq_index *idx, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                  uint32_t *dropped_reads) {
+    return guarded([&]() -> int {
+        if (!idx || !spans || !chains || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        return ctx_chains(idx->def_ctx.get(), spans, chains, n_reads, stored, needed, dropped_reads);
+    });
+}
+
+int mq_ctx_chains_device(mq_ctx *ctx, const mq_chain_span **d_spans, const mq_chain **d_chains) {
+    return guarded([&]() -> int {
+        if (!ctx || !d_spans || !d_chains) return set_err(MQ_EINVAL, "bad arguments");
+        return ctx_chains_device(ctx, d_spans, d_chains);
+    });
+}
+
 int mq_map_batch(mq_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n, mq_hit *out) {
     return guarded([&]() -> int {
         if (!idx || (n && (!offsets || !out))) return set_err(MQ_EINVAL, "bad arguments");
@@ -928,6 +1107,19 @@ int mq_format_paf(const mq_index *idx, const char *q_id, uint64_t q_len, const m
                          hit->rc ? "-" : "+", it->second.first.c_str(), r_len, hit->r_start, hit->r_end, hit->score, r_len,
                          hit->mapq);
         return w;
+    });
+}
+
+int mq_format_paf_chain(const mq_index *idx, const char *q_id, uint64_t q_len, const mq_chain *chain, char *buf, size_t cap) {
+    return guarded([&]() -> int {
+        if (!idx || !q_id || !chain || !buf) return set_err(MQ_EINVAL, "bad arguments");
+        auto it = idx->refs.find(chain->ref_id);
+        if (it == idx->refs.end()) return set_err(MQ_EINVAL, "unknown ref_id in chain");
+        const unsigned long long r_len = it->second.second;
+        // the columns of mq_format_paf, from the words the two records share
+        const unsigned long long qs = ((unsigned long long)chain->q_start_hi << 32) | chain->q_start, qe = ((unsigned long long)chain->q_end_hi << 32) | chain->q_end;
+        return snprintf(buf, cap, "%s\t%llu\t%llu\t%llu\t%s\t%s\t%llu\t%u\t%u\t%u\t%llu\t%u", q_id, (unsigned long long)q_len, qs, qe,
+                        chain->rc ? "-" : "+", it->second.first.c_str(), r_len, chain->r_start, chain->r_end, chain->score, r_len, chain->mapq);
     });
 }
 

@@ -59,16 +59,95 @@ struct AnchorOut {
     AnchorCounters *counters;
 };
 
+// The chains output of a launch (CHN instantiations only: mq_ctx_reserve_chains).  A candidate as the candidate loop leaves it, staged
+// until the read's number of candidates is known: 32 bytes, two 16-byte words
+struct ChainRec {
+    uint32_t ref, rc_mapq;   // rc in bit 0, mapq == 60 in bit 1
+    uint32_t q_start, q_end; // first.q_start, last.q_end (as Match stores it)
+    uint32_t r_a, r_b;       // the two r ends get_match takes (chain_r_ends), r_b as Match stores it
+    uint32_t score, nkept;
+};
+static_assert(sizeof(ChainRec) == 32 && sizeof(mq_chain) == 48 && sizeof(mq_chain) == sizeof(mq_hit), "chain records");
+using ChainOut = ChainLaunch;  // (mq_blocks.hpp: the launch's arguments live in its counter block)
+
+// get_match's choice of reference ends (src/chain.rs:162-168) as a candidate is staged: r_start, and r_end as Match stores it.  A staged
+// record comes back through find_coords as a chain of ONE run whose first and last are the same record -- the choice is made once, here.
+__device__ __forceinline__ void chain_r_ends(bool rc, uint32_t nkept, const MatchRec &first, const MatchRec &last, uint32_t &r_a, uint32_t &r_b) {
+    if (rc && nkept > 1) {
+        r_a = last.r_start;
+        r_b = first.r_end;
+    } else {
+        r_a = first.r_start;
+        r_b = last.r_end;
+    }
+}
+
+// get_match's `- 1`s and choice of reference ends (src/chain.rs:162-168) and find_coords (src/mers.rs:131-183) for one chain of N_RUNS kept
+// runs, from the ends of its first and last run: declares qs64, qe64 (columns 3, 4, 64-bit), frs, fre (columns 8, 9) in the scope it
+// stands in.  usize arithmetic, wrapping like a release build: exc_s / exc_e wrap when the run's r_end lies beyond THIS reference's end (a
+// run the precedence quirk extended onto another, longer reference); all 64 bits go out.
+// ONE copy of the arithmetic, as a statement macro and not only as a function: the hit takes it in place, the chains output through
+// find_coords below.  Five wordings of a __forceinline__ function called from the hit path each moved the SGPR spill counts of three to
+// six existing map_declined_kernel instantiations (kernels that spill 200-350 SGPRs; which ones moved changed with the wording), and
+// the kernels' code is held identical across changes; these statements in place leave all of them as they were.
+#define MQ_FIND_COORDS(RC, FIRST_Q_START, LAST_Q_END, FIRST_R_START, FIRST_R_END, LAST_R_START, LAST_R_END, N_RUNS, Q_LEN, R_LEN) \
+    const uint64_t q_start = (FIRST_Q_START);                                                                                    \
+    const uint64_t q_end = (uint64_t)(LAST_Q_END) - 1;                                                                           \
+    uint64_t r_start, r_end;                                                                                                     \
+    if ((RC) && (N_RUNS) > 1) {                                                                                                  \
+        r_start = (LAST_R_START);                                                                                                \
+        r_end = (uint64_t)(FIRST_R_END) - 1;                                                                                     \
+    } else {                                                                                                                     \
+        r_start = (FIRST_R_START);                                                                                               \
+        r_end = (uint64_t)(LAST_R_END) - 1;                                                                                      \
+    }                                                                                                                            \
+    const uint64_t r_len = (R_LEN);                                                                                              \
+    const uint64_t tail = (Q_LEN) - q_end - 1;                                                                                   \
+    uint64_t frs, fre, exc_s, exc_e;                                                                                             \
+    if (!(RC)) {                                                                                                                 \
+        if (r_start >= q_start) { frs = r_start - q_start; exc_s = q_start; }                                                    \
+        else { frs = 0; exc_s = r_start; }                                                                                       \
+        if (r_end + tail <= r_len - 1) { fre = r_end + tail; exc_e = tail; }                                                     \
+        else { fre = r_len - 1; exc_e = r_len - r_end - 1; }                                                                     \
+    } else {                                                                                                                     \
+        if (r_end + q_start <= r_len - 1) { fre = r_end + q_start; exc_s = q_start; }                                            \
+        else { fre = r_len - 1; exc_s = r_len - r_end - 1; }                                                                     \
+        if (r_start >= tail) { frs = r_start - tail; exc_e = tail; }                                                             \
+        else { frs = 0; exc_e = r_start; }                                                                                       \
+    }                                                                                                                            \
+    const uint64_t qs64 = q_start - exc_s, qe64 = q_end + exc_e;
+
+// ... as the device function of (rc, first / last ends, n_runs, q_len, r_len): what the chains output's copy-out calls per candidate
+struct ChainCoords {
+    uint64_t qs64, qe64, frs, fre;
+};
+__device__ __forceinline__ ChainCoords find_coords(bool rc, uint32_t first_q_start, uint32_t last_q_end, uint32_t first_r_start, uint32_t first_r_end,
+                                                   uint32_t last_r_start, uint32_t last_r_end, uint32_t n_runs, uint64_t q_len, uint64_t r_len_of_ref) {
+    MQ_FIND_COORDS(rc, first_q_start, last_q_end, first_r_start, first_r_end, last_r_start, last_r_end, n_runs, q_len, r_len_of_ref)
+    ChainCoords o;
+    o.qs64 = qs64;
+    o.qe64 = qe64;
+    o.frs = frs;
+    o.fre = fre;
+    return o;
+}
+
 // Per-reference Chain::get_match + best-of + find_coords.  CH = lanes used per chunk (64; smaller only in tests
 // so that ordinary inputs exercise the multi-chunk path).
 // first: lane i's record i already in a register (the caller read the first chunk itself); with nm <= CH nothing is read here then
 // ANCH: the runs of the winning chain -- the list filter_matches_max leaves, src/chain.rs:123-129 -- go to ao's pool as well, and `span`
 // says where ({0, 0} for a read that is not mapped).  Every line of that sits under `if constexpr (ANCH)`: the instantiations without it
 // are the code they were.
-template <int CH, bool ANCH = false>
+// CHN: every candidate chain goes to co's pool (mq_ctx_reserve_chains), in the order the loop below visits the references -- that of each
+// reference's first run in the read -- and `cspan` says where.  The number of candidates is known only when the loop ends and a read's
+// entries are contiguous, claimed with ONE atomic add: so the loop stages each candidate in the wave's chain window `cwin`, and the copy-out
+// behind the loop finishes them (find_coords against each chain's own reference length, MQ_CHAIN_TOP) with a lane per candidate.  Every
+// line of that sits under `if constexpr (CHN)`.
+template <int CH, bool ANCH = false, bool CHN = false>
 __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint32_t nm, const DevParams &P, uint64_t q_len,
                                             const uint64_t *__restrict__ ref_lens, mq_hit &out, const MatchRec *first = nullptr,
-                                            const AnchorOut *ao = nullptr, mq_anchor_span *span = nullptr) {
+                                            const AnchorOut *ao = nullptr, mq_anchor_span *span = nullptr, const ChainOut *co = nullptr,
+                                            ChainRec *__restrict__ cwin = nullptr, mq_chain_span *cspan = nullptr) {
     const uint32_t lane = lane_id();
     // find_largest_two_chains state (src/mers.rs:110-129)
     uint32_t max_count = 0, second_count = 0, n_cand = 0;
@@ -134,6 +213,24 @@ __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint
             pending &= ~__ballot(v0 && m.ref == r);
             if (nkept == 0) continue;  // len_f == 0 => None (cannot happen: the anchor is compatible with itself)
             // find_largest_two_chains update (strict >)
+            if constexpr (CHN) {
+                // candidate n_cand's tuple (wave-uniform) into the chain window, by lane 0: two 16-byte vector stores.  A candidate has at
+                // least one run of its own, so n_cand < nm <= the window's records here (ChainOut::win_cap): the stage cannot overflow.
+                if (lane == 0) {
+                    const bool crc = first.rc != 0;
+                    ChainRec cr;
+                    cr.ref = r;
+                    cr.rc_mapq = (crc ? 1u : 0u) | (((P.s != 0 && P.c != 0) && (nkept >= P.c || score >= P.s)) ? 2u : 0u);
+                    cr.q_start = first.q_start;
+                    cr.q_end = last.q_end;
+                    chain_r_ends(crc, nkept, first, last, cr.r_a, cr.r_b);
+                    cr.score = score;
+                    cr.nkept = nkept;
+                    uint4 *w = reinterpret_cast<uint4 *>(cwin + n_cand);
+                    w[0] = make_uint4(cr.ref, cr.rc_mapq, cr.q_start, cr.q_end);
+                    w[1] = make_uint4(cr.r_a, cr.r_b, cr.score, cr.nkept);
+                }
+            }
             n_cand++;
             if (score > max_count) {
                 second_count = max_count;
@@ -150,6 +247,35 @@ __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint
             }
         }
     }
+    if constexpr (CHN) {
+        // the copy-out, for every read with a candidate (mapped or tied).  This wave's staged records are read back by this wave: the
+        // ordering the Match window has between the runs' stores and this stage's loads (map_read) -- the stores acknowledged, the wave
+        // together -- and plain loads.  The claim first: ONE atomic add of n_cand on the pool cursor, which counts on past the capacity.
+        if (n_cand) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (map_read's statement in front of this stage, verbatim: not a new fence)
+            wave_sync();
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(&co->counters->cursor, (unsigned long long)n_cand);
+            at = rdlane64(at, 0);
+            cspan->count = n_cand;
+            if (at + n_cand > (unsigned long long)co->cap) {
+                if (lane == 0) atomicAdd(&co->counters->dropped_reads, 1u);
+                cspan->first = MQ_CHAINS_DROPPED;
+            } else {
+                cspan->first = (uint32_t)at;
+                for (uint32_t c = lane; c < n_cand; c += 64u) {  // rounds of 64, lane = candidate
+                    const uint4 *w = reinterpret_cast<const uint4 *>(cwin + c);
+                    const uint4 w0 = w[0], w1 = w[1];
+                    // (the staged ends are the ones get_match chose: as a chain of one run they come through the choice unchanged)
+                    const ChainCoords fc = find_coords((w0.y & 1u) != 0, w0.z, w0.w, w1.x, w1.y, w1.x, w1.y, 1u, q_len, ref_lens[w0.x]);
+                    uint4 *dst = reinterpret_cast<uint4 *>(co->pool + at + c);  // 48 bytes: three 16-byte vector stores
+                    dst[0] = make_uint4(w1.z == max_count ? MQ_CHAIN_TOP : 0u, w0.x, w0.y & 1u, (w0.y & 2u) ? 60u : 0u);
+                    dst[1] = make_uint4((uint32_t)fc.qs64, (uint32_t)fc.qe64, (uint32_t)fc.frs, (uint32_t)fc.fre);
+                    dst[2] = make_uint4(w1.z, w1.w, (uint32_t)(fc.qs64 >> 32), (uint32_t)(fc.qe64 >> 32));
+                }
+            }
+        }
+    }
     out.status = MQ_HIT_UNMAPPED;
     out.ref_id = 0;
     out.rc = 0;
@@ -159,38 +285,12 @@ __device__ __forceinline__ void chain_stage(MatchRec *__restrict__ scratch, uint
     if (n_cand > 1 && max_count == second_count) return;  // determine_best_match: tie => None (src/mers.rs:106)
     // get_match coordinates (src/chain.rs:162-168), usize arithmetic
     const bool rc = bfirst.rc != 0;
-    const uint64_t q_start = bfirst.q_start;
-    const uint64_t q_end = (uint64_t)blast.q_end - 1;
-    uint64_t r_start, r_end;
-    if (rc && b_len > 1) {
-        r_start = blast.r_start;
-        r_end = (uint64_t)bfirst.r_end - 1;
-    } else {
-        r_start = bfirst.r_start;
-        r_end = (uint64_t)blast.r_end - 1;
-    }
-    // find_coords (src/mers.rs:131-183)
-    const uint64_t r_len = ref_lens[b_ref];
-    const uint64_t tail = q_len - q_end - 1;
-    uint64_t frs, fre, exc_s, exc_e;
-    if (!rc) {
-        if (r_start >= q_start) { frs = r_start - q_start; exc_s = q_start; }
-        else { frs = 0; exc_s = r_start; }
-        if (r_end + tail <= r_len - 1) { fre = r_end + tail; exc_e = tail; }
-        else { fre = r_len - 1; exc_e = r_len - r_end - 1; }
-    } else {
-        if (r_end + q_start <= r_len - 1) { fre = r_end + q_start; exc_s = q_start; }
-        else { fre = r_len - 1; exc_s = r_len - r_end - 1; }
-        if (r_start >= tail) { frs = r_start - tail; exc_e = tail; }
-        else { frs = 0; exc_e = r_start; }
-    }
+    // get_match coordinates (src/chain.rs:162-168) and find_coords (src/mers.rs:131-183)
+    MQ_FIND_COORDS(rc, bfirst.q_start, blast.q_end, bfirst.r_start, bfirst.r_end, blast.r_start, blast.r_end, b_len, q_len, ref_lens[b_ref])
     out.status = MQ_HIT_MAPPED;
     out.ref_id = b_ref;
     out.rc = rc ? 1u : 0u;
     out.mapq = b_mapq;
-    // usize arithmetic, wrapping like a release build: exc_s / exc_e wrap when the run's r_end lies beyond THIS reference's end
-    // (a run the precedence quirk extended onto another, longer reference); all 64 bits go out
-    const uint64_t qs64 = q_start - exc_s, qe64 = q_end + exc_e;
     out.q_start = (uint32_t)qs64;
     out.q_end = (uint32_t)qe64;
     out.q_start_hi = (uint32_t)(qs64 >> 32);

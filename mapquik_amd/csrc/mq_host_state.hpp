@@ -94,6 +94,22 @@ struct mq_ctx {
     ScopedEvent anch_done;                // behind the last launch sequence that wrote anchors (recorded on ITS stream: the context's, or the caller's)
     bool anch_ran = false;                // ... recorded at least once
     uint32_t anch_n = 0;                  // reads of the last batch that delivered anchors
+    // mq_ctx_reserve_chains: the chains output of the context's batches, member for member what the anchors have (chn_reads == 0: no
+    // reservation), and the chain windows of the context's launches.  Allocated at the reservation, never by a launch -- but for the windows
+    // of the host-driven redo, whose size is the longest redone read's: they live as long as that redo's Match windows do (redo_relaunch).
+    uint32_t chn_reads = 0;               // max_reads
+    uint64_t chn_cap = 0;                 // max_chains (< 2^32 - 1)
+    Buf<mq_chain> chn_pool;
+    Buf<mq_chain_span> chn_spans;
+    Buf<ChainCounters> chn_counters;      // one block (mq_blocks.hpp), cleared in front of every batch's main launch
+    Buf<uint32_t> chn_ids;                // the host-driven redo's read numbers (ChainLaunch::ids of redo_relaunch)
+    Buf<ChainRec> chn_windows;            // a window of chain_win_cap(cap_matches) records for every mapping wave a batch of max_reads reads can employ
+    PinnedBuf<mq_chain> h_chn_pool;       // mq_ctx_chains' host copies
+    PinnedBuf<mq_chain_span> h_chn_spans;
+    PinnedBuf<ChainCounters> h_chn_counters;
+    ScopedEvent chn_done;                 // behind the last launch sequence that wrote chains (recorded on ITS stream)
+    bool chn_ran = false;                 // ... recorded at least once
+    uint32_t chn_n = 0;                   // reads of the last batch that delivered chains
     // mq_ctx_reserve_redo: what the device form needs to redo its overflow reads in stream (none: they come back MQ_HIT_OVERFLOW).  The
     // last member, so the first to go: it waits for its own last launch, and its buffers go before the context's.
     std::unique_ptr<RedoArena> redo;
@@ -115,6 +131,7 @@ struct RedoArena {
     Buf<uint64_t> src;             // where slot j's read begins in the caller's buffer
     Buf<mq_hit> hits;
     Buf<MatchRec> windows;         // grid * max(MAP_WAVES, ML_WAVES) windows of cap records
+    Buf<ChainRec> chain_windows;   // as many chain windows of chain_win_cap(cap) records, while the owning context has a chains reservation
     Buf<RedoCounters> counters;    // one block (mq_blocks.hpp), cleared in front of every device-form call
     ScopedEvent done;              // behind redo_scatter_kernel of the last device-form call
     bool ran = false;              // ... recorded at least once
@@ -306,11 +323,11 @@ struct mq_index {
     int grid_ref = 0;                        // workgroups of seed_ref_kernel that stay resident
     // launch geometry (workgroups) and scratch sizes, fixed at the first map call
     uint32_t grid_fused = 0, grid_seed = 0, grid_map = 0;  // map_kernel; seed_reads_kernel, map_lists_kernel (split)
-    // ... of the launches of contexts with an anchor reservation: the minimum over grid_fused and the index's anchors pair, worked out at the
-    // first reservation (an index nobody reserves anchors on keeps its launch geometry)
-    std::once_flag anchors_geometry_once;
-    int anchors_geometry_rc = MQ_OK;
-    uint32_t grid_fused_anchors = 0;
+    // ... of the launches of contexts with an anchors or a chains reservation: the minimum over grid_fused and the output pairs the index can
+    // launch (anchors, chains, both), worked out at the first reservation of either kind (an index nobody reserves on keeps its launch geometry)
+    std::once_flag outputs_geometry_once;
+    int outputs_geometry_rc = MQ_OK;
+    uint32_t grid_fused_outputs = 0;
     uint32_t cap_matches = 0;
     bool split = false;             // diagnostic MQ_PIPELINE=split: the two phases as separate launches (a profiler then prices each)
     bool force_general = false;     // test hook MQ_FORCE_GENERAL=1: never take the fast seeding path
@@ -489,16 +506,24 @@ using MapFn = void (*)(MapArgs);
 struct MapPair {
     MapFn map, declined;
 };
-template <int CH, bool TIMING, bool VAR, class Spec = SpecNone, bool ANCH = false>
+template <int CH, bool TIMING, bool VAR, class Spec = SpecNone, bool ANCH = false, bool CHN = false>
 constexpr MapPair map_pair() {
-    return {map_kernel<CH, TIMING, VAR, Spec, ANCH>, map_declined_kernel<CH, TIMING, VAR, Spec, ANCH>};
+    return {map_kernel<CH, TIMING, VAR, Spec, ANCH, CHN>, map_declined_kernel<CH, TIMING, VAR, Spec, ANCH, CHN>};
 }
 static const MapPair MAP_KERNELS[2][2][2] = {{{map_pair<64, false, false>(), map_pair<4, false, false>()}, {map_pair<64, true, false>(), map_pair<64, true, false>()}},
                                              {{map_pair<64, false, true>(), map_pair<4, false, true>()}, {map_pair<64, true, true>(), map_pair<64, true, true>()}}};
-// The anchors dimension: the SpecNone, non-instrumented pairs once more with the anchor output (a context with a reservation:
-// mq_ctx_reserve_anchors), by [seeding variant != 0][chain chunk 4].  MAP_SPECS has no such dimension: a reserving context launches SpecNone.
-static const MapPair MAP_KERNELS_ANCHORS[2][2] = {{map_pair<64, false, false, SpecNone, true>(), map_pair<4, false, false, SpecNone, true>()},
-                                                  {map_pair<64, false, true, SpecNone, true>(), map_pair<4, false, true, SpecNone, true>()}};
+// The output dimensions: the SpecNone, non-instrumented pairs once more with the anchor output, the chains output or both (a context with
+// a reservation: mq_ctx_reserve_anchors, mq_ctx_reserve_chains), by [anchors][chains][seeding variant != 0][chain chunk 4].  The [0][0]
+// corner is not built: it is MAP_KERNELS.  MAP_SPECS has no such dimension: a reserving context launches SpecNone.
+template <bool ANCH, bool CHN>
+constexpr MapPair out_pair(bool var, bool ch4) {
+    return var ? (ch4 ? map_pair<4, false, true, SpecNone, ANCH, CHN>() : map_pair<64, false, true, SpecNone, ANCH, CHN>())
+               : (ch4 ? map_pair<4, false, false, SpecNone, ANCH, CHN>() : map_pair<64, false, false, SpecNone, ANCH, CHN>());
+}
+#define MQ_OUT_PAIRS(A, C) {{out_pair<A, C>(false, false), out_pair<A, C>(false, true)}, {out_pair<A, C>(true, false), out_pair<A, C>(true, true)}}
+static const MapPair MAP_KERNELS_OUTPUTS[2][2][2][2] = {{{{{nullptr, nullptr}, {nullptr, nullptr}}, {{nullptr, nullptr}, {nullptr, nullptr}}}, MQ_OUT_PAIRS(false, true)},
+                                                        {MQ_OUT_PAIRS(true, false), MQ_OUT_PAIRS(true, true)}};
+#undef MQ_OUT_PAIRS
 
 // The spec dimension of the table: the product pair (chunk 64, not instrumented, frozen reading) compiled for the parameters nearly
 // every run uses -- the reference's defaults -k 5 -l 31 with homopolymer compression and SipHash, the -k 7 of its real-data runs, and the
@@ -530,11 +555,11 @@ static uint32_t map_spec_of(const mq_index *idx) {
     return 0;
 }
 // the pair of a fused launch sequence, and the spec id it carries
-// anchors: the launching context has an anchor reservation and the launch delivers (never the instrumented one)
-static const MapPair &map_pair_of(const mq_index *idx, bool instrumented, uint32_t *spec_id = nullptr, bool anchors = false) {
-    if (anchors && !instrumented) {
+// anchors, chains: the launching context has that reservation and the launch delivers (never the instrumented one)
+static const MapPair &map_pair_of(const mq_index *idx, bool instrumented, uint32_t *spec_id = nullptr, bool anchors = false, bool chains = false) {
+    if ((anchors || chains) && !instrumented) {
         if (spec_id) *spec_id = 0;
-        return MAP_KERNELS_ANCHORS[idx->dp.variant != 0][idx->chain_chunk == 4];
+        return MAP_KERNELS_OUTPUTS[anchors][chains][idx->dp.variant != 0][idx->chain_chunk == 4];
     }
     const uint32_t sid = instrumented ? 0u : idx->map_spec;
     if (spec_id) *spec_id = sid;
@@ -593,21 +618,31 @@ static int ensure_geometry(mq_index *idx) {
     return idx->geometry_rc;
 }
 
-// ... of a context that reserves anchors: the index's anchors pair (its seeding variant and chain chunk are fixed at mq_index_new) joins the
-// occupancy minimum -- for the launches of such contexts only, in a second grid
-static int ensure_anchors_geometry(mq_index *idx) {
+// ... of a context that reserves anchors or chains: the index's three output pairs (its seeding variant and chain chunk are fixed at
+// mq_index_new) join the occupancy minimum -- for the launches of such contexts only, in a second grid
+static int ensure_outputs_geometry(mq_index *idx) {
     int rc = ensure_geometry(idx);
     if (rc) return rc;
-    std::call_once(idx->anchors_geometry_once, [idx] {
-        const MapPair &kp = map_pair_of(idx, false, nullptr, true);
+    std::call_once(idx->outputs_geometry_once, [idx] {
         int occ = 0, occ_min = INT_MAX;
-        for (const MapFn fn : {kp.map, kp.declined}) {
-            if ((idx->anchors_geometry_rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return;
-            occ_min = std::min(occ_min, occ);
-        }
-        idx->grid_fused_anchors = std::min(idx->grid_fused, (uint32_t)(occ_min * idx->n_cu));
+        for (const MapPair *kp : {&map_pair_of(idx, false, nullptr, true, false), &map_pair_of(idx, false, nullptr, false, true), &map_pair_of(idx, false, nullptr, true, true)})
+            for (const MapFn fn : {kp->map, kp->declined}) {
+                if ((idx->outputs_geometry_rc = occ_of((const void *)fn, 64 * MAP_WAVES, occ))) return;
+                occ_min = std::min(occ_min, occ);
+            }
+        idx->grid_fused_outputs = std::min(idx->grid_fused, (uint32_t)(occ_min * idx->n_cu));
     });
-    return idx->anchors_geometry_rc;
+    return idx->outputs_geometry_rc;
+}
+
+// records of a chain window beside a Match window of `cap` records: a read chained from LDS (up to MAP_LDS_RECS records, whatever cap is)
+// stages there too
+static uint32_t chain_win_cap(uint32_t cap) { return std::max(cap, MAP_LDS_RECS); }
+// mapping waves a launch over up to n reads can employ, in either pipeline (ctx_ensure's count for the Match windows)
+static size_t map_waves_for(const mq_index *idx, uint32_t n) {
+    const size_t max_waves = std::max((size_t)idx->grid_fused * MAP_WAVES, (size_t)idx->grid_map * ML_WAVES);
+    const size_t wpw = (size_t)std::max(MAP_WAVES, ML_WAVES);
+    return std::min(max_waves, ((size_t)n + wpw - 1) / wpw * wpw + wpw);
 }
 
 // list entries reserved per base, in 1/65536: 4 d + 1/512 -- canonical selection keeps 1-(1-d)^2 ~ 2 d of the l-mers, so this
@@ -637,8 +672,7 @@ static int ctx_ensure(mq_ctx *c, uint32_t n, uint64_t total_bases, uint32_t f16)
         // workgroup): a context that only ever sees chunks of a thousand reads does not pay for 4,096 waves' windows (268 MB of fresh
         // device memory, ~8 ms, per context)
         const size_t max_waves = std::max((size_t)idx->grid_fused * MAP_WAVES, (size_t)idx->grid_map * ML_WAVES);
-        const size_t wpw = (size_t)std::max(MAP_WAVES, ML_WAVES);
-        const size_t want = std::min(max_waves, ((size_t)n + wpw - 1) / wpw * wpw + wpw);
+        const size_t want = map_waves_for(idx, n);  // (the chain windows of a chains reservation are counted by the same function)
         if (want > c->scratch_waves) {
             c->scratch_waves = 0;
             const size_t nw = std::min(max_waves, want + want / 4);

@@ -51,6 +51,7 @@ struct MapArgs {
     AnchorOut anchors;            // the pool, its capacity, the batch's AnchorCounters (NOT in `counters`: those are cleared per launch)
     mq_anchor_span *anchor_spans; // read r's span goes to anchor_spans[anchor_ids ? anchor_ids[r] : r] ...
     const uint32_t *anchor_ids;   // ... nullptr: the launch's read numbers are the batch's; a redo launch: its read -> the batch's read, 0xFFFFFFFF: write no span
+    // (the chains output's arguments are NOT here: counters->chains, mq_blocks.hpp -- these kernel arguments stay the size they were)
 };
 
 // Per-read timing of the instrumented launch (mq_map_probe_stats -> mq_last_read_cycles).  The two arrays ALIAS the split pipeline's per-read
@@ -412,18 +413,35 @@ __device__ __forceinline__ void store_span(const MapArgs &A, uint32_t r, const m
     }
 }
 
+// CHN instantiations: read r's chain span, the same way
+static_assert(sizeof(mq_chain_span) == 8, "chain span");
+__device__ __forceinline__ void store_chain_span(const MapArgs &A, uint32_t r, const mq_chain_span &sp) {
+    if (lane_id() == 0) {
+        const ChainLaunch &C = A.counters->chains;
+        const uint32_t id = C.ids ? C.ids[r] : r;
+        if (id != 0xFFFFFFFFu) *reinterpret_cast<span_word *>(C.spans + id) = make_uint2(sp.first, sp.count);
+    }
+}
+// the chain window of mapping wave wave_gid (CHN instantiations)
+__device__ __forceinline__ ChainRec *chain_window(const MapArgs &A, uint32_t wave_gid) {
+    return A.counters->chains.windows + (size_t)wave_gid * A.counters->chains.win_cap;
+}
+
 // ANCH: the winning chain's runs go to A.anchors, and sp says where (chain_stage); {0, 0} for a read that is unmapped, tied, too short or
 // leaves with MQ_HIT_OVERFLOW -- it claims nothing
-template <int CH, bool TIMING, bool VAR = true, class Spec = SpecNone, bool ANCH = false>
+// CHN: every candidate chain goes to the pool of A.counters->chains (ChainLaunch, mq_blocks.hpp) by way of the wave's chain window cwin, and csp says where; {0, 0} for a read without a run,
+// too short, or one that leaves with MQ_HIT_OVERFLOW
+template <int CH, bool TIMING, bool VAR = true, class Spec = SpecNone, bool ANCH = false, bool CHN = false>
 __device__ __forceinline__ void map_read(const MapArgs &A, MapListLds &S, MatchRec *scratch, uint32_t r, uint64_t len, uint32_t cnt,
                                          uint64_t base, unsigned long long &t_steps, unsigned long long &t_lookups, mq_hit &h,
-                                         mq_anchor_span *sp = nullptr) {
+                                         mq_anchor_span *sp = nullptr, ChainRec *cwin = nullptr, mq_chain_span *csp = nullptr) {
     const uint32_t lane = lane_id();
     const DevParams &P = A.P;
     const uint32_t k = spec_k<Spec>(P);
     h.status = MQ_HIT_UNMAPPED;
     h.ref_id = h.rc = h.mapq = h.q_start = h.q_end = h.r_start = h.r_end = h.score = h.n_kminmers = h.q_start_hi = h.q_end_hi = 0;
     if constexpr (ANCH) sp->first = sp->count = 0;
+    if constexpr (CHN) csp->first = csp->count = 0;
     uint32_t n_kmm = 0;
     if (cnt == LIST_OVERFLOW) {
         h.status = MQ_HIT_OVERFLOW;  // the list fits neither its region nor the pool: nothing was computed for this read
@@ -486,7 +504,8 @@ __device__ __forceinline__ void map_read(const MapArgs &A, MapListLds &S, MatchR
             MatchRec m0 = {};
             if (lane_id() < sink.n_matches) m0 = S.rec[lane_id()];
             mq_clk(8);
-            if constexpr (ANCH) chain_stage<CH, true>(S.rec, sink.n_matches, P, len, A.ref_lens, h, &m0, &A.anchors, sp);
+            if constexpr (CHN) chain_stage<CH, ANCH, true>(S.rec, sink.n_matches, P, len, A.ref_lens, h, &m0, &A.anchors, sp, &A.counters->chains, cwin, csp);
+            else if constexpr (ANCH) chain_stage<CH, true>(S.rec, sink.n_matches, P, len, A.ref_lens, h, &m0, &A.anchors, sp);
             else chain_stage<CH>(S.rec, sink.n_matches, P, len, A.ref_lens, h, &m0);
         } else {
             if (sink.n_matches > 0 && sink.n_matches <= A.cap_matches) {  // many records: those in LDS join the others in the scratch
@@ -499,7 +518,8 @@ __device__ __forceinline__ void map_read(const MapArgs &A, MapListLds &S, MatchR
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // Match records written by this wave are in L2
                 wave_sync();
                 mq_clk(8);
-                if constexpr (ANCH) chain_stage<CH, true>(scratch, sink.n_matches, P, len, A.ref_lens, h, nullptr, &A.anchors, sp);
+                if constexpr (CHN) chain_stage<CH, ANCH, true>(scratch, sink.n_matches, P, len, A.ref_lens, h, nullptr, &A.anchors, sp, &A.counters->chains, cwin, csp);
+                else if constexpr (ANCH) chain_stage<CH, true>(scratch, sink.n_matches, P, len, A.ref_lens, h, nullptr, &A.anchors, sp);
                 else chain_stage<CH>(scratch, sink.n_matches, P, len, A.ref_lens, h);
             }
         }
@@ -539,7 +559,9 @@ union MapWaveLds {
 // launched only for an index whose A.P says the same (MAP_SPECS, mq_host_state.hpp)
 // ANCH: the pair of a context with an anchor reservation (mq_ctx_reserve_anchors; SpecNone, not instrumented): every read's span is stored
 // with its hit, the winning chain's runs by chain_stage
-template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone, bool ANCH = false>
+// CHN: the pair of a context with a chains reservation (mq_ctx_reserve_chains; SpecNone, not instrumented), alone or with ANCH: every read's
+// chain span is stored with its hit, its candidate chains by chain_stage
+template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone, bool ANCH = false, bool CHN = false>
 __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(const MapArgs A) {
     // one block of LDS with the tables FIRST: T.rot's entries are addressed through the 16-bit immediate offset of ds_read_b128
     __shared__ struct {
@@ -646,7 +668,9 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         if (lane == 0 && rn < n_items) nd = work[rn];  // a vector load by one lane: in flight through the map phase (a scalar load would be waited for at its first LDS wait)
         mq_hit h;
         mq_anchor_span sp;  // (ANCH only)
-        if constexpr (ANCH) map_read<CH, TIMING, VAR, Spec, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp);
+        mq_chain_span csp;  // (CHN only)
+        if constexpr (CHN) map_read<CH, TIMING, VAR, Spec, ANCH, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp, chain_window(A, wave_gid), &csp);
+        else if constexpr (ANCH) map_read<CH, TIMING, VAR, Spec, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp);
         else map_read<CH, TIMING, VAR, Spec>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
         wave_sync();
         const uint32_t r_done = r;
@@ -657,6 +681,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
         asm volatile("" ::: "memory");  // the prefetched descriptor is out of its registers before the result's store is issued
         store_hit(A, r_done, h);
         if constexpr (ANCH) store_span(A, r_done, sp);
+        if constexpr (CHN) store_chain_span(A, r_done, csp);
         if (rn < n_items && (nw & WORK_SKIP)) take_now();  // that read went first
         if (TIMING && lane == 0) {
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_read0;
@@ -680,7 +705,7 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_kernel(c
 
 // The reads map_kernel queued (the fast seeder declined them): seeded stretch by stretch (seed_read_hybrid), mapped, stored.  Launched behind
 // map_kernel in every launch sequence; its waves leave at once when the queue is empty.
-template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone, bool ANCH = false>
+template <int CH, bool TIMING = false, bool VAR = false, class Spec = SpecNone, bool ANCH = false, bool CHN = false>
 __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined_kernel(const MapArgs A) {
     const uint32_t nq = A.counters->queue_len;
     if (nq == 0) return;
@@ -717,11 +742,14 @@ __global__ __launch_bounds__(64 * MAP_WAVES, MQ_MAP_MIN_WAVES) void map_declined
         wave_sync();
         mq_hit h;
         mq_anchor_span sp;  // (ANCH only)
-        if constexpr (ANCH) map_read<CH, TIMING, VAR, Spec, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp);
+        mq_chain_span csp;  // (CHN only)
+        if constexpr (CHN) map_read<CH, TIMING, VAR, Spec, ANCH, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp, chain_window(A, wave_gid), &csp);
+        else if constexpr (ANCH) map_read<CH, TIMING, VAR, Spec, true>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h, &sp);
         else map_read<CH, TIMING, VAR, Spec>(A, S.map, scratch, r, len, cnt, base, t_steps, t_lookups, h);
         wave_sync();
         store_hit(A, r, h);
         if constexpr (ANCH) store_span(A, r, sp);
+        if constexpr (CHN) store_chain_span(A, r, csp);
         if (TIMING && lane == 0) {  // mq_last_read_cycles: this read's cycles here; in the start word's place the seeding split (format: read_start)
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t_read0;
             read_cycles(A)[r] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
