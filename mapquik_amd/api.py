@@ -190,20 +190,14 @@ def load_library(path=None):
         L.mq_map_reserve_redo.argtypes = [vp, u32, u32]
         L.mq_ctx_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.mq_map_redo_counts.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
-    if hasattr(L, "mq_ctx_reserve_anchors"):
-        pp = C.POINTER(vp)
-        L.mq_ctx_reserve_anchors.argtypes = [vp, u32, u64]
-        L.mq_map_reserve_anchors.argtypes = [vp, u32, u64]
-        L.mq_ctx_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
-        L.mq_map_anchors.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
-        L.mq_ctx_anchors_device.argtypes = [vp, pp, pp]
-    if hasattr(L, "mq_ctx_reserve_chains"):
-        pp = C.POINTER(vp)
-        L.mq_ctx_reserve_chains.argtypes = [vp, u32, u64]
-        L.mq_map_reserve_chains.argtypes = [vp, u32, u64]
-        L.mq_ctx_chains.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
-        L.mq_map_chains.argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
-        L.mq_ctx_chains_device.argtypes = [vp, pp, pp]
+    pp = C.POINTER(vp)
+    for kind in ("anchors", "chains"):  # the two pooled outputs: one family of entry points each
+        if hasattr(L, "mq_ctx_reserve_" + kind):
+            for scope in ("ctx", "map"):
+                getattr(L, "mq_%s_reserve_%s" % (scope, kind)).argtypes = [vp, u32, u64]
+                getattr(L, "mq_%s_%s" % (scope, kind)).argtypes = [vp, pp, pp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+            getattr(L, "mq_ctx_%s_device" % kind).argtypes = [vp, pp, pp]
+    if hasattr(L, "mq_format_paf_chain"):
         L.mq_format_paf_chain.argtypes = [vp, C.c_char_p, u64, vp, C.c_char_p, C.c_size_t]
     if hasattr(L, "mq_index_reopen"):
         L.mq_index_reopen.argtypes = [vp]
@@ -224,28 +218,28 @@ def _err(L, what):
     return MapquikError("%s: %s" % (what, (L.mq_last_error() or b"").decode(errors="replace")))
 
 
-def _anchors(L, fn, what, handle):
-    """(spans, anchors, info) of mq_ctx_anchors / mq_map_anchors: numpy copies of the library's host arrays"""
-    sp, an = C.c_void_p(), C.c_void_p()
+def _pooled(L, what, handle, span_dtype, item_dtype):
+    """(spans, items, info) of mq_ctx_anchors / mq_map_anchors / mq_ctx_chains / mq_map_chains (`what`): numpy copies of the library's host arrays"""
+    sp, it = C.c_void_p(), C.c_void_p()
     n, dropped = C.c_uint32(), C.c_uint32()
     stored, needed = C.c_uint64(), C.c_uint64()
-    if fn(handle, C.byref(sp), C.byref(an), C.byref(n), C.byref(stored), C.byref(needed), C.byref(dropped)) != 0:
+    if getattr(L, what)(handle, C.byref(sp), C.byref(it), C.byref(n), C.byref(stored), C.byref(needed), C.byref(dropped)) != 0:
         raise _err(L, what)
-    spans = np.frombuffer(C.string_at(sp.value, n.value * anchor_span_dtype.itemsize), dtype=anchor_span_dtype).copy() if n.value else np.zeros(0, dtype=anchor_span_dtype)
-    anchors = np.frombuffer(C.string_at(an.value, stored.value * anchor_dtype.itemsize), dtype=anchor_dtype).copy() if stored.value else np.zeros(0, dtype=anchor_dtype)
-    return spans, anchors, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
+    spans = np.frombuffer(C.string_at(sp.value, n.value * span_dtype.itemsize), dtype=span_dtype).copy() if n.value else np.zeros(0, dtype=span_dtype)
+    items = np.frombuffer(C.string_at(it.value, stored.value * item_dtype.itemsize), dtype=item_dtype).copy() if stored.value else np.zeros(0, dtype=item_dtype)
+    return spans, items, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
 
 
-def _chains(L, fn, what, handle):
-    """(spans, chains, info) of mq_ctx_chains / mq_map_chains: numpy copies of the library's host arrays"""
-    sp, ch = C.c_void_p(), C.c_void_p()
-    n, dropped = C.c_uint32(), C.c_uint32()
-    stored, needed = C.c_uint64(), C.c_uint64()
-    if fn(handle, C.byref(sp), C.byref(ch), C.byref(n), C.byref(stored), C.byref(needed), C.byref(dropped)) != 0:
+def _reserve_pooled(L, what, handle, max_reads, max_entries):
+    if getattr(L, what)(handle, int(max_reads), int(max_entries)) != 0:
         raise _err(L, what)
-    spans = np.frombuffer(C.string_at(sp.value, n.value * chain_span_dtype.itemsize), dtype=chain_span_dtype).copy() if n.value else np.zeros(0, dtype=chain_span_dtype)
-    chains = np.frombuffer(C.string_at(ch.value, stored.value * chain_dtype.itemsize), dtype=chain_dtype).copy() if stored.value else np.zeros(0, dtype=chain_dtype)
-    return spans, chains, dict(stored=stored.value, needed=needed.value, dropped_reads=dropped.value)
+
+
+def _pooled_device(L, what, handle):
+    sp, it = C.c_void_p(), C.c_void_p()
+    if getattr(L, what)(handle, C.byref(sp), C.byref(it)) != 0:
+        raise _err(L, what)
+    return sp.value, it.value
 
 
 class PinnedBuffer:
@@ -500,21 +494,19 @@ class Index:
 
     def reserve_anchors(self, max_reads, max_anchors):
         """Context.reserve_anchors for the default context (map_batch, map_batch_device); (0, 0) releases."""
-        if self._L.mq_map_reserve_anchors(self._h, int(max_reads), int(max_anchors)) != 0:
-            raise _err(self._L, "mq_map_reserve_anchors")
+        _reserve_pooled(self._L, "mq_map_reserve_anchors", self._h, max_reads, max_anchors)
 
     def anchors(self):
         """Context.anchors for the default context."""
-        return _anchors(self._L, self._L.mq_map_anchors, "mq_map_anchors", self._h)
+        return _pooled(self._L, "mq_map_anchors", self._h, anchor_span_dtype, anchor_dtype)
 
     def reserve_chains(self, max_reads, max_chains):
         """Context.reserve_chains for the default context (map_batch, map_batch_device); (0, 0) releases."""
-        if self._L.mq_map_reserve_chains(self._h, int(max_reads), int(max_chains)) != 0:
-            raise _err(self._L, "mq_map_reserve_chains")
+        _reserve_pooled(self._L, "mq_map_reserve_chains", self._h, max_reads, max_chains)
 
     def chains(self):
         """Context.chains for the default context."""
-        return _chains(self._L, self._L.mq_map_chains, "mq_map_chains", self._h)
+        return _pooled(self._L, "mq_map_chains", self._h, chain_span_dtype, chain_dtype)
 
     def format_paf_chain(self, q_id, q_len, chain):
         """The twelve PAF columns of any chain of chains() (mq_format_paf_chain)."""
@@ -770,40 +762,32 @@ class Context:
     def reserve_anchors(self, max_reads, max_anchors):
         """From now on every batch of up to max_reads reads mapped on this context also delivers the Match runs of each mapped read's winning
         chain, from a pool of max_anchors entries (include/mapquik_hip.h: mq_ctx_reserve_anchors).  (0, 0) releases."""
-        if self._L.mq_ctx_reserve_anchors(self._h, int(max_reads), int(max_anchors)) != 0:
-            raise _err(self._L, "mq_ctx_reserve_anchors")
+        _reserve_pooled(self._L, "mq_ctx_reserve_anchors", self._h, max_reads, max_anchors)
 
     def anchors(self):
         """(spans, anchors, info) of the context's last batch, which it finishes: read r's runs are anchors[spans[r]["first"]:][:spans[r]["count"]]
         in read order (first == MQ_ANCHORS_DROPPED: the pool was too small for them); info = dict(stored, needed, dropped_reads)."""
-        return _anchors(self._L, self._L.mq_ctx_anchors, "mq_ctx_anchors", self._h)
+        return _pooled(self._L, "mq_ctx_anchors", self._h, anchor_span_dtype, anchor_dtype)
 
     def reserve_chains(self, max_reads, max_chains):
         """From now on every batch of up to max_reads reads mapped on this context also delivers every candidate chain of every read -- one per
         reference with a Match run in the read, ties included -- from a pool of max_chains entries (include/mapquik_hip.h:
         mq_ctx_reserve_chains).  (0, 0) releases."""
-        if self._L.mq_ctx_reserve_chains(self._h, int(max_reads), int(max_chains)) != 0:
-            raise _err(self._L, "mq_ctx_reserve_chains")
+        _reserve_pooled(self._L, "mq_ctx_reserve_chains", self._h, max_reads, max_chains)
 
     def chains(self):
         """(spans, chains, info) of the context's last batch, which it finishes: read r's chains are chains[spans[r]["first"]:][:spans[r]["count"]]
         in the order of each reference's first run in the read (first == MQ_CHAINS_DROPPED: the pool was too small for them); info =
         dict(stored, needed, dropped_reads).  A read is mapped exactly when one of its chains has flags == MQ_CHAIN_TOP."""
-        return _chains(self._L, self._L.mq_ctx_chains, "mq_ctx_chains", self._h)
+        return _pooled(self._L, "mq_ctx_chains", self._h, chain_span_dtype, chain_dtype)
 
     def chains_device(self):
         """(device pointer of the spans, device pointer of the chains): the arrays a map_batch_device call on this context writes."""
-        sp, ch = C.c_void_p(), C.c_void_p()
-        if self._L.mq_ctx_chains_device(self._h, C.byref(sp), C.byref(ch)) != 0:
-            raise _err(self._L, "mq_ctx_chains_device")
-        return sp.value, ch.value
+        return _pooled_device(self._L, "mq_ctx_chains_device", self._h)
 
     def anchors_device(self):
         """(device pointer of the spans, device pointer of the anchors): the arrays a map_batch_device call on this context writes."""
-        sp, an = C.c_void_p(), C.c_void_p()
-        if self._L.mq_ctx_anchors_device(self._h, C.byref(sp), C.byref(an)) != 0:
-            raise _err(self._L, "mq_ctx_anchors_device")
-        return sp.value, an.value
+        return _pooled_device(self._L, "mq_ctx_anchors_device", self._h)
 
     def last_map_ms(self):
         ms = C.c_float()

@@ -25,6 +25,20 @@ struct IdSpan {
     uint32_t len;
 };
 
+// a chunk's share of a pooled per-read output: read i's entries are pool[spans[i].first, + spans[i].count); text: their lines
+template <class Span, class Item>
+struct PooledItems {
+    std::vector<Span> spans;
+    std::vector<Item> pool;
+    std::string text;
+    bool holds(size_t i) const { return i < spans.size() && (uint64_t)spans[i].first + spans[i].count <= pool.size(); }
+    void clear() {
+        spans.clear();
+        pool.clear();
+        text.clear();
+    }
+};
+
 // one unit of work through the pipeline: raw bytes + the reads found in them
 struct Chunk {
     size_t seq_no = 0;
@@ -39,14 +53,10 @@ struct Chunk {
     std::vector<std::pair<uint64_t, uint64_t>> regions;
     std::vector<mq_hit> hits;
     std::string paf, unmapped, unmapped_fa;  // formatted output of this chunk
-    // --anchors: the chunk's spans and anchors (copies of mq_ctx_anchors' arrays, taken when the chunk's slot was waited for) and their text
-    std::vector<mq_anchor_span> a_spans;
-    std::vector<mq_anchor> a_pool;
-    std::string anchors;
-    // --chains: the same for the chunk's chain spans and chains (mq_ctx_chains)
-    std::vector<mq_chain_span> c_spans;
-    std::vector<mq_chain> c_pool;
-    std::string chains;
+    // --anchors, --chains: the chunk's spans and pool entries (copies of mq_ctx_anchors' / mq_ctx_chains' arrays, taken when the chunk's
+    // slot was waited for) and their text
+    PooledItems<mq_anchor_span, mq_anchor> anchors;
+    PooledItems<mq_chain_span, mq_chain> chains;
     // set by the whole-member gzip reader: the chunk's bytes still sit in a member's inflate buffer (kept alive by ext_hold);
     // the parser thread that takes the chunk copies them into buf first
     const uint8_t *ext_src = nullptr;
@@ -81,11 +91,7 @@ struct Chunk {
         paf.clear();
         unmapped.clear();
         unmapped_fa.clear();
-        a_spans.clear();
-        a_pool.clear();
         anchors.clear();
-        c_spans.clear();
-        c_pool.clear();
         chains.clear();
     }
 };

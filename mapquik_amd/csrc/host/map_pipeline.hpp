@@ -49,49 +49,34 @@ inline bool collect_device_records(mq_ctx *ctx, feeder::Chunk &c, uint32_t fx_fo
     return false;
 }
 
-// --anchors: the spans and anchors of the batch the slot has just finished become the chunk's (the library's host copies last until the
-// slot's next submit).  A pool that was too small for the chunk ends the run, like any other pipeline failure, with what it needed.
-inline void take_anchors(mq_ctx *ctx, feeder::Chunk &c) {
-    c.a_spans.clear();
-    c.a_pool.clear();
+// --anchors, --chains: the spans and pool entries of the batch the slot has just finished become the chunk's (the library's host copies
+// last until the slot's next submit).  A pool that was too small for the chunk ends the run, like any other pipeline failure, with what it
+// needed.  read_back: mq_ctx_anchors / mq_ctx_chains, `call` its name; option, pool_noun: "--anchors", "anchor" / "--chains", "chain"
+template <class Span, class Item, class ReadBack>
+inline void take_pooled(ReadBack read_back, const char *call, const char *option, const char *pool_noun, mq_ctx *ctx, const feeder::Chunk &c,
+                        feeder::PooledItems<Span, Item> &out) {
+    out.spans.clear();
+    out.pool.clear();
     if (c.hits.empty()) return;  // nothing was mapped for this chunk: the slot's last batch is somebody else's
-    const mq_anchor_span *spans = nullptr;
-    const mq_anchor *pool = nullptr;
+    const Span *spans = nullptr;
+    const Item *pool = nullptr;
     uint32_t n = 0, dropped = 0;
     uint64_t stored = 0, needed = 0;
-    if (mq_ctx_anchors(ctx, &spans, &pool, &n, &stored, &needed, &dropped) != MQ_OK) throw Error(std::string("mq_ctx_anchors: ") + last_error());
-    if (n != c.hits.size()) throw Error("mq_ctx_anchors: " + std::to_string(n) + " spans for a chunk of " + std::to_string(c.hits.size()) + " reads");
+    if (read_back(ctx, &spans, &pool, &n, &stored, &needed, &dropped) != MQ_OK) throw Error(std::string(call) + ": " + last_error());
+    if (n != c.hits.size()) throw Error(std::string(call) + ": " + std::to_string(n) + " spans for a chunk of " + std::to_string(c.hits.size()) + " reads");
     if (dropped)
-        throw Error("--anchors: the anchor pool of a stream slot was too small for " + std::to_string(dropped) + " reads of a chunk: " + std::to_string(needed) +
-                    " entries needed, " + std::to_string(stored) + " reserved");
-    c.a_spans.assign(spans, spans + n);
-    c.a_pool.assign(pool, pool + stored);
-}
-
-// --chains: the same for the chunk's chain spans and chains
-inline void take_chains(mq_ctx *ctx, feeder::Chunk &c) {
-    c.c_spans.clear();
-    c.c_pool.clear();
-    if (c.hits.empty()) return;
-    const mq_chain_span *spans = nullptr;
-    const mq_chain *pool = nullptr;
-    uint32_t n = 0, dropped = 0;
-    uint64_t stored = 0, needed = 0;
-    if (mq_ctx_chains(ctx, &spans, &pool, &n, &stored, &needed, &dropped) != MQ_OK) throw Error(std::string("mq_ctx_chains: ") + last_error());
-    if (n != c.hits.size()) throw Error("mq_ctx_chains: " + std::to_string(n) + " spans for a chunk of " + std::to_string(c.hits.size()) + " reads");
-    if (dropped)
-        throw Error("--chains: the chain pool of a stream slot was too small for " + std::to_string(dropped) + " reads of a chunk: " + std::to_string(needed) +
-                    " entries needed, " + std::to_string(stored) + " reserved");
-    c.c_spans.assign(spans, spans + n);
-    c.c_pool.assign(pool, pool + stored);
+        throw Error(std::string(option) + ": the " + pool_noun + " pool of a stream slot was too small for " + std::to_string(dropped) + " reads of a chunk: " +
+                    std::to_string(needed) + " entries needed, " + std::to_string(stored) + " reserved");
+    out.spans.assign(spans, spans + n);
+    out.pool.assign(pool, pool + stored);
 }
 
 // --chains: the lines of read i -- one per chain, in span order: the twelve PAF columns of the chain (mq_format_paf_chain's bytes), tp:A:P
 // for the read's unique top chain and tp:A:S for every other, cn:i:<n_runs>, and tie:i:1 on a top chain of a tied read (tp S: no primary)
 inline std::string format_chains(feeder::Chunk &c, PafWriter &pw, size_t i) {
-    if (i >= c.c_spans.size() || (uint64_t)c.c_spans[i].first + c.c_spans[i].count > c.c_pool.size()) return "--chains: a read without its chains";
-    const mq_chain *ch = c.c_pool.data() + c.c_spans[i].first;
-    const uint32_t n = c.c_spans[i].count;
+    if (!c.chains.holds(i)) return "--chains: a read without its chains";
+    const mq_chain *ch = c.chains.pool.data() + c.chains.spans[i].first;
+    const uint32_t n = c.chains.spans[i].count;
     uint32_t tops = 0;
     for (uint32_t j = 0; j < n; ++j) tops += (ch[j].flags & MQ_CHAIN_TOP) ? 1u : 0u;
     char tag[64];
@@ -99,17 +84,17 @@ inline std::string format_chains(feeder::Chunk &c, PafWriter &pw, size_t i) {
         mq_hit h;  // field for field the chain's layout: the columns are where the PAF writer reads them
         static_assert(sizeof(mq_hit) == sizeof(mq_chain), "mq_chain has the layout of mq_hit");
         memcpy(&h, &ch[j], sizeof(h));
-        pw.append(c.chains, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);
-        c.chains.pop_back();  // (the writer's newline)
+        pw.append(c.chains.text, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);
+        c.chains.text.pop_back();  // (the writer's newline)
         const bool top = (ch[j].flags & MQ_CHAIN_TOP) != 0;
-        c.chains.append(tag, (size_t)snprintf(tag, sizeof(tag), "\ttp:A:%c\tcn:i:%u%s\n", top && tops == 1 ? 'P' : 'S', ch[j].n_runs, top && tops > 1 ? "\ttie:i:1" : ""));
+        c.chains.text.append(tag, (size_t)snprintf(tag, sizeof(tag), "\ttp:A:%c\tcn:i:%u%s\n", top && tops == 1 ? 'P' : 'S', ch[j].n_runs, top && tops > 1 ? "\ttie:i:1" : ""));
     }
     return "";
 }
 
 // A mapped chunk's output: PAF lines of the mapped reads (src/mers.rs:181), and of the unmapped ones the names (want_unmapped) and the
 // records as FASTA (want_fasta, for a second pass).  Returns the error text for a hit that is neither, "" else.
-// want_anchors: beside a mapped read's PAF line, one line per Match run of its chain, in read order (take_anchors filled a_spans / a_pool):
+// want_anchors: beside a mapped read's PAF line, one line per Match run of its chain, in read order (take_pooled filled c.anchors):
 // q_id, q_start, q_end, strand, r_name, r_start, r_end, count
 // want_chains: one line per candidate chain of EVERY read, mapped or tied (format_chains)
 inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmapped, bool want_fasta, bool want_anchors = false, bool want_chains = false) {
@@ -124,15 +109,16 @@ inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmap
         if (h.status == MQ_HIT_MAPPED) {
             pw.append(c.paf, (const char *)c.buf + c.ids[i].off, c.ids[i].len, c.lens[i], h);  // src/mers.rs:181
             if (want_anchors) {
-                if (i >= c.a_spans.size() || (uint64_t)c.a_spans[i].first + c.a_spans[i].count > c.a_pool.size()) return "--anchors: a mapped read without its anchors";
+                if (!c.anchors.holds(i)) return "--anchors: a mapped read without its anchors";
                 const std::string &rn = pw.ref_name(h.ref_id);
                 char num[128];
-                for (uint32_t j = 0; j < c.a_spans[i].count; ++j) {
-                    const mq_anchor &a = c.a_pool[(size_t)c.a_spans[i].first + j];
-                    c.anchors.append((const char *)c.buf + c.ids[i].off, c.ids[i].len);
-                    c.anchors.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%c\t", a.q_start, a.q_end, h.rc ? '-' : '+'));
-                    c.anchors += rn;
-                    c.anchors.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%u\n", a.r_start, a.r_end, a.count));
+                std::string &txt = c.anchors.text;
+                for (uint32_t j = 0; j < c.anchors.spans[i].count; ++j) {
+                    const mq_anchor &a = c.anchors.pool[(size_t)c.anchors.spans[i].first + j];
+                    txt.append((const char *)c.buf + c.ids[i].off, c.ids[i].len);
+                    txt.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%c\t", a.q_start, a.q_end, h.rc ? '-' : '+'));
+                    txt += rn;
+                    txt.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t%u\n", a.r_start, a.r_end, a.count));
                 }
             }
             continue;
@@ -241,8 +227,8 @@ class MapPipeline {
                 } else if (mq_ctx_wait(ctx[sl].handle()) != MQ_OK) {
                     throw Error(std::string("mq_ctx_wait: ") + last_error());
                 }
-                if (p.cfg_.anchors) take_anchors(ctx[sl].handle(), *c);
-                if (p.cfg_.chains) take_chains(ctx[sl].handle(), *c);
+                if (p.cfg_.anchors) take_pooled(mq_ctx_anchors, "mq_ctx_anchors", "--anchors", "anchor", ctx[sl].handle(), *c, c->anchors);
+                if (p.cfg_.chains) take_pooled(mq_ctx_chains, "mq_ctx_chains", "--chains", "chain", ctx[sl].handle(), *c, c->chains);
             } catch (const std::exception &e) { p.fail(e.what()); }
             c->unparsed = false;
             inflight[sl] = nullptr;
@@ -362,8 +348,8 @@ class MapPipeline {
             if (!c->paf.empty()) fwrite(c->paf.data(), 1, c->paf.size(), paf_);
             if (unm_ && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm_);
             if (ufa_ && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa_);
-            if (cfg_.anchors && !c->anchors.empty()) fwrite(c->anchors.data(), 1, c->anchors.size(), cfg_.anchors);
-            if (cfg_.chains && !c->chains.empty()) fwrite(c->chains.data(), 1, c->chains.size(), cfg_.chains);
+            if (cfg_.anchors && !c->anchors.text.empty()) fwrite(c->anchors.text.data(), 1, c->anchors.text.size(), cfg_.anchors);
+            if (cfg_.chains && !c->chains.text.empty()) fwrite(c->chains.text.data(), 1, c->chains.text.size(), cfg_.chains);
             feed_.recycle(c);
             t_write_us_ += us_since(tw0);
         }

@@ -156,30 +156,33 @@ class Ctx {
     void reserve(uint32_t max_reads, uint64_t max_bytes) {
         if (mq_ctx_reserve(h_, max_reads, max_bytes) != MQ_OK) throw Error("mq_ctx_reserve: " + last_error());
     }
-    // --anchors: spans and an anchor pool for chunks of up to max_bytes raw bytes.  The bounds: a record takes at least four bytes of a
-    // file (">\nA\n"), so a chunk holds at most max_bytes / 4 + 1 reads; a read has no more Match runs than k-min-mers and fewer k-min-mers
-    // than minimizers, and the library sizes its minimizer lists at bytes x (4 density + 1/512) entries -- the same number of anchors
-    // here.  A chunk that needs more (reads inside dense tandem arrays) reports dropped reads, and the run ends with what it needed.
+    // --anchors, --chains: spans and a pool for chunks of up to max_bytes raw bytes (pool_bounds).  A chunk that needs more (reads inside
+    // dense tandem arrays) reports dropped reads, and the run ends with what it needed.
     void reserve_anchors(uint64_t max_bytes, double density) {
-        const uint64_t reads = std::min<uint64_t>(max_bytes / 4 + 1, (1u << 30) - 1);
-        const double f = std::min(1.0, 4.0 * (density > 0 ? density : 0.0) + 1.0 / 512.0);
-        const uint64_t anchors = std::min<uint64_t>((uint64_t)((double)max_bytes * f) + 64, 0xFFFFFFFEull - 1);
-        if (mq_ctx_reserve_anchors(h_, (uint32_t)reads, anchors) != MQ_OK) throw Error("mq_ctx_reserve_anchors: " + last_error());
+        const PoolBounds b = pool_bounds(max_bytes, density);
+        if (mq_ctx_reserve_anchors(h_, b.reads, b.entries) != MQ_OK) throw Error("mq_ctx_reserve_anchors: " + last_error());
         anchors_bytes_ = max_bytes;
     }
     uint64_t anchors_bytes() const { return anchors_bytes_; }  // the chunk size the slot's anchor reservation was made for (0: none)
-    // --chains: spans and a chain pool for chunks of up to max_bytes raw bytes, by the same bounds: a read has no more chains than runs, and
-    // no more runs than k-min-mers
     void reserve_chains(uint64_t max_bytes, double density) {
-        const uint64_t reads = std::min<uint64_t>(max_bytes / 4 + 1, (1u << 30) - 1);
-        const double f = std::min(1.0, 4.0 * (density > 0 ? density : 0.0) + 1.0 / 512.0);
-        const uint64_t chains = std::min<uint64_t>((uint64_t)((double)max_bytes * f) + 64, 0xFFFFFFFEull - 1);
-        if (mq_ctx_reserve_chains(h_, (uint32_t)reads, chains) != MQ_OK) throw Error("mq_ctx_reserve_chains: " + last_error());
+        const PoolBounds b = pool_bounds(max_bytes, density);
+        if (mq_ctx_reserve_chains(h_, b.reads, b.entries) != MQ_OK) throw Error("mq_ctx_reserve_chains: " + last_error());
         chains_bytes_ = max_bytes;
     }
     uint64_t chains_bytes() const { return chains_bytes_; }
 
   private:
+    // The bounds of both pooled outputs: a record takes at least four bytes of a file (">\nA\n"), so a chunk holds at most max_bytes / 4 + 1
+    // reads; a read has no more chains than Match runs, no more runs than k-min-mers and fewer k-min-mers than minimizers, and the library
+    // sizes its minimizer lists at bytes x (4 density + 1/512) entries -- the same number of pool entries here.
+    struct PoolBounds {
+        uint32_t reads;
+        uint64_t entries;
+    };
+    static PoolBounds pool_bounds(uint64_t max_bytes, double density) {
+        const double f = std::min(1.0, 4.0 * (density > 0 ? density : 0.0) + 1.0 / 512.0);
+        return {(uint32_t)std::min<uint64_t>(max_bytes / 4 + 1, (1u << 30) - 1), std::min<uint64_t>((uint64_t)((double)max_bytes * f) + 64, 0xFFFFFFFEull - 1)};
+    }
     mq_ctx *h_ = nullptr;
     uint64_t anchors_bytes_ = 0, chains_bytes_ = 0;
 };

@@ -27,7 +27,8 @@ struct ProbeStats {
 // the launch sequence's counter block, in what used to be spare words, so that MapArgs -- the kernel arguments of EVERY instantiation -- stays
 // the size it was.  Written by the host behind the block's clearing, in stream order; all zero for a launch without the output.
 struct ChainRec;
-struct ChainCounters;
+struct PoolCounters;
+using ChainCounters = PoolCounters;
 struct ChainLaunch {
     mq_chain *pool;
     uint32_t cap;      // entries of the pool
@@ -121,28 +122,18 @@ struct RedoCounters {
 static_assert(sizeof(RedoCounters) == 16 && offsetof(RedoCounters, claimed) == 0 && offsetof(RedoCounters, left) == 4 && offsetof(RedoCounters, spare) == 8,
               "redo counters");
 
-// ------------------------------------------------------------------ the anchor output of a batch (mq_ctx::anch_counters = MapArgs::anchor_counters)
-// cleared by the host once per BATCH, in front of its main launch sequence -- not per launch, as MapCounters is: the batch's redo launches go
-// on claiming from the same cursor.  Written by chain_stage<CH, true> (mq_chain.hpp).
-struct AnchorCounters {
+// ------------------------------------------------------------------ a pooled output of a batch (PooledOutput::counters, mq_host_state.hpp)
+// One block per output: the anchors' (AnchorOut::counters, written by chain_stage<CH, true>, mq_chain.hpp) and the chains'
+// (ChainLaunch::counters, written by chain_stage<CH, ANCH, true>).  Cleared by the host once per BATCH, in front of its main launch sequence --
+// not per launch, as MapCounters is: the batch's redo launches go on claiming from the same cursor.
+struct PoolCounters {
     unsigned long long cursor;  // pool entries claimed; counts on past the pool's capacity, so it ends as what the batch needed
-    uint32_t dropped_reads;     // mapped reads whose claim did not fit (span first = MQ_ANCHORS_DROPPED)
+    uint32_t dropped_reads;     // reads whose claim did not fit (span first = MQ_ANCHORS_DROPPED / MQ_CHAINS_DROPPED)
     uint32_t spare;
 };
-static_assert(sizeof(AnchorCounters) == 16 && offsetof(AnchorCounters, cursor) == 0 && offsetof(AnchorCounters, dropped_reads) == 8 &&
-                  offsetof(AnchorCounters, spare) == 12,
-              "anchor counters");
-
-// ------------------------------------------------------------------ the chains output of a batch (mq_ctx::chn_counters = ChainLaunch::counters)
-// cleared by the host once per BATCH, in front of its main launch sequence -- not per launch, as MapCounters is: the batch's redo launches go
-// on claiming from the same cursor.  Written by chain_stage<CH, ANCH, true> (mq_chain.hpp).
-struct ChainCounters {
-    unsigned long long cursor;  // pool entries claimed; counts on past the pool's capacity, so it ends as what the batch needed
-    uint32_t dropped_reads;     // reads whose claim did not fit (span first = MQ_CHAINS_DROPPED)
-    uint32_t spare;
-};
-static_assert(sizeof(ChainCounters) == 16 && offsetof(ChainCounters, cursor) == 0 && offsetof(ChainCounters, dropped_reads) == 8 &&
-                  offsetof(ChainCounters, spare) == 12,
-              "chain counters");
+using AnchorCounters = PoolCounters;
+static_assert(sizeof(PoolCounters) == 16 && offsetof(PoolCounters, cursor) == 0 && offsetof(PoolCounters, dropped_reads) == 8 &&
+                  offsetof(PoolCounters, spare) == 12,
+              "pool counters");
 
 }  // namespace mq

@@ -1,6 +1,8 @@
 // mq_capi_map.hpp -- C ABI, mapping side: launch sequences (the kernel pair of each comes from MAP_KERNELS), stream-slot contexts
-// (mq_ctx_*), host-buffer and device-resident entry points, device-parsed FASTA chunks, PAF formatting, page-locked host memory (part of
-// the one translation unit mq_capi.hip).  Temporary device memory is a Buf: it goes when its function returns, by whichever way.
+// (mq_ctx_*), host-buffer and device-resident entry points, the overflow redo (through the host, and in stream), the reservation and
+// read-back of the pooled outputs (PooledOutput, mq_host_state.hpp: anchors and chains share every line but the chain windows),
+// device-parsed FASTA chunks, PAF formatting, page-locked host memory (part of the one translation unit mq_capi.hip).  Temporary device
+// memory is a Buf: it goes when its function returns, by whichever way.
 #pragma once
 
 struct LaunchOpt {
@@ -13,33 +15,17 @@ struct LaunchOpt {
     uint32_t f16 = 0;                      // 0 => list_f16(idx)
     const uint32_t *d_lens = nullptr;      // spans form: per-read lengths
     bool instrumented = false;             // mq_map_probe_stats: the launch that counts lookups and probe steps (slower, never timed)
-    // the anchor output (mq_ctx_reserve_anchors) of a batch's redo launch: the batch's cursor goes on, the spans go where the map says
-    bool anchor_redo = false;
-    const uint32_t *d_anchor_ids = nullptr;  // MapArgs::anchor_ids
-    mq_ctx *anchors_of = nullptr;            // the context whose reservations (anchors, chains) the launch delivers to (nullptr: c itself; the arena's launch: its owner)
-    // the chains output (mq_ctx_reserve_chains) of a batch's redo launch, the same way; and the chain windows that go with scratch_override
-    bool chain_redo = false;
-    const uint32_t *d_chain_ids = nullptr;   // ChainLaunch::ids
-    ChainRec *chain_windows_override = nullptr;  // as many windows as scratch_override has, of chain_win_cap(cap_override) records
+    // the pooled outputs (PooledOutput: anchors, chains) the launch delivers to
+    mq_ctx *outputs_of = nullptr;          // the context whose reservations they are (nullptr: c itself; the arena's launch: its owner)
+    bool redo = false;                     // a redo launch of a batch: the batch's cursors go on, every span goes where the id map says
+    const uint32_t *d_ids = nullptr;       // ... the id map of both outputs (MapArgs::anchor_ids, ChainLaunch::ids); nullptr: each reservation's own `ids`
+    ChainRec *chain_windows_override = nullptr;  // goes with scratch_override: as many windows, of chain_win_cap(cap_override) records
 };
 
-// A batch of n reads on a context with an anchor reservation is refused when it has more reads than spans.  The entry points ask before
-// they queue anything (a FASTX piece: before its map launch -- the number of records is known only at the wait); launch_map asks again,
-// where the spans are about to be written.  Nothing of the context changes here: the batch becomes "the last batch" in launch_map.
-static int anchors_admit(const mq_ctx *c, uint32_t n) {
-    if (c->anch_reads && n > c->anch_reads)
-        return set_err(MQ_EINVAL, "more reads in the batch than the context's anchor reservation holds (mq_ctx_reserve_anchors: max_reads)");
-    return MQ_OK;
-}
-// ... the same for a chains reservation
-static int chains_admit(const mq_ctx *c, uint32_t n) {
-    if (c->chn_reads && n > c->chn_reads)
-        return set_err(MQ_EINVAL, "more reads in the batch than the context's chains reservation holds (mq_ctx_reserve_chains: max_reads)");
-    return MQ_OK;
-}
+// (nothing of the context changes here: the batch becomes "the last batch" in launch_map)
 static int outputs_admit(const mq_ctx *c, uint32_t n) {
-    int rc = anchors_admit(c, n);
-    return rc ? rc : chains_admit(c, n);
+    int rc = c->anchors.admit(n);
+    return rc ? rc : c->chains.admit(n);
 }
 
 // One launch sequence on stream `st` using the context's scratch.  ctx_ensure(c, n, total_bases, f16) must have succeeded.
@@ -47,26 +33,18 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
                       const LaunchOpt &o = LaunchOpt()) {
     mq_index *idx = c->idx;
     if (n == 0) return MQ_OK;
-    // a context with an anchor reservation takes the anchors pair (never for the instrumented launch, nor for mq_kminmers_batch's)
-    mq_ctx *ac = o.anchors_of ? o.anchors_of : c;
-    const bool anch = ac->anch_reads != 0 && !o.instrumented && !o.d_dump && !idx->split;
-    if (anch && !o.anchor_redo) {
-        int rc = anchors_admit(ac, n);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(ac->anch_counters, 0, sizeof(AnchorCounters), st));  // once per batch: its redo launches claim from the same cursor
-        ac->anch_n = n;  // from here on mq_ctx_anchors describes this batch
-    }
-    // ... and one with a chains reservation the chains pair (both: the pair that writes both)
-    const bool chn = ac->chn_reads != 0 && !o.instrumented && !o.d_dump && !idx->split;
+    // a context with an anchors reservation takes the anchors pair, one with a chains reservation the chains pair, one with both the pair
+    // that writes both (never for the instrumented launch, nor for mq_kminmers_batch's, nor in the split pipeline)
+    mq_ctx *oc = o.outputs_of ? o.outputs_of : c;
+    const bool delivers = !o.instrumented && !o.d_dump && !idx->split;
+    const bool anch = oc->anchors.reads != 0 && delivers, chn = oc->chains.reads != 0 && delivers;
+    int rc;
+    if (anch && !o.redo && ((rc = oc->anchors.admit(n)) || (rc = oc->anchors.begin_batch(n, st)))) return rc;
     if (chn) {
         if (o.scratch_override && !o.chain_windows_override) return set_err(MQ_ESTATE, "a redo launch of a chains context without chain windows");
-        if (!o.chain_redo) {
-            int rc = chains_admit(ac, n);
-            if (rc) return rc;
-            HIPCHK(hipMemsetAsync(ac->chn_counters, 0, sizeof(ChainCounters), st));  // once per batch, as the anchors'
-            ac->chn_n = n;  // from here on mq_ctx_chains describes this batch
-        }
+        if (!o.redo && ((rc = oc->chains.admit(n)) || (rc = oc->chains.begin_batch(n, st)))) return rc;
     }
+    const auto id_map = [&o](const Buf<uint32_t> &own) -> const uint32_t * { return !o.redo ? nullptr : o.d_ids ? o.d_ids : own.p; };
     HIPCHK(hipMemsetAsync(c->d_counter, 0, sizeof(MapCounters), st));
     HIPCHK(hipEventRecord(c->ev0, st));
     MapArgs A;
@@ -99,21 +77,21 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     A.stats64 = &c->d_counter.p->probe;
     A.work = c->work;
     A.heavy_first = idx->heavy_first ? 1u : 0u;
-    A.anchors.pool = anch ? ac->anch_pool.p : nullptr;
-    A.anchors.cap = anch ? (uint32_t)ac->anch_cap : 0u;
-    A.anchors.counters = anch ? ac->anch_counters.p : nullptr;
-    A.anchor_spans = anch ? ac->anch_spans.p : nullptr;
-    A.anchor_ids = anch ? o.d_anchor_ids : nullptr;
+    A.anchors.pool = anch ? oc->anchors.pool.p : nullptr;
+    A.anchors.cap = anch ? (uint32_t)oc->anchors.cap : 0u;
+    A.anchors.counters = anch ? oc->anchors.counters.p : nullptr;
+    A.anchor_spans = anch ? oc->anchors.spans.p : nullptr;
+    A.anchor_ids = anch ? id_map(oc->anchors.ids) : nullptr;
     if (chn) {
         // the chains output's launch arguments: into the counter block, behind its clearing (from pageable memory: the bytes are taken now)
         ChainLaunch cl;
-        cl.pool = ac->chn_pool.p;
-        cl.cap = (uint32_t)ac->chn_cap;
+        cl.pool = oc->chains.pool.p;
+        cl.cap = (uint32_t)oc->chains.cap;
         cl.win_cap = chain_win_cap(A.cap_matches);
-        cl.counters = ac->chn_counters.p;
-        cl.windows = o.scratch_override ? o.chain_windows_override : ac->chn_windows.p;
-        cl.spans = ac->chn_spans.p;
-        cl.ids = o.d_chain_ids;
+        cl.counters = oc->chains.counters.p;
+        cl.windows = o.scratch_override ? o.chain_windows_override : oc->chn_windows.p;
+        cl.spans = oc->chains.spans.p;
+        cl.ids = id_map(oc->chains.ids);
         HIPCHK(hipMemcpyAsync(&c->d_counter.p->chains, &cl, sizeof(ChainLaunch), hipMemcpyHostToDevice, st));
     }
     if (!idx->split) {
@@ -154,15 +132,8 @@ static int launch_map(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offse
     }
     HIPCHK(hipEventRecord(c->ev1, st));
     c->ev_valid = true;
-    if (anch) {
-        HIPCHK(hipEventRecord(ac->anch_done, st));
-        ac->anch_ran = true;
-    }
-    if (chn) {
-        HIPCHK(hipEventRecord(ac->chn_done, st));
-        ac->chn_ran = true;
-    }
-    return MQ_OK;
+    if (anch && (rc = oc->anchors.mark_done(st))) return rc;
+    return chn ? oc->chains.mark_done(st) : MQ_OK;
 }
 
 // Reads that came back MQ_HIT_OVERFLOW (more Match runs than the per-wave scratch holds, or a minimizer list denser than its
@@ -197,7 +168,7 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
     Buf<uint64_t> d_so;
     Buf<mq_hit> d_sh;
     hipError_t e = big.try_alloc((uint64_t)rgrid * waves * cap);
-    if (e == hipSuccess && c->chn_reads) e = big_chains.try_alloc((uint64_t)rgrid * waves * chain_win_cap(cap));
+    if (e == hipSuccess && c->chains.reads) e = big_chains.try_alloc((uint64_t)rgrid * waves * chain_win_cap(cap));
     if (e == hipSuccess) e = d_sb.try_alloc(sub_total + 1);
     if (e == hipSuccess) e = d_so.try_alloc(so.size());
     if (e == hipSuccess) e = d_sh.try_alloc(redo.size());
@@ -211,15 +182,12 @@ static int redo_relaunch(mq_ctx *c, const std::vector<uint32_t> &redo, const std
         o.cap_override = cap;
         o.grid_override = rgrid;
         o.f16 = 65536u;
-        if (c->anch_reads) {  // a read that is redone delivers its anchors from the redo: same pool, same cursor, its span to the batch's read number
-            e = hipMemcpyAsync(c->anch_ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-            o.anchor_redo = true;
-            o.d_anchor_ids = c->anch_ids;
-        }
-        if (c->chn_reads && e == hipSuccess) {  // ... and its chains
-            e = hipMemcpyAsync(c->chn_ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-            o.chain_redo = true;
-            o.d_chain_ids = c->chn_ids;
+        // a read that is redone delivers its anchors and chains from the redo: same pools, same cursors, its spans to the batch's read number
+        // (each reservation's own `ids`)
+        o.redo = true;
+        if (c->anchors.reads) e = hipMemcpyAsync(c->anchors.ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (c->chains.reads && e == hipSuccess) {
+            e = hipMemcpyAsync(c->chains.ids, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
             o.chain_windows_override = big_chains;
         }
         if (e == hipSuccess) rrc = launch_map(c, d_sb, d_so, (uint32_t)redo.size(), d_sh, c->stream, o);
@@ -375,7 +343,7 @@ static int ctx_reserve_redo(mq_ctx *c, uint32_t max_reads, uint32_t max_read_len
     if ((rc = a->bases.alloc((uint64_t)max_reads * stride)) || (rc = a->offsets.alloc((uint64_t)max_reads + 1)) || (rc = a->lens.alloc(max_reads)) ||
         (rc = a->ids.alloc(max_reads)) || (rc = a->src.alloc(max_reads)) || (rc = a->hits.alloc(max_reads)) ||
         (rc = a->windows.alloc((uint64_t)a->grid * REDO_WAVES * a->cap)) || (rc = a->counters.alloc(1)) ||
-        (c->chn_reads && (rc = a->chain_windows.alloc((uint64_t)a->grid * REDO_WAVES * chain_win_cap(a->cap)))))
+        (c->chains.reads && (rc = a->chain_windows.alloc((uint64_t)a->grid * REDO_WAVES * chain_win_cap(a->cap)))))
         return rc;
     std::vector<uint64_t> slot_at((size_t)max_reads + 1);
     for (size_t j = 0; j <= max_reads; ++j) slot_at[j] = j * stride;
@@ -394,9 +362,8 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     int rc;
     HIPCHK(hipMemsetAsync(a.counters, 0, sizeof(RedoCounters), st));
     HIPCHK(hipMemsetAsync(a.lens, 0, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims is a read of length 0
-    const bool anch = c->anch_reads != 0 && !c->idx->split;
-    const bool chn = c->chn_reads != 0 && !c->idx->split;
-    if (anch || chn) HIPCHK(hipMemsetAsync(a.ids, 0xFF, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims writes no span
+    const bool outputs = (c->anchors.reads != 0 || c->chains.reads != 0) && !c->idx->split;
+    if (outputs) HIPCHK(hipMemsetAsync(a.ids, 0xFF, (size_t)a.max_reads * sizeof(uint32_t), st));  // a slot nobody claims writes no span
     if ((rc = launch(redo_collect_kernel, (n + 255u) / 256u, 256, st, d_out, d_offsets, n, a.max_reads, a.max_read_len, a.counters, a.ids, a.src, a.lens))) return rc;
     if ((rc = launch(redo_copy_kernel, (a.max_reads + REDO_COPY_WAVES - 1u) / REDO_COPY_WAVES, 64 * REDO_COPY_WAVES, st, d_bases, a.src, a.lens, a.max_reads, a.bases, a.stride))) return rc;
     LaunchOpt o;
@@ -405,17 +372,11 @@ static int redo_in_stream(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_o
     o.grid_override = a.grid;
     o.f16 = 65536u;
     o.d_lens = a.lens;
-    if (anch) {  // the slot-to-read array is the arena launch's id map; stream order makes the redo's span the read's final one
-        o.anchor_redo = true;
-        o.d_anchor_ids = a.ids;
-        o.anchors_of = c;
-    }
-    if (chn) {
-        o.chain_redo = true;
-        o.d_chain_ids = a.ids;
-        o.anchors_of = c;
-        o.chain_windows_override = a.chain_windows;
-    }
+    // the arena's launch delivers to c's reservations; the slot-to-read array is its id map, and stream order makes the redo's span the read's final one
+    o.outputs_of = c;
+    o.redo = true;
+    o.d_ids = a.ids;
+    if (c->chains.reads) o.chain_windows_override = a.chain_windows;
     if ((rc = launch_map(&a.sub, a.bases, a.offsets, a.max_reads, a.hits, st, o))) return rc;
     if ((rc = launch(redo_scatter_kernel, (a.max_reads + 255u) / 256u, 256, st, a.hits, a.ids, a.counters, a.max_reads, d_out))) return rc;
     HIPCHK(hipEventRecord(a.done, st));
@@ -439,165 +400,101 @@ static int ctx_redo_counts(mq_ctx *c, uint32_t *redone, uint32_t *left) {
     return MQ_OK;
 }
 
-// ---- the anchor output (mq_ctx_reserve_anchors): spans, pool, counter block and their host copies belong to the context and are
-// allocated here; a launch only points its MapArgs at them.
+// ---- the pooled outputs (PooledOutput, mq_host_state.hpp): the two operations that need the context's own
 
-// (0, 0): the reservation goes.  A failure leaves the context with the reservation it had.
-static int ctx_reserve_anchors(mq_ctx *c, uint32_t max_reads, uint64_t max_anchors) {
+// A failure leaves the context with the reservation it had: everything is allocated into locals first.
+template <class Item, class Span>
+template <class Alloc, class Commit>
+int PooledOutput<Item, Span>::reserve(mq_ctx *c, uint32_t max_reads, uint64_t max_entries, Alloc alloc_extra, Commit commit_extra) {
     mq_index *idx = c->idx;
     int rc = ctx_require_idle(c);
     if (rc) return rc;
     if ((rc = use_device(idx))) return rc;
-    const bool release = max_reads == 0 && max_anchors == 0;
-    Buf<mq_anchor> pool;
-    Buf<mq_anchor_span> spans;
-    Buf<AnchorCounters> counters;
-    Buf<uint32_t> ids;
-    PinnedBuf<mq_anchor> h_pool;
-    PinnedBuf<mq_anchor_span> h_spans;
-    PinnedBuf<AnchorCounters> h_counters;
-    hipEvent_t done = nullptr;
+    const bool release = max_reads == 0 && max_entries == 0;
+    Buf<Item> new_pool;
+    Buf<Span> new_spans;
+    Buf<PoolCounters> new_counters;
+    Buf<uint32_t> new_ids;
+    PinnedBuf<Item> new_h_pool;
+    PinnedBuf<Span> new_h_spans;
+    PinnedBuf<PoolCounters> new_h_counters;
+    hipEvent_t new_done = nullptr;
     if (!release) {
-        if (max_reads == 0 || max_anchors == 0) return set_err(MQ_EINVAL, "max_reads and max_anchors must both be positive (or both 0: release)");
-        if (max_reads > WORK_ID_MASK || max_anchors >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and max_anchors below 2^32 - 1");
-        if (idx->split) return set_err(MQ_EINVAL, "the split pipeline (MQ_PIPELINE=split) writes no anchors: reserve them on an index that runs the fused kernels");
+        const std::string max_noun = std::string("max_") + noun;
+        if (max_reads == 0 || max_entries == 0) return set_err(MQ_EINVAL, "max_reads and " + max_noun + " must both be positive (or both 0: release)");
+        if (max_reads > WORK_ID_MASK || max_entries >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and " + max_noun + " below 2^32 - 1");
+        if (idx->split)
+            return set_err(MQ_EINVAL, std::string("the split pipeline (MQ_PIPELINE=split) writes no ") + noun + ": reserve them on an index that runs the fused kernels");
         if ((rc = ensure_outputs_geometry(idx))) return rc;
-        if ((rc = pool.alloc(max_anchors)) || (rc = spans.alloc(max_reads)) || (rc = counters.alloc(1)) || (rc = ids.alloc(max_reads)) ||
-            (rc = h_pool.alloc(max_anchors)) || (rc = h_spans.alloc(max_reads)) || (rc = h_counters.alloc(1)))
+        if ((rc = new_pool.alloc(max_entries)) || (rc = new_spans.alloc(max_reads)) || (rc = new_counters.alloc(1)) || (rc = new_ids.alloc(max_reads)) ||
+            (rc = alloc_extra()) || (rc = new_h_pool.alloc(max_entries)) || (rc = new_h_spans.alloc(max_reads)) || (rc = new_h_counters.alloc(1)))
             return rc;
-        if (!c->anch_done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        if (!done) HIPCHK(hipEventCreateWithFlags(&new_done, hipEventDisableTiming));
     }
-    if (c->anch_ran) (void)hipEventSynchronize(c->anch_done);  // the stream of the last launch has passed the arrays that go
-    c->anch_pool = std::move(pool);
-    c->anch_spans = std::move(spans);
-    c->anch_counters = std::move(counters);
-    c->anch_ids = std::move(ids);
-    c->h_anch_pool = std::move(h_pool);
-    c->h_anch_spans = std::move(h_spans);
-    c->h_anch_counters = std::move(h_counters);
-    if (done) c->anch_done.h = done;
-    c->anch_reads = max_reads;
-    c->anch_cap = max_anchors;
-    c->anch_ran = false;
-    c->anch_n = 0;
+    if (ran) (void)hipEventSynchronize(done);  // the stream of the last launch has passed the arrays that go
+    pool = std::move(new_pool);
+    spans = std::move(new_spans);
+    counters = std::move(new_counters);
+    ids = std::move(new_ids);
+    commit_extra();
+    h_pool = std::move(new_h_pool);
+    h_spans = std::move(new_h_spans);
+    h_counters = std::move(new_h_counters);
+    if (new_done) done.h = new_done;
+    reads = max_reads;
+    cap = max_entries;
+    ran = false;
+    n = 0;
     return MQ_OK;
 }
 
-// host copies of the last batch's spans, anchors and counters, once everything that writes them is done
-static int ctx_anchors(mq_ctx *c, const mq_anchor_span **spans, const mq_anchor **anchors, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
-                       uint32_t *dropped_reads) {
-    if (!c->anch_reads) return set_err(MQ_ESTATE, "no anchors reserved on this context: call mq_ctx_reserve_anchors first");
+template <class Item, class Span>
+int PooledOutput<Item, Span>::read_back(mq_ctx *c, const Span **out_spans, const Item **out_pool, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
+                                        uint32_t *dropped_reads) {
+    if (!reads) return require_reserved();
     if (c->fx_kind != FxKind::None) return set_err(MQ_ESTATE, "context has a submitted piece: call mq_ctx_wait_fasta first");
     int rc;
-    if (c->pending && (rc = ctx_wait(c))) return rc;  // (the host-driven redo, which delivers the redone reads' anchors, runs there)
-    *spans = c->h_anch_spans;
-    *anchors = c->h_anch_pool;
+    if (c->pending && (rc = ctx_wait(c))) return rc;  // (the host-driven redo, which delivers the redone reads' items, runs there)
+    *out_spans = h_spans;
+    *out_pool = h_pool;
     *n_reads = 0;
     *stored = *needed = 0;
     *dropped_reads = 0;
-    if (!c->anch_ran || c->anch_n == 0) return MQ_OK;  // no batch yet, or one without reads
+    if (!ran || n == 0) return MQ_OK;  // no batch yet, or one without reads
     if ((rc = use_device(c->idx))) return rc;
-    HIPCHK(hipEventSynchronize(c->anch_done));
-    HIPCHK(hipMemcpy(c->h_anch_counters, c->anch_counters, sizeof(AnchorCounters), hipMemcpyDeviceToHost));
-    const AnchorCounters &v = *c->h_anch_counters.p;
-    const uint64_t have = std::min<uint64_t>(v.cursor, c->anch_cap);
-    HIPCHK(hipMemcpy(c->h_anch_spans, c->anch_spans, (size_t)c->anch_n * sizeof(mq_anchor_span), hipMemcpyDeviceToHost));
-    if (have) HIPCHK(hipMemcpy(c->h_anch_pool, c->anch_pool, (size_t)have * sizeof(mq_anchor), hipMemcpyDeviceToHost));
-    *n_reads = c->anch_n;
+    HIPCHK(hipEventSynchronize(done));
+    HIPCHK(hipMemcpy(h_counters, counters, sizeof(PoolCounters), hipMemcpyDeviceToHost));
+    const PoolCounters &v = *h_counters.p;
+    const uint64_t have = std::min<uint64_t>(v.cursor, cap);
+    HIPCHK(hipMemcpy(h_spans, spans, (size_t)n * sizeof(Span), hipMemcpyDeviceToHost));
+    if (have) HIPCHK(hipMemcpy(h_pool, pool, (size_t)have * sizeof(Item), hipMemcpyDeviceToHost));
+    *n_reads = n;
     *stored = have;
     *needed = v.cursor;
     *dropped_reads = v.dropped_reads;
     return MQ_OK;
 }
 
-static int ctx_anchors_device(mq_ctx *c, const mq_anchor_span **d_spans, const mq_anchor **d_anchors) {
-    if (!c->anch_reads) return set_err(MQ_ESTATE, "no anchors reserved on this context: call mq_ctx_reserve_anchors first");
-    *d_spans = c->anch_spans;
-    *d_anchors = c->anch_pool;
-    return MQ_OK;
+static int ctx_reserve_anchors(mq_ctx *c, uint32_t max_reads, uint64_t max_anchors) {
+    return c->anchors.reserve(c, max_reads, max_anchors, [] { return (int)MQ_OK; }, [] {});
 }
 
-// ---- the chains output (mq_ctx_reserve_chains): the anchors' plumbing once more, plus the chain windows -- the context's, and its redo
-// arena's when it has one (an arena reserved later allocates its own: ctx_reserve_redo)
-
-// (0, 0): the reservation goes.  A failure leaves the context with the reservation it had.
+// ... the chains bring the chain windows: the context's, and its redo arena's when it has one (an arena reserved later allocates its own:
+// ctx_reserve_redo)
 static int ctx_reserve_chains(mq_ctx *c, uint32_t max_reads, uint64_t max_chains) {
     mq_index *idx = c->idx;
-    int rc = ctx_require_idle(c);
-    if (rc) return rc;
-    if ((rc = use_device(idx))) return rc;
-    const bool release = max_reads == 0 && max_chains == 0;
-    Buf<mq_chain> pool;
-    Buf<mq_chain_span> spans;
-    Buf<ChainCounters> counters;
-    Buf<uint32_t> ids;
     Buf<ChainRec> windows, arena_windows;
-    PinnedBuf<mq_chain> h_pool;
-    PinnedBuf<mq_chain_span> h_spans;
-    PinnedBuf<ChainCounters> h_counters;
-    hipEvent_t done = nullptr;
-    if (!release) {
-        if (max_reads == 0 || max_chains == 0) return set_err(MQ_EINVAL, "max_reads and max_chains must both be positive (or both 0: release)");
-        if (max_reads > WORK_ID_MASK || max_chains >= 0xFFFFFFFFull) return set_err(MQ_EINVAL, "max_reads must be below 2^30 and max_chains below 2^32 - 1");
-        if (idx->split) return set_err(MQ_EINVAL, "the split pipeline (MQ_PIPELINE=split) writes no chains: reserve them on an index that runs the fused kernels");
-        if ((rc = ensure_outputs_geometry(idx))) return rc;
-        if ((rc = pool.alloc(max_chains)) || (rc = spans.alloc(max_reads)) || (rc = counters.alloc(1)) || (rc = ids.alloc(max_reads)) ||
-            (rc = windows.alloc((uint64_t)map_waves_for(idx, max_reads) * chain_win_cap(idx->cap_matches))) ||
-            (c->redo && (rc = arena_windows.alloc((uint64_t)c->redo->grid * REDO_WAVES * chain_win_cap(c->redo->cap)))) ||
-            (rc = h_pool.alloc(max_chains)) || (rc = h_spans.alloc(max_reads)) || (rc = h_counters.alloc(1)))
+    return c->chains.reserve(
+        c, max_reads, max_chains,
+        [&]() -> int {
+            int rc = windows.alloc((uint64_t)map_waves_for(idx, max_reads) * chain_win_cap(idx->cap_matches));
+            if (!rc && c->redo) rc = arena_windows.alloc((uint64_t)c->redo->grid * REDO_WAVES * chain_win_cap(c->redo->cap));
             return rc;
-        if (!c->chn_done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    }
-    if (c->chn_ran) (void)hipEventSynchronize(c->chn_done);  // the stream of the last launch has passed the arrays that go
-    c->chn_pool = std::move(pool);
-    c->chn_spans = std::move(spans);
-    c->chn_counters = std::move(counters);
-    c->chn_ids = std::move(ids);
-    c->chn_windows = std::move(windows);
-    if (c->redo) c->redo->chain_windows = std::move(arena_windows);
-    c->h_chn_pool = std::move(h_pool);
-    c->h_chn_spans = std::move(h_spans);
-    c->h_chn_counters = std::move(h_counters);
-    if (done) c->chn_done.h = done;
-    c->chn_reads = max_reads;
-    c->chn_cap = max_chains;
-    c->chn_ran = false;
-    c->chn_n = 0;
-    return MQ_OK;
-}
-
-// host copies of the last batch's spans, chains and counters, once everything that writes them is done
-static int ctx_chains(mq_ctx *c, const mq_chain_span **spans, const mq_chain **chains, uint32_t *n_reads, uint64_t *stored, uint64_t *needed,
-                      uint32_t *dropped_reads) {
-    if (!c->chn_reads) return set_err(MQ_ESTATE, "no chains reserved on this context: call mq_ctx_reserve_chains first");
-    if (c->fx_kind != FxKind::None) return set_err(MQ_ESTATE, "context has a submitted piece: call mq_ctx_wait_fasta first");
-    int rc;
-    if (c->pending && (rc = ctx_wait(c))) return rc;  // (the host-driven redo, which delivers the redone reads' chains, runs there)
-    *spans = c->h_chn_spans;
-    *chains = c->h_chn_pool;
-    *n_reads = 0;
-    *stored = *needed = 0;
-    *dropped_reads = 0;
-    if (!c->chn_ran || c->chn_n == 0) return MQ_OK;  // no batch yet, or one without reads
-    if ((rc = use_device(c->idx))) return rc;
-    HIPCHK(hipEventSynchronize(c->chn_done));
-    HIPCHK(hipMemcpy(c->h_chn_counters, c->chn_counters, sizeof(ChainCounters), hipMemcpyDeviceToHost));
-    const ChainCounters &v = *c->h_chn_counters.p;
-    const uint64_t have = std::min<uint64_t>(v.cursor, c->chn_cap);
-    HIPCHK(hipMemcpy(c->h_chn_spans, c->chn_spans, (size_t)c->chn_n * sizeof(mq_chain_span), hipMemcpyDeviceToHost));
-    if (have) HIPCHK(hipMemcpy(c->h_chn_pool, c->chn_pool, (size_t)have * sizeof(mq_chain), hipMemcpyDeviceToHost));
-    *n_reads = c->chn_n;
-    *stored = have;
-    *needed = v.cursor;
-    *dropped_reads = v.dropped_reads;
-    return MQ_OK;
-}
-
-static int ctx_chains_device(mq_ctx *c, const mq_chain_span **d_spans, const mq_chain **d_chains) {
-    if (!c->chn_reads) return set_err(MQ_ESTATE, "no chains reserved on this context: call mq_ctx_reserve_chains first");
-    *d_spans = c->chn_spans;
-    *d_chains = c->chn_pool;
-    return MQ_OK;
+        },
+        [&] {
+            c->chn_windows = std::move(windows);
+            if (c->redo) c->redo->chain_windows = std::move(arena_windows);
+        });
 }
 
 static int ctx_map_device(mq_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint32_t n, uint64_t total_bases, mq_hit *d_out,
@@ -940,7 +837,7 @@ int mq_ctx_anchors(mq_ctx *ctx, const mq_anchor_span **spans, const mq_anchor **
                    uint32_t *dropped_reads) {
     return guarded([&]() -> int {
         if (!ctx || !spans || !anchors || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
-        return ctx_anchors(ctx, spans, anchors, n_reads, stored, needed, dropped_reads);
+        return ctx->anchors.read_back(ctx, spans, anchors, n_reads, stored, needed, dropped_reads);
     });
 }
 
@@ -949,14 +846,14 @@ int mq_map_anchors(mq_index *idx, const mq_anchor_span **spans, const mq_anchor 
     return guarded([&]() -> int {
         if (!idx || !spans || !anchors || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        return ctx_anchors(idx->def_ctx.get(), spans, anchors, n_reads, stored, needed, dropped_reads);
+        return idx->def_ctx->anchors.read_back(idx->def_ctx.get(), spans, anchors, n_reads, stored, needed, dropped_reads);
     });
 }
 
 int mq_ctx_anchors_device(mq_ctx *ctx, const mq_anchor_span **d_spans, const mq_anchor **d_anchors) {
     return guarded([&]() -> int {
         if (!ctx || !d_spans || !d_anchors) return set_err(MQ_EINVAL, "bad arguments");
-        return ctx_anchors_device(ctx, d_spans, d_anchors);
+        return ctx->anchors.device_pointers(d_spans, d_anchors);
     });
 }
 
@@ -979,7 +876,7 @@ int mq_ctx_chains(mq_ctx *ctx, const mq_chain_span **spans, const mq_chain **cha
                   uint32_t *dropped_reads) {
     return guarded([&]() -> int {
         if (!ctx || !spans || !chains || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
-        return ctx_chains(ctx, spans, chains, n_reads, stored, needed, dropped_reads);
+        return ctx->chains.read_back(ctx, spans, chains, n_reads, stored, needed, dropped_reads);
     });
 }
 
@@ -988,14 +885,14 @@ int mq_map_chains(mq_index *idx, const mq_chain_span **spans, const mq_chain **c
     return guarded([&]() -> int {
         if (!idx || !spans || !chains || !n_reads || !stored || !needed || !dropped_reads) return set_err(MQ_EINVAL, "bad arguments");
         std::lock_guard<std::mutex> lk(idx->mu);
-        return ctx_chains(idx->def_ctx.get(), spans, chains, n_reads, stored, needed, dropped_reads);
+        return idx->def_ctx->chains.read_back(idx->def_ctx.get(), spans, chains, n_reads, stored, needed, dropped_reads);
     });
 }
 
 int mq_ctx_chains_device(mq_ctx *ctx, const mq_chain_span **d_spans, const mq_chain **d_chains) {
     return guarded([&]() -> int {
         if (!ctx || !d_spans || !d_chains) return set_err(MQ_EINVAL, "bad arguments");
-        return ctx_chains_device(ctx, d_spans, d_chains);
+        return ctx->chains.device_pointers(d_spans, d_chains);
     });
 }
 

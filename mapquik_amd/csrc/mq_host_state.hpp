@@ -27,6 +27,69 @@ static int launch(void (*kernel)(KA...), uint32_t grid, uint32_t block, hipStrea
 enum class FxKind { None, Fasta, Fastq, FastaLines };
 
 struct RedoArena;  // (below: it holds an mq_ctx of its own)
+struct mq_ctx;
+
+// A pooled per-read output of a context's batches -- the anchors (mq_ctx_reserve_anchors) and the chains (mq_ctx_reserve_chains): read r's
+// items are pool[spans[r].first, + spans[r].count), claimed by the kernels from one cursor (PoolCounters, mq_blocks.hpp).  reads == 0: no
+// reservation -- the context runs the kernels it always ran.  Everything is allocated at the reservation, never by a launch; a launch only
+// points its arguments here.  What holds for every such output:
+//   - the counter block is cleared once per BATCH, by the batch's main launch (begin_batch), not per launch: the batch's redo launches claim
+//     from the same cursor, and place each span where an id map says (the arena's slot-to-read array, or `ids` for the host-driven redo);
+//   - `done` is recorded on the stream of every launch sequence that delivered (the context's, or the caller's), and whoever reads the
+//     arrays or lets them go waits for it;
+//   - a reservation is refused while a batch or a piece is pending, and a failed one leaves the reservation that was there.
+template <class Item, class Span>
+struct PooledOutput {
+    const char *const noun, *const adjective;  // "anchors" / "anchor", "chains" / "chains": the error texts, and mq_ctx_reserve_<noun>
+    uint32_t reads = 0;              // max_reads
+    uint64_t cap = 0;                // max entries of the pool (< 2^32 - 1)
+    Buf<Item> pool;
+    Buf<Span> spans;
+    Buf<PoolCounters> counters;      // one block
+    Buf<uint32_t> ids;               // the host-driven redo's read numbers (redo_relaunch)
+    PinnedBuf<Item> h_pool;          // read_back's host copies
+    PinnedBuf<Span> h_spans;
+    PinnedBuf<PoolCounters> h_counters;
+    ScopedEvent done;
+    bool ran = false;                // `done` has been recorded since the reservation
+    uint32_t n = 0;                  // reads of the last batch that delivered
+
+    PooledOutput(const char *noun_, const char *adjective_) : noun(noun_), adjective(adjective_) {}
+    // A batch is refused when it has more reads than spans.  The entry points ask before they queue anything (a FASTX piece: before its map
+    // launch -- the number of records is known only at the wait); launch_map asks again, where the spans are about to be written.
+    int admit(uint32_t batch) const {
+        if (reads && batch > reads)
+            return set_err(MQ_EINVAL, std::string("more reads in the batch than the context's ") + adjective + " reservation holds (mq_ctx_reserve_" + noun + ": max_reads)");
+        return MQ_OK;
+    }
+    // the main (not a redo) launch of a batch, in front of its kernels: from here on read_back describes this batch
+    int begin_batch(uint32_t batch, hipStream_t st) {
+        HIPCHK(hipMemsetAsync(counters, 0, sizeof(PoolCounters), st));
+        n = batch;
+        return MQ_OK;
+    }
+    // behind the kernels of every launch sequence that delivered
+    int mark_done(hipStream_t st) {
+        HIPCHK(hipEventRecord(done, st));
+        ran = true;
+        return MQ_OK;
+    }
+    int require_reserved() const {
+        return reads ? MQ_OK : set_err(MQ_ESTATE, std::string("no ") + noun + " reserved on this context: call mq_ctx_reserve_" + noun + " first");
+    }
+    int device_pointers(const Span **d_spans, const Item **d_pool) const {
+        if (!reads) return require_reserved();
+        *d_spans = spans;
+        *d_pool = pool;
+        return MQ_OK;
+    }
+    // (mq_capi_map.hpp, beside ctx_require_idle and ctx_wait) (0, 0) releases; alloc_extra() / commit_extra(): what the reservation brings
+    // beyond the owner's arrays -- allocated with them, committed with them (a release commits what was never allocated: it goes)
+    template <class Alloc, class Commit>
+    int reserve(mq_ctx *c, uint32_t max_reads, uint64_t max_entries, Alloc alloc_extra, Commit commit_extra);
+    // host copies of the last batch's spans, pool and counters, once everything that writes them is done
+    int read_back(mq_ctx *c, const Span **out_spans, const Item **out_pool, uint32_t *n_reads, uint64_t *stored, uint64_t *needed, uint32_t *dropped_reads);
+};
 
 // One stream slot: everything a map launch sequence writes (work counters, Match scratch, minimizer lists,
 // events) plus the staging buffers of the host-buffer entry points.  Launch sequences of DIFFERENT contexts of one index
@@ -80,36 +143,13 @@ struct mq_ctx {
     const uint32_t *p_lens = nullptr;
     uint32_t p_n = 0;
     mq_hit *p_out = nullptr;
-    // mq_ctx_reserve_anchors: the anchor output of the context's batches (anch_reads == 0: no reservation -- the context runs the kernels it
-    // always ran).  Allocated at the reservation, never by a launch.
-    uint32_t anch_reads = 0;              // max_reads
-    uint64_t anch_cap = 0;                // max_anchors (< 2^32 - 1)
-    Buf<mq_anchor> anch_pool;
-    Buf<mq_anchor_span> anch_spans;
-    Buf<AnchorCounters> anch_counters;    // one block (mq_blocks.hpp), cleared in front of every batch's main launch
-    Buf<uint32_t> anch_ids;               // the host-driven redo's read numbers (MapArgs::anchor_ids of redo_relaunch)
-    PinnedBuf<mq_anchor> h_anch_pool;     // mq_ctx_anchors' host copies
-    PinnedBuf<mq_anchor_span> h_anch_spans;
-    PinnedBuf<AnchorCounters> h_anch_counters;
-    ScopedEvent anch_done;                // behind the last launch sequence that wrote anchors (recorded on ITS stream: the context's, or the caller's)
-    bool anch_ran = false;                // ... recorded at least once
-    uint32_t anch_n = 0;                  // reads of the last batch that delivered anchors
-    // mq_ctx_reserve_chains: the chains output of the context's batches, member for member what the anchors have (chn_reads == 0: no
-    // reservation), and the chain windows of the context's launches.  Allocated at the reservation, never by a launch -- but for the windows
-    // of the host-driven redo, whose size is the longest redone read's: they live as long as that redo's Match windows do (redo_relaunch).
-    uint32_t chn_reads = 0;               // max_reads
-    uint64_t chn_cap = 0;                 // max_chains (< 2^32 - 1)
-    Buf<mq_chain> chn_pool;
-    Buf<mq_chain_span> chn_spans;
-    Buf<ChainCounters> chn_counters;      // one block (mq_blocks.hpp), cleared in front of every batch's main launch
-    Buf<uint32_t> chn_ids;                // the host-driven redo's read numbers (ChainLaunch::ids of redo_relaunch)
-    Buf<ChainRec> chn_windows;            // a window of chain_win_cap(cap_matches) records for every mapping wave a batch of max_reads reads can employ
-    PinnedBuf<mq_chain> h_chn_pool;       // mq_ctx_chains' host copies
-    PinnedBuf<mq_chain_span> h_chn_spans;
-    PinnedBuf<ChainCounters> h_chn_counters;
-    ScopedEvent chn_done;                 // behind the last launch sequence that wrote chains (recorded on ITS stream)
-    bool chn_ran = false;                 // ... recorded at least once
-    uint32_t chn_n = 0;                   // reads of the last batch that delivered chains
+    // mq_ctx_reserve_anchors / mq_ctx_reserve_chains: the two pooled outputs of the context's batches (PooledOutput above), and the chain
+    // windows of the context's launches, which come and go with the chains reservation: a window of chain_win_cap(cap_matches) records for
+    // every mapping wave a batch of max_reads reads can employ.  (The windows of the host-driven redo, whose size is the longest redone
+    // read's, live as long as that redo's Match windows do: redo_relaunch.)
+    PooledOutput<mq_anchor, mq_anchor_span> anchors{"anchors", "anchor"};
+    PooledOutput<mq_chain, mq_chain_span> chains{"chains", "chains"};
+    Buf<ChainRec> chn_windows;
     // mq_ctx_reserve_redo: what the device form needs to redo its overflow reads in stream (none: they come back MQ_HIT_OVERFLOW).  The
     // last member, so the first to go: it waits for its own last launch, and its buffers go before the context's.
     std::unique_ptr<RedoArena> redo;

@@ -386,7 +386,9 @@ def over(mq, oracle, simlib):
     diag = ox.map_batch_diag(bases, offs, po, threads=4)[1]
     n_over = int((diag["n_matches"] > CM.MATCH_CAP).sum())
     assert 3 <= n_over < offs.size - 1
-    yield dict(n_over=n_over, ix=ix, bases=bases, offs=offs, exp=exp, want=want, need=sum(len(e) for e in exp), lens=(offs[1:] - offs[:-1]).astype(np.int64))
+    aexp = A.batch(oracle, ox, po, bases, offs)  # (the anchors of the same batch: test_both_reservations_through_*)
+    yield dict(n_over=n_over, ix=ix, bases=bases, offs=offs, exp=exp, want=want, need=sum(len(e) for e in exp), lens=(offs[1:] - offs[:-1]).astype(np.int64),
+               aexp=aexp, aneed=sum(len(e.runs) for e in aexp if e), over_mapped=[int(r) for r in np.flatnonzero(diag["n_matches"] > CM.MATCH_CAP) if aexp[r]])
     ix.close()
 
 
@@ -426,6 +428,71 @@ def test_in_stream_redo_delivers_chains(mq, over, arena_first):
     assert hits.tobytes() == fx["want"].tobytes()
     assert c.redo_counts() == (fx["n_over"], 0)
     assert not _check(got, exp, need, hits)
+    c.close()
+    for b in (db, do, dout):
+        b.free()
+
+
+def _both_reserving(c, fx):
+    """the chains and the anchors reservation on c (which may have a redo arena already), spans and pools of both filled with 0xFF"""
+    n = fx["offs"].size - 1
+    assert fx["over_mapped"]  # a redone read with a winning chain: the redo's one id map places a span of either kind
+    c.reserve_chains(n, fx["need"])
+    c.reserve_anchors(n, fx["aneed"])
+    _poison(c, n, fx["need"])
+    sp, an = c.anchors_device()
+    assert hipmem.hip().hipMemset(sp, 0xFF, 8 * n) == 0 and hipmem.hip().hipMemset(an, 0xFF, 20 * fx["aneed"]) == 0
+    hipmem.device_sync()
+
+
+def _check_anchors(got, aexp, aneed):
+    """spans and anchors against the anchors model, read for read (test_anchors_and_chains_together's comparison)"""
+    spans, anchors, info = got
+    assert spans.size == len(aexp)
+    assert not ((spans["first"] == DROPPED) & (spans["count"] == DROPPED)).any()  # every span was written
+    assert info == dict(stored=aneed, needed=aneed, dropped_reads=0) and anchors.size == aneed
+    for r, e in enumerate(aexp):
+        f, k = int(spans["first"][r]), int(spans["count"][r])
+        assert k == (len(e.runs) if e else 0), r
+        if e:
+            assert f + k <= aneed, r
+            assert [tuple(int(v) for v in a) for a in anchors[f:f + k].tolist()] == A.as32(e.runs), r
+
+
+def test_both_reservations_through_the_host_driven_redo(mq, over):
+    """anchors and chains on one context, the overflow reads redone through the host: one list of read numbers places the redo's spans of
+    both kinds"""
+    fx = over
+    c = fx["ix"].context()
+    _both_reserving(c, fx)
+    hits = c.map_batch(fx["bases"], fx["offs"])
+    assert hits.tobytes() == fx["want"].tobytes()
+    assert not _check(c.chains(), fx["exp"], fx["need"], hits)
+    _check_anchors(c.anchors(), fx["aexp"], fx["aneed"])
+    c.close()
+
+
+@pytest.mark.parametrize("arena_first", [False, True])
+def test_both_reservations_through_the_in_stream_redo(mq, over, arena_first):
+    """... and redone in stream: the arena's slot-to-read array is the id map of both outputs.  arena_first as in
+    test_in_stream_redo_delivers_chains"""
+    fx = over
+    bases, offs = fx["bases"], fx["offs"]
+    n = offs.size - 1
+    db, do, dout = hipmem.DevBuf.from_numpy(bases), hipmem.DevBuf.from_numpy(offs), hipmem.DevBuf(n * 48)
+    c = fx["ix"].context()
+    if arena_first:
+        c.reserve_redo(n + 7, int(fx["lens"].max()))
+    _both_reserving(c, fx)
+    if not arena_first:
+        c.reserve_redo(n + 7, int(fx["lens"].max()))
+    c.map_batch_device(db.ptr, do.ptr, n, int(offs[-1]), dout.ptr)
+    got = c.chains()
+    hits = dout.to_numpy(mq.hit_dtype, n)
+    assert hits.tobytes() == fx["want"].tobytes()
+    assert c.redo_counts() == (fx["n_over"], 0)
+    assert not _check(got, fx["exp"], fx["need"], hits)
+    _check_anchors(c.anchors(), fx["aexp"], fx["aneed"])
     c.close()
     for b in (db, do, dout):
         b.free()
