@@ -260,6 +260,32 @@ int mq_index_reopen(mq_index *idx);
 int mq_index_resize(mq_index *idx, uint64_t table_slots, uint32_t slots_per_kminmer);
 mq_index *mq_index_load_sized(const char *path, int device, uint64_t table_slots, uint32_t slots_per_kminmer);
 mq_index *mq_index_clone_sized(const mq_index *src, int device, uint64_t table_slots, uint32_t slots_per_kminmer);
+/* Another finished index taken in.  Merging src into dst with source reference id i becoming id_base + i ends exactly where one
+ * mq_index_new + mq_index_add_ref of all of dst's references (under their ids) and all of src's (under the moved ids) +
+ * mq_index_finalize ends: the same key set; the same live set (a key live in both turns dead, a key dead in either is dead); for every
+ * live key the same payload with the id moved; n_kminmers = the sum, n_keys = the distinct keys, n_unique = the live keys; the same
+ * reference names and lengths.  A dead key's payload is unspecified, as everywhere.  The argument is the one of the extension above: an
+ * occupied slot re-inserted as (key, first payload, once / more than once) is all another table needs.
+ *   mq_index_merge(dst, src, id_base)        both finalized, dst != src.  On one device the source table is streamed straight into dst's
+ *                            table; across devices the occupied slots are packed on src's device and 32 bytes per key cross the link
+ *                            (as mq_index_clone_sized sends them).  src is only read.
+ *   mq_index_merge_file(dst, path, id_base)  the same from a file mq_index_save wrote: its slots are streamed in bounded chunks through a
+ *                            device buffer; the file's own table is never allocated.  Before the first insert one pass over the file's
+ *                            slots applies mq_index_load's per-slot checks (a count of 0, a key 0 outside its slot, is_key0 > 1, an id the
+ *                            file's reference table does not have) and holds the live slots against the header's n_unique.  One
+ *                            corruption is out of a merge's reach: the same key in two slots of the file, which mq_index_load catches by
+ *                            recounting an otherwise empty table -- such a file behaves as if the key had been inserted twice.
+ * Both wait for the device first (as mq_index_reopen and mq_index_resize do) and answer MQ_ESTATE when dst or src is not finalized or
+ * a context of dst has a submitted batch that was not waited for.  Refused with MQ_EINVAL, dst untouched and usable: seeding parameters
+ * that differ (k, l, density, use_hpc, the seeding-variant bits, MQ_FLAG_FAST_KH; mq_last_error names both sets -- c, s, g and the case
+ * folding stay dst's); a moved id that reaches 2^24 or is already an id of dst; dst == src; everything mq_index_load refuses.
+ * The table grows first (mq_index_resize's route; peak memory: both tables) when the summed n_kminmers ask for a larger one at the
+ * index's table factor (mq_index_finalize's rule for a reopened index), and never shrinks.  A failure up to there (no memory for the
+ * larger table or the chunk buffer) leaves dst finalized and usable; one behind the first insert launch has changed the only table there
+ * is, and dst answers MQ_ESTATE to everything but mq_index_free.  Afterwards dst is finalized, its contexts stay valid, and
+ * mq_index_save of it is loadable. */
+int mq_index_merge(mq_index *dst, const mq_index *src, uint32_t id_base);
+int mq_index_merge_file(mq_index *dst, const char *path, uint32_t id_base);
 int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len);
 /* The parameters an index was built with (a loaded file's k, l, density, use_hpc and seeding variant decide its keys), and the ones that
  * act at mapping time only -- Params.c / .s (Chain::get_match, src/chain.rs:147-169), .g (the gap tests, src/chain.rs:132-142) and the

@@ -52,7 +52,8 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_ctx_reserve_redo", "mq_ctx_redo_counts", "mq_map_reserve_redo", "mq_map_redo_counts",
            "mq_ctx_reserve_anchors", "mq_ctx_anchors", "mq_ctx_anchors_device", "mq_map_reserve_anchors", "mq_map_anchors",
            "mq_ctx_reserve_chains", "mq_ctx_chains", "mq_ctx_chains_device", "mq_map_reserve_chains", "mq_map_chains", "mq_format_paf_chain",
-           "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized"]
+           "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized",
+           "mq_index_merge", "mq_index_merge_file"]
 
 
 class MapquikError(RuntimeError):
@@ -206,6 +207,9 @@ def load_library(path=None):
         L.mq_index_load_sized.argtypes = [C.c_char_p, C.c_int, u64, u32]
         L.mq_index_clone_sized.restype = vp
         L.mq_index_clone_sized.argtypes = [vp, C.c_int, u64, u32]
+    if hasattr(L, "mq_index_merge"):
+        L.mq_index_merge.argtypes = [vp, vp, u32]
+        L.mq_index_merge_file.argtypes = [vp, C.c_char_p, u32]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -328,6 +332,31 @@ class Index:
         a build of this index's k-min-mers gets at `factor` slots each (2..64).  At most one of the two; neither: nothing happens."""
         if self._L.mq_index_resize(self._h, int(table_slots), int(factor)) != 0:
             raise _err(self._L, "mq_index_resize")
+
+    def next_ref_id(self):
+        """the smallest id behind every reference id the index has (--add-reference's rule: ids continue behind the largest)"""
+        n, seen, rid = self.stats()["n_refs"], 0, 0
+        name, ln = C.c_char_p(), C.c_uint64()
+        while seen < n:
+            if self._L.mq_index_ref_info(self._h, rid, C.byref(name), C.byref(ln)) == 0:
+                seen += 1
+            rid += 1
+        return rid
+
+    def merge(self, other, id_base=None):
+        """Another finalized index merged into this one (mq_index_merge): `other`'s reference id i becomes id_base + i (None: this index's
+        largest id + 1), and this index ends where one build of both reference sets ends.  Returns the id_base used."""
+        base = self.next_ref_id() if id_base is None else int(id_base)
+        if self._L.mq_index_merge(self._h, other.handle, base) != 0:
+            raise _err(self._L, "mq_index_merge")
+        return base
+
+    def merge_file(self, path, id_base=None):
+        """Index.merge from a file written by Index.save (mq_index_merge_file): its slots are streamed into this index's table."""
+        base = self.next_ref_id() if id_base is None else int(id_base)
+        if self._L.mq_index_merge_file(self._h, os.fsencode(path), base) != 0:
+            raise _err(self._L, "mq_index_merge_file")
+        return base
 
     def close(self):
         if getattr(self, "_h", None):

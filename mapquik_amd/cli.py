@@ -106,6 +106,9 @@ def build_parser():
     ap.add_argument("--add-reference", dest="add_reference", help="with --index: add this FASTA's records to the loaded index (ids continue behind "
                     "its largest id), then map; --save-index writes the extended index.  The table grows, when it has to, by --table-factor "
                     "(default: the library's 8, whatever factor the file was saved at) (extension)")
+    ap.add_argument("--merge-index", dest="merge_index", action="append", default=[], metavar="FILE",
+                    help="merge this saved index into the one --index / --reference / --add-reference produced (same seeding parameters; ids continue "
+                         "behind its largest id); repeatable, applied in command-line order; --save-index then writes the merged index (extension)")
     ap.add_argument("--table-factor", type=int, dest="table_factor", help="index table slots per k-min-mer, 2..64 (library default 8); with --index "
                     "the loaded table gets that size (extension)")
     ap.add_argument("--seeding-variant", type=int, default=0, dest="seeding_variant",
@@ -201,13 +204,15 @@ def main(argv=None):
         ap.error("--add-reference adds to the index given with --index (and excludes --reference)")  # exit status 2
     if opt.table_factor is not None and not 2 <= opt.table_factor <= 64:
         ap.error("--table-factor wants 2..64")
+    if opt.merge_index and not opt.load_index and not opt.reference:
+        ap.error("--merge-index merges into the index given with --index or built from --reference")
     if opt.add_reference:
         opt.reference = opt.add_reference  # from here on the file is this run's reference file
     if not opt.reads:
         raise SystemExit("Please specify an input file.")
     if not opt.reference and not opt.load_index:
         raise SystemExit("Please specify a reference file.")
-    if opt.load_index and opt.save_index and not opt.add_reference:
+    if opt.load_index and opt.save_index and not opt.add_reference and not opt.merge_index:
         raise SystemExit("error: --index cannot be combined with --save-index (unless --add-reference extends it)")
     lines, st = banner_lines(opt)
     for ln in lines:
@@ -256,10 +261,16 @@ def main(argv=None):
             n = index.add_ref(ref_idx, name, np.frombuffer(seq, dtype=np.uint8))
             print("Indexed reference %s: %d k-min-mers." % (name, n))  # src/closures.rs:58
         unique = index.finalize()
-        if opt.save_index:
-            ts = time.time()
-            index.save(opt.save_index)
-            print("Saved index to %s in %s." % (opt.save_index, rust_duration(time.time() - ts)))
+    for path in opt.merge_index:  # in command-line order, each file's ids behind every id the index has by then
+        before = index.stats()
+        index.merge_file(path)
+        ist = index.stats()
+        print("Merged index %s: %d references, %d k-min-mers." % (path, ist["n_refs"] - before["n_refs"], ist["n_kminmers"] - before["n_kminmers"]))
+        unique = ist["n_unique"]
+    if opt.save_index:
+        ts = time.time()
+        index.save(opt.save_index)
+        print("Saved index to %s in %s." % (opt.save_index, rust_duration(time.time() - ts)))
     print("Indexed %d unique k-min-mers in %s." % (unique, rust_duration(time.time() - t0)))  # src/closures.rs:92
 
     t0 = time.time()

@@ -124,6 +124,21 @@ class ReadOnlyIndex {
     void save(const std::string &path) const {
         if (mq_index_save(h_, path.c_str()) != MQ_OK) throw Error("ReadOnlyIndex::save: " + last_error());
     }
+    // a saved index merged into this one (mq_index_merge_file), its reference ids behind every id this index has; returns what it brought
+    struct Merged {
+        uint64_t refs, kminmers;
+    };
+    Merged merge_file(const std::string &path) {
+        mq_index_stats a, b;
+        mq_index_get_stats(h_, &a);
+        uint32_t next = 0;
+        for (uint64_t seen = 0; seen < a.n_refs; ++next)
+            if (mq_index_ref_info(h_, next, nullptr, nullptr) == MQ_OK) ++seen;
+        if (mq_index_merge_file(h_, path.c_str(), next) != MQ_OK) throw Error("ReadOnlyIndex::merge_file: " + last_error());
+        mq_index_get_stats(h_, &b);
+        unique_ = b.n_unique;
+        return Merged{b.n_refs - a.n_refs, b.n_kminmers - a.n_kminmers};
+    }
 
   private:
     friend class Index;

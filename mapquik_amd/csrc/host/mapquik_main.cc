@@ -124,6 +124,7 @@ struct Opt {
     int table_factor = 2;  // table slots per inserted k-min-mer: this driver is bound by its host side (mq_index_set_table_factor)
     bool table_factor_given = false;  // --table-factor on the command line: only then is a loaded index's table given another size
     std::string add_reference;  // --add-reference (with --index): a FASTA whose records are added to the loaded index; `reference` holds it too, so it takes the routes of --reference
+    std::vector<std::string> merge_index;  // --merge-index, repeatable: saved indexes merged, in this order, into the finalized index of this run (mq_index_merge_file)
     std::string save_index, load_index;  // --save-index / --index: the on-disk index (the reference has none and re-indexes on every run)
     std::string second;  // "k2,l2,d2"
     long k2 = 0, l2 = 0;
@@ -140,7 +141,7 @@ static void usage() {
          "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -629,6 +630,12 @@ static void finalise_save_clone(const Opt &o, const Devices &dev, std::unique_pt
         tl("into_read_only returned (table allocated, k-min-mers inserted)");
         building.reset();
     }
+    // --merge-index: before the index is saved and before the replicas are made
+    for (const std::string &path : o.merge_index) {
+        const ReadOnlyIndex::Merged m = ro[0]->merge_file(path);
+        printf("Merged index %s: %llu references, %llu k-min-mers.\n", path.c_str(), (unsigned long long)m.refs, (unsigned long long)m.kminmers);
+        tl("index file merged");
+    }
     if (!o.save_index.empty()) {
         const auto ts = Clock::now();
         ro[0]->save(o.save_index);
@@ -798,6 +805,7 @@ int main(int argc, char **argv) {
         else if (a == "--save-index") o.save_index = val();
         else if (a == "--index") o.load_index = val();
         else if (a == "--add-reference") o.add_reference = val();
+        else if (a == "--merge-index") o.merge_index.push_back(val());
         else if (a == "--seeding-variant") {
             o.seeding_variant = atoi(val());
             if (o.seeding_variant < 0 || o.seeding_variant > 63) { fprintf(stderr, "error: --seeding-variant wants 0..63 (bits 1 2 4 8 16 32)\n"); return 2; }
@@ -818,10 +826,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "error: --add-reference adds to the index given with --index (and excludes --reference)\n");
         return 2;
     }
+    if (!o.merge_index.empty() && o.load_index.empty() && o.reference.empty() && o.add_reference.empty()) {
+        fprintf(stderr, "error: --merge-index merges into the index given with --index or built from --reference\n");
+        return 2;
+    }
     if (!o.add_reference.empty()) o.reference = o.add_reference;  // from here on the file is this run's reference file: same routes, same log lines
     if (o.reads.empty()) { fprintf(stderr, "Please specify an input file.\n"); return 101; }          // panic!, src/main.rs:191
     if (o.reference.empty() && o.load_index.empty()) { fprintf(stderr, "Please specify a reference file.\n"); return 101; }   // src/main.rs:192
-    if (!o.load_index.empty() && ((!o.save_index.empty() && o.add_reference.empty()) || !o.second.empty())) {
+    if (!o.load_index.empty() && ((!o.save_index.empty() && o.add_reference.empty() && o.merge_index.empty()) || !o.second.empty())) {
         fprintf(stderr, "error: --index cannot be combined with --save-index (unless --add-reference extends it) or --second-pass (a second pass builds its own index)\n");
         return 2;
     }

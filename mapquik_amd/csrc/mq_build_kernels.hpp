@@ -373,6 +373,124 @@ __global__ __launch_bounds__(256) void retable_kernel(const Bucket *__restrict__
     flush_insert_counts(n_claimed, n_dead, acc);
 }
 
+// mq_index_merge / mq_index_merge_file: the occupied slots of ANOTHER finalized index into a table that is already populated, the source's
+// reference ids moved by id_base.  table_insert does not care in which order, or in how many launches, the insertions of all references
+// arrive ("Extension is exact"), and an occupied slot re-inserted as (key, first payload, once / more than once) is
+// all another table needs: a key of both tables claims nothing and gets ENTRY_DUP, a key that is dead in the source arrives with
+// times = 2 and kills the destination's, a new key claims its slot with the moved id.  A dead key's payload stays whichever insertion
+// claimed the slot.  The key 0 goes from the source's extra bucket (or its is_key0 slot) to the destination's through table_insert.
+// The kernels count what the host needs to bring n_keys and n_unique up to date without a pass over the table, per lane, then one
+// wave reduction and one atomic per counter (the shape of flush_insert_counts).  acc: [0] keys newly claimed, [1] of those, the ones that
+// arrived dead (times >= 2 or end == 0), [2] every key that turned dead, as table_insert counts them: the [1] born dead and the
+// destination's keys that were live -- so live-and-turned-dead = [2] - [1], n_keys += [0], n_unique += [0] - [2].  (table_insert's
+// own two counters do not tell a key born dead from one turned dead; the third is kept here, so insert_kernel, retable_kernel and
+// unpack_slots_kernel are as built.)
+struct MergeCounts {
+    uint32_t claimed = 0, born_dead = 0, dead = 0;
+};
+__device__ __forceinline__ void merge_insert(Bucket *__restrict__ table, uint64_t mask, unsigned long long key, Entry e, uint32_t times, uint32_t id_base, MergeCounts &c) {
+    e.id_rc = (((e.id_rc >> 1) + id_base) << 1) | (e.id_rc & 1u);  // (ENTRY_DUP has been taken out by the caller: it travels as `times`)
+    const uint32_t before = c.claimed;
+    table_insert(table, mask, key, e, times, c.claimed, c.dead);
+    if (c.claimed != before && (times > 1u || e.end == 0u)) c.born_dead++;
+}
+__device__ __forceinline__ void flush_merge_counts(const MergeCounts &c, unsigned long long *__restrict__ acc) {
+    const uint32_t a = wave_sum_u32(c.claimed), b = wave_sum_u32(c.born_dead), d = wave_sum_u32(c.dead);
+    if (lane_id() == 0) {
+        if (a) atomicAdd(&acc[0], (unsigned long long)a);
+        if (b) atomicAdd(&acc[1], (unsigned long long)b);
+        if (d) atomicAdd(&acc[2], (unsigned long long)d);
+    }
+}
+
+// Table to table (both on one device): retable_kernel's source side -- a lane pair per 64-byte bucket, the loads of RETABLE_AHEAD slots,
+// 64 slots apart, issued before the first of them is inserted -- in front of merge_insert.  The destination is populated, so an insert
+// walks further than retable_kernel's into a zeroed table of the same size; the stream in is the same.
+__global__ __launch_bounds__(256) void merge_table_kernel(const Bucket *__restrict__ src, uint64_t n_buckets_plus1, Bucket *__restrict__ dst, uint64_t dst_mask,
+                                                          uint32_t id_base, unsigned long long *__restrict__ acc) {
+    MergeCounts cnt;
+    const uint64_t n = 2 * n_buckets_plus1;  // slots of the source, the extra bucket's two included (>= 4)
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x * RETABLE_AHEAD;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) * RETABLE_AHEAD + (threadIdx.x & 63u); i0 < n; i0 += step) {
+        uint4 kk[RETABLE_AHEAD];
+        Entry e[RETABLE_AHEAD];
+        uint32_t claims[RETABLE_AHEAD];
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {  // (a slot past the end reads the last one again: no branch around a load)
+            const uint64_t i = i0 + 64u * u < n ? i0 + 64u * u : n - 1;
+            const Bucket &B = src[i >> 1];
+            kk[u] = ld_u4(B.key);
+            e[u] = B.pay[i & 1u];
+            claims[u] = B.claims;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {
+            const uint64_t i = i0 + 64u * u;
+            const uint32_t w = (uint32_t)i & 1u;
+            const bool extra = (i >> 1) == n_buckets_plus1 - 1;
+            const unsigned long long key = extra ? 0ull : w ? u64_of(kk[u].z, kk[u].w) : u64_of(kk[u].x, kk[u].y);
+            const bool occupied = i < n && (extra ? (w == 0 && claims[u] != 0) : key != 0);
+            if (occupied) {
+                Entry x = e[u];
+                const uint32_t times = (x.id_rc & ENTRY_DUP) ? 2u : 1u;
+                x.id_rc &= ~ENTRY_DUP;
+                merge_insert(dst, dst_mask, key, x, times, id_base, cnt);
+            }
+        }
+    }
+    flush_merge_counts(cnt, acc);
+}
+
+// The same from an array of saved slots (a chunk of an index file; the packed slots of a source on another device): consecutive lanes
+// take consecutive 32-byte slots, RETABLE_AHEAD of them loaded before the first is inserted.  The slots have been checked
+// (merge_check_slots_kernel for a file; pack_slots_kernel wrote the others): count >= 1, key 0 <=> is_key0 == 1, ids the source has.
+__global__ __launch_bounds__(256) void merge_slots_kernel(const SavedSlot *__restrict__ in, uint64_t n, Bucket *__restrict__ dst, uint64_t dst_mask, uint32_t id_base,
+                                                          unsigned long long *__restrict__ acc) {
+    MergeCounts cnt;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x * RETABLE_AHEAD;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) * RETABLE_AHEAD + (threadIdx.x & 63u); i0 < n; i0 += step) {
+        uint4 lo[RETABLE_AHEAD], hi[RETABLE_AHEAD];
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {  // (n >= 1 here; a slot past the end reads the last one again)
+            const uint64_t i = i0 + 64u * u < n ? i0 + 64u * u : n - 1;
+            lo[u] = ld_u4(&in[i].e);
+            hi[u] = ld_u4(&in[i].key);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < RETABLE_AHEAD; ++u) {
+            if (i0 + 64u * u < n) {
+                Entry x;
+                x.start = lo[u].x;
+                x.end = lo[u].y;
+                x.offset = lo[u].z;
+                x.id_rc = lo[u].w & ~ENTRY_DUP;
+                merge_insert(dst, dst_mask, u64_of(hi[u].x, hi[u].y), x, hi[u].z /* count */, id_base, cnt);
+            }
+        }
+    }
+    flush_merge_counts(cnt, acc);
+}
+
+// mq_index_merge_file, in front of the first insert: unpack_slots_kernel's per-slot refusals (a count of 0, a key 0 outside its slot or
+// an is_key0 slot with another key, is_key0 > 1, a reference id beyond the file's largest or in a hole of its reference table --
+// ref_lens is the FILE's dense length array) without a table.  flags: [0] set for a slot that fails, [1] the slots that would be live
+// (count 1 and end != 0), which the caller holds against the header's n_unique.
+__global__ void merge_check_slots_kernel(const SavedSlot *__restrict__ in, uint64_t n, uint32_t max_id, const uint64_t *__restrict__ ref_lens,
+                                         unsigned long long *__restrict__ flags) {
+    uint32_t live = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const SavedSlot v = in[i];
+        const uint32_t id = v.e.id_rc >> 1;
+        if (v.count == 0 || id > max_id || ref_lens[id] == 0 || (v.is_key0 != 0) != (v.key == 0) || v.is_key0 > 1u) {
+            atomicOr(&flags[0], 1ull);
+            continue;
+        }
+        if (v.count == 1u && v.e.end != 0u) live++;
+    }
+    live = wave_sum_u32(live);
+    if (lane_id() == 0 && live) atomicAdd(&flags[1], (unsigned long long)live);
+}
+
 __global__ void lookup_kernel(const Bucket *__restrict__ table, uint64_t mask, const uint64_t *__restrict__ keys, uint32_t n,
                               uint8_t *__restrict__ found, mq_kminmer *__restrict__ entries, uint32_t *__restrict__ ref_ids) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

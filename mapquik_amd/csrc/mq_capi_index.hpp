@@ -71,11 +71,14 @@ void mq_index_free(mq_index *idx) { delete idx; }
 // A reopened index whose finalize failed after its first insert launch: the table holds some of the new keys, the counts none of them,
 // and inserting the chunks again would turn every new live key dead.  (A fresh build's retry gets a new table; an extension has none.)
 static const char *const EXTEND_FAILED = "a finalize of this reopened index failed part way: the table is no longer exact, free the index";
+// The same for a merge (mq_index_merge*, mq_capi_index_io.hpp) that failed behind its first insert launch: the only table there is has changed.
+static const char *const MERGE_FAILED = "a merge into this index failed part way: the table is no longer exact, free the index";
+static int extend_failed_err(const mq_index *idx) { return set_err(MQ_ESTATE, idx->merge_failed ? MERGE_FAILED : EXTEND_FAILED); }
 
 // what every mq_index_add_ref* refuses before anything is registered or overwritten
 static int check_new_ref(const mq_index *idx, uint32_t ref_id, uint64_t len) {
     if (idx->finalized) return set_err(MQ_ESTATE, "index already finalized");
-    if (idx->extend_failed) return set_err(MQ_ESTATE, EXTEND_FAILED);
+    if (idx->extend_failed) return extend_failed_err(idx);
     if (len >= (1ull << 32)) return set_err(MQ_EINVAL, "sequence length must be < 2^32");
     if (ref_id >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, "ref_id must be < 2^24 (reference lengths are kept in a dense device array)");
     if (idx->refs.count(ref_id)) return set_err(MQ_EINVAL, "duplicate ref_id");
@@ -384,7 +387,7 @@ int64_t mq_index_finalize(mq_index *idx) {
         if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
         std::lock_guard<std::mutex> lk(idx->mu);
         if (idx->finalized) return (int64_t)idx->n_unique;
-        if (idx->extend_failed) return set_err(MQ_ESTATE, EXTEND_FAILED);
+        if (idx->extend_failed) return extend_failed_err(idx);
         int rc = use_device(idx);
         if (rc) return rc;
         const bool timing = env_set("MQ_BUILD_TIMING");  // diagnostic: where the wall time of finalize goes (stderr)

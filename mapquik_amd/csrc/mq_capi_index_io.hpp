@@ -200,6 +200,191 @@ static mq_index *load_index(const char *path, int device, uint64_t table_slots, 
     });
 }
 
+// ---- mq_index_merge / mq_index_merge_file: another finalized index into this one (merge_table_kernel, merge_slots_kernel).
+// What both routes share: the refusals that leave dst as it was, the growth, the counters, the bookkeeping afterwards.
+
+static std::string shortest_double(double v) {
+    char b[64];
+    for (int prec = 1; prec <= 17; ++prec) {
+        snprintf(b, sizeof(b), "%.*g", prec, v);
+        if (strtod(b, nullptr) == v) break;
+    }
+    return b;
+}
+static std::string seeding_text(const mq_params &p) {
+    char b[256];
+    snprintf(b, sizeof(b), "-k %u -l %u -d %s%s --seeding-variant %u%s", p.k, p.l, shortest_double(p.density).c_str(), p.use_hpc ? "" : " --nohpc",
+             (p.flags & MQ_FLAG_SEED_VARIANT_MASK) >> MQ_FLAG_SEED_VARIANT_SHIFT, (p.flags & MQ_FLAG_FAST_KH) ? " --fast-kh" : "");
+    return b;
+}
+// the parameters that decide an index's keys; c, s, g and the case folding act at mapping time and stay dst's
+static int merge_check_params(const char *who, const mq_params &d, const mq_params &s, const std::string &what) {
+    const uint32_t seeding = MQ_FLAG_SEED_VARIANT_MASK | MQ_FLAG_FAST_KH;
+    if (d.k == s.k && d.l == s.l && d.density == s.density && (d.use_hpc != 0) == (s.use_hpc != 0) && (d.flags & seeding) == (s.flags & seeding)) return MQ_OK;
+    return set_err(MQ_EINVAL, std::string(who) + ": " + what + " was built with " + seeding_text(s) + ": indexes merge under the same seeding parameters (this index: " +
+                                  seeding_text(d) + ")");
+}
+// a moved id must stay below 2^24 and must not be an id dst has
+static int merge_check_ids(const char *who, const mq_index *dst, const std::map<uint32_t, std::pair<std::string, uint64_t>> &src_refs, uint32_t id_base) {
+    for (auto &kv : src_refs) {
+        const uint64_t moved = (uint64_t)kv.first + id_base;
+        if (moved >= MQ_MAX_REF_ID) return set_err(MQ_EINVAL, std::string(who) + ": reference id " + std::to_string(kv.first) + " + id_base reaches 2^24");
+        if (dst->refs.count((uint32_t)moved)) return set_err(MQ_EINVAL, std::string(who) + ": reference id " + std::to_string(moved) + " (moved) is already an id of this index");
+    }
+    return MQ_OK;
+}
+static int merge_check_dst(const char *who, const mq_index *dst) {
+    if (dst->extend_failed) return extend_failed_err(dst);
+    if (!dst->finalized) return set_err(MQ_ESTATE, std::string(who) + ": index not finalized");
+    bool busy = dst->def_ctx && (dst->def_ctx->pending || dst->def_ctx->fx_kind != FxKind::None);
+    {
+        std::lock_guard<std::mutex> lk(const_cast<mq_index *>(dst)->ctx_mu);
+        for (const mq_ctx *c : dst->ctxs) busy = busy || c->pending || c->fx_kind != FxKind::None;
+    }
+    if (busy) return set_err(MQ_ESTATE, std::string(who) + ": a context of this index has a submitted batch: wait for it first");
+    return MQ_OK;
+}
+// The table grown, if the summed k-min-mers ask for it at the index's factor (finalize's rule for a reopened index: never smaller), and
+// in any case so that an empty slot remains whatever the two key sets share.  Until here a failure leaves dst as it was.
+static int merge_grow(const char *who, mq_index *dst, uint64_t src_kmm, uint64_t src_keys) {
+    uint64_t nslots = std::max(table_slots_for(dst, dst->n_kmm_total + src_kmm), dst->nslots);
+    while (nslots <= dst->n_keys + src_keys && nslots <= MQ_MAX_TABLE_SLOTS) nslots <<= 1;
+    if (nslots > MQ_MAX_TABLE_SLOTS) return set_err(MQ_EINVAL, std::string(who) + ": the merged table would pass 2^40 slots");
+    return nslots > dst->nslots ? retable(dst, nslots) : MQ_OK;
+}
+// from the first insert launch on the only table there is has changed: a failure leaves an index that can only be freed
+static int merge_fail(mq_index *dst, int rc) {
+    dst->finalized = false;
+    dst->extend_failed = dst->merge_failed = true;
+    return rc;
+}
+// the counters read back (the wait for the inserts), the index's counts, references and device length array brought up to date
+static int merge_finish(const char *who, mq_index *dst, const Buf<unsigned long long> &d_acc, const std::map<uint32_t, std::pair<std::string, uint64_t>> &src_refs,
+                        uint32_t id_base, uint64_t src_kmm, uint64_t src_keys) {
+    unsigned long long acc[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(acc, d_acc, 24, hipMemcpyDeviceToHost));
+    if (acc[0] > src_keys || acc[1] > acc[0] || acc[1] > acc[2] || acc[2] - acc[1] > dst->n_unique + acc[0])
+        return set_err(MQ_ESTATE, std::string(who) + ": the insert counters disagree with the two indexes' counts (internal error)");
+    dst->n_keys += acc[0];
+    dst->n_unique = dst->n_unique + acc[0] - acc[2];
+    dst->n_kmm_total += src_kmm;
+    for (auto &kv : src_refs) dst->refs[kv.first + id_base] = kv.second;
+    return upload_ref_lens(dst);
+}
+static uint32_t merge_grid(uint64_t n_slots) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_slots + 256 * RETABLE_AHEAD - 1) / (256 * RETABLE_AHEAD), 1u << 16)); }
+
+// index to index; both locked, every refusal behind us.  Same device: table to table.  Another device (or MQ_MERGE_PACKED=1, test hook
+// read here): the occupied slots packed on the source's device, 32 bytes per key over the link, merge_slots_kernel here.
+static int merge_index_locked(mq_index *dst, const mq_index *src, uint32_t id_base) {
+    const char *who = "mq_index_merge";
+    int rc;
+    const bool packed = src->device != dst->device || env_int("MQ_MERGE_PACKED", 0) != 0;
+    const uint64_t n = src->n_keys;
+    Buf<SavedSlot> d_in;  // (on dst's device)
+    if (packed) {
+        Buf<SavedSlot> d_pack;
+        if ((rc = use_device(src))) return rc;
+        HIPCHK(hipDeviceSynchronize());
+        if ((rc = pack_table(src, who, d_pack))) return rc;
+        if ((rc = use_device(dst)) || (rc = d_in.alloc(n + 1))) return rc;
+        if (n) HIPCHK(hipMemcpyPeer(d_in, dst->device, d_pack, src->device, n * sizeof(SavedSlot)));
+        if ((rc = use_device(src))) return rc;
+        d_pack.reset();
+    }
+    if ((rc = use_device(dst))) return rc;
+    HIPCHK(hipDeviceSynchronize());  // launches queued on the contexts read the table that is about to change
+    if ((rc = merge_grow(who, dst, src->n_kmm_total, n))) return rc;
+    Buf<unsigned long long> d_acc;
+    if ((rc = d_acc.alloc(3))) return rc;
+    HIPCHK(hipMemset(d_acc, 0, 24));
+    if (packed) {
+        if (n) rc = launch(merge_slots_kernel, merge_grid(n), 256, 0, (const SavedSlot *)d_in.p, n, dst->table, dst->nslots - 1, id_base, d_acc);
+    } else {
+        const uint64_t nb1 = src->nslots / 2 + 1;
+        rc = launch(merge_table_kernel, merge_grid(2 * nb1), 256, 0, src->table, nb1, dst->table, dst->nslots - 1, id_base, d_acc);
+    }
+    if (rc || (rc = merge_finish(who, dst, d_acc, src->refs, id_base, src->n_kmm_total, n))) return merge_fail(dst, rc);
+    return MQ_OK;
+}
+
+// A file's slots, chunk by chunk, through one page-locked buffer and one device buffer (IX_IO_CHUNK bytes at most): f(device slots, count)
+// per chunk, on the null stream, waited for before the buffers are used again.
+template <class F>
+static int for_file_slots(int fd, off_t slots_at, size_t total, uint8_t *hb, Buf<uint8_t> &d, const char *path, F f) {
+    for (size_t o = 0; o < total; o += IX_IO_CHUNK) {
+        const size_t n = std::min(IX_IO_CHUNK, total - o);
+        size_t got = 0;
+        while (got < n) {
+            const ssize_t r = ::pread(fd, hb + got, n - got, slots_at + (off_t)(o + got));
+            if (r <= 0) return set_err(MQ_EINVAL, std::string(IX_TRUNCATED) + path);
+            got += (size_t)r;
+        }
+        HIPCHK(hipMemcpy(d, hb, n, hipMemcpyHostToDevice));
+        int rc = f((const SavedSlot *)d.p, (uint64_t)(n / sizeof(SavedSlot)));
+        if (rc) return rc;
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return MQ_OK;
+}
+
+static int merge_file_locked(mq_index *dst, const char *path, uint32_t id_base) {
+    const char *who = "mq_index_merge_file";
+    auto refuse = [&](const char *why) { return set_err(MQ_EINVAL, std::string(who) + ": " + why + path); };
+    ScopedFd fd(::open(path, O_RDONLY));
+    if (fd < 0) return set_err(MQ_EINVAL, std::string(who) + ": cannot open: " + path);
+    IxHeader h;
+    const char *why = read_header(fd, &h);
+    if (why) return refuse(why);
+    int rc = check_params(&h.p);
+    if (rc) return rc;
+    if ((rc = merge_check_params(who, dst->params, h.p, path))) return rc;
+    mq_index file_side;  // (a holder for the loader's read_refs: no device state)
+    file_side.device = dst->device;
+    if ((why = read_refs(fd, h.w[IX_N_REFS], &file_side))) return refuse(why);
+    if ((rc = merge_check_ids(who, dst, file_side.refs, id_base))) return rc;
+    const uint64_t n = h.w[IX_N_KEYS];
+    const size_t total = (size_t)n * sizeof(SavedSlot);
+    const off_t slots_at = ::lseek(fd, 0, SEEK_CUR);
+    struct stat sb;
+    if (slots_at < 0 || ::fstat(fd, &sb) != 0 || (uint64_t)sb.st_size < (uint64_t)slots_at + total) return refuse(IX_TRUNCATED);
+    if ((uint64_t)sb.st_size > (uint64_t)slots_at + total) return refuse("corrupt index file (bytes after the last slot): ");
+    if ((rc = use_device(dst))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    // pass 1: the loader's per-slot checks over every slot of the file, against the FILE's reference table, before the first insert
+    PinnedBuf<uint8_t> hb;
+    Buf<uint8_t> d;
+    Buf<uint64_t> d_flens;
+    Buf<unsigned long long> d_flags, d_acc;
+    const uint32_t f_max_id = max_ref_id(&file_side);
+    if (total) {
+        std::vector<uint64_t> lens((size_t)f_max_id + 1, 0);
+        for (auto &kv : file_side.refs) lens[kv.first] = kv.second.second;
+        if ((rc = hb.alloc(std::min(total, IX_IO_CHUNK))) || (rc = d.alloc(std::min(total, IX_IO_CHUNK))) || (rc = d_flens.alloc(lens.size())) || (rc = d_flags.alloc(2))) return rc;
+        HIPCHK(hipMemcpy(d_flens, lens.data(), lens.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_flags, 0, 16));
+        if ((rc = for_file_slots(fd, slots_at, total, hb, d, path, [&](const SavedSlot *s, uint64_t ns) {
+                 return launch(merge_check_slots_kernel, (uint32_t)std::min<uint64_t>((ns + 255) / 256, 1u << 16), 256, 0, s, ns, f_max_id, (const uint64_t *)d_flens.p, d_flags);
+             })))
+            return rc;
+        unsigned long long flags[2] = {1, 0};
+        HIPCHK(hipMemcpy(flags, d_flags, 16, hipMemcpyDeviceToHost));
+        if (flags[0]) return refuse("corrupt index file (an entry names a reference the file does not have, or a malformed slot): ");
+        if (flags[1] != h.w[IX_N_UNIQUE]) return refuse("corrupt index file (key counts or reference ids disagree with its header): ");
+    } else if (h.w[IX_N_UNIQUE] != 0) {
+        return refuse("corrupt index file (key counts or reference ids disagree with its header): ");
+    }
+    if ((rc = merge_grow(who, dst, h.w[IX_N_KMM], n))) return rc;
+    if ((rc = d_acc.alloc(3))) return rc;
+    HIPCHK(hipMemset(d_acc, 0, 24));
+    // pass 2: the inserts
+    if (total)
+        rc = for_file_slots(fd, slots_at, total, hb, d, path, [&](const SavedSlot *s, uint64_t ns) {
+            return launch(merge_slots_kernel, merge_grid(ns), 256, 0, s, ns, dst->table, dst->nslots - 1, id_base, d_acc);
+        });
+    if (rc || (rc = merge_finish(who, dst, d_acc, file_side.refs, id_base, h.w[IX_N_KMM], n))) return merge_fail(dst, rc);
+    return MQ_OK;
+}
+
 extern "C" {
 
 int mq_index_save(const mq_index *idx, const char *path) {
@@ -333,6 +518,36 @@ mq_index *mq_index_clone_sized(const mq_index *src, int device, uint64_t table_s
         }
         idx->finalized = true;
         return idx.release();
+    });
+}
+
+// Another finalized index merged into dst, source id i becoming id_base + i: dst ends where one build of both reference sets ends (the
+// header has the contract).  Both indexes are locked, in address order.
+int mq_index_merge(mq_index *dst, const mq_index *src, uint32_t id_base) {
+    return guarded([&]() -> int {
+        if (!dst || !src) return set_err(MQ_EINVAL, "mq_index_merge: dst or src is NULL");
+        if (dst == src) return set_err(MQ_EINVAL, "mq_index_merge: dst and src are the same index");
+        mq_index *s = const_cast<mq_index *>(src);
+        std::mutex &first = dst < s ? dst->mu : s->mu, &second = dst < s ? s->mu : dst->mu;
+        std::lock_guard<std::mutex> lk1(first), lk2(second);
+        int rc = merge_check_dst("mq_index_merge", dst);
+        if (rc) return rc;
+        if (!src->finalized) return set_err(MQ_ESTATE, "mq_index_merge: src is not finalized");
+        if ((rc = merge_check_params("mq_index_merge", dst->params, src->params, "src"))) return rc;
+        if ((rc = merge_check_ids("mq_index_merge", dst, src->refs, id_base))) return rc;
+        return merge_index_locked(dst, src, id_base);
+    });
+}
+
+// The same from a file written by mq_index_save: its slots are streamed through a bounded device buffer into dst's table; the file's own
+// table is never allocated.
+int mq_index_merge_file(mq_index *dst, const char *path, uint32_t id_base) {
+    return guarded([&]() -> int {
+        if (!dst || !path) return set_err(MQ_EINVAL, "mq_index_merge_file: dst or path is NULL");
+        std::lock_guard<std::mutex> lk(dst->mu);
+        int rc = merge_check_dst("mq_index_merge_file", dst);
+        if (rc) return rc;
+        return merge_file_locked(dst, path, id_base);
     });
 }
 

@@ -720,12 +720,22 @@ mq_ctx *mq_ctx_new(mq_index *idx) {
             set_err(MQ_EINVAL, "idx is NULL");
             return nullptr;
         }
-        return ctx_create(idx);
+        mq_ctx *c = ctx_create(idx);
+        if (c) {
+            std::lock_guard<std::mutex> lk(idx->ctx_mu);
+            idx->ctxs.push_back(c);
+        }
+        return c;
     });
 }
 
 void mq_ctx_free(mq_ctx *ctx) {
     if (!ctx) return;
+    {
+        std::lock_guard<std::mutex> lk(ctx->idx->ctx_mu);
+        auto &v = ctx->idx->ctxs;
+        v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
+    }
     hipSetDevice(ctx->idx->device);
     ctx_release(ctx);
 }

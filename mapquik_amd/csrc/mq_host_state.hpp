@@ -357,6 +357,10 @@ struct mq_index {
     bool finalized = false;
     bool extending = false;     // mq_index_reopen: the table holds the keys of an earlier finalize, the next one inserts into it
     bool extend_failed = false; // a finalize of a reopened index failed with part of the new keys in the table: no retry could be exact
+    bool merge_failed = false;  // ... or a merge (mq_index_merge*) did, behind its first insert launch: set with extend_failed, finalized cleared
+    // the contexts mq_ctx_new made on this index (not the default one): mq_index_merge* refuses while one of them has a batch in flight
+    std::mutex ctx_mu;
+    std::vector<mq_ctx *> ctxs;
     uint32_t table_factor = 0;  // mq_index_set_table_factor: slots per inserted k-min-mer (0: the default, 8)
     uint64_t nslots = 0;
     uint64_t n_unique = 0, n_keys = 0;
