@@ -247,6 +247,10 @@ __global__ void insert_kernel(const RefKmm *__restrict__ kmm, uint64_t n, Bucket
     flush_insert_counts(n_claimed, n_dead, acc);
 }
 
+// THE occupied-slot rule of a kernel that walks a table slot by slot: way w of bucket B holds a key iff its key word is not 0; of the extra
+// bucket (the key 0's, behind the table) only way 0 counts, and `claims` says whether the key 0 is there.
+__device__ __forceinline__ bool slot_occupied(const Bucket &B, uint32_t w, bool extra) { return extra ? (w == 0 && B.claims != 0) : B.key[w] != 0; }
+
 // One pass over a finished table (mq_index_load's check of a file against its header; the build counts while it inserts):
 // Index::get_count (src/index.rs:90-92) = live slots, the number of distinct keys, the largest reference id stored.
 // acc: [0] live, [1] keys, [2] max ref id + 1 over occupied slots.
@@ -256,7 +260,7 @@ __global__ void count_kernel(const Bucket *__restrict__ table, uint64_t n_bucket
         const Bucket &B = table[i >> 1];
         const uint32_t w = (uint32_t)i & 1u;
         const bool extra = (i >> 1) == n_buckets_plus1 - 1;
-        const bool occupied = extra ? (w == 0 && B.claims != 0) : B.key[w] != 0;
+        const bool occupied = slot_occupied(B, w, extra);
         if (occupied) {
             keys++;
             const Entry e = B.pay[w];
@@ -292,7 +296,7 @@ __global__ void pack_slots_kernel(const Bucket *__restrict__ table, uint64_t n_b
         const Bucket &B = table[i >> 1];
         const uint32_t w = (uint32_t)i & 1u;
         const bool extra = (i >> 1) == n_buckets_plus1 - 1;
-        const bool occupied = extra ? (w == 0 && B.claims != 0) : B.key[w] != 0;
+        const bool occupied = slot_occupied(B, w, extra);
         if (occupied) {
             const unsigned long long at = atomicAdd(cursor, 1ull);
             if (at < cap) {
@@ -316,6 +320,8 @@ __global__ void unpack_slots_kernel(const SavedSlot *__restrict__ in, uint64_t n
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const SavedSlot v = in[i];
         const uint32_t id = v.e.id_rc >> 1;
+        // (the per-slot refusal stands twice: merge_check_slots_kernel must refuse what this refuses -- change both; a shared predicate cost
+        // that kernel two VGPRs, profiles/NOTES.md 2026-10-21)
         if (v.count == 0 || id > max_id || ref_lens[id] == 0 || (v.is_key0 != 0) != (v.key == 0) || v.is_key0 > 1u) {
             atomicOr(flags, 1u);
             continue;
@@ -481,6 +487,7 @@ __global__ void merge_check_slots_kernel(const SavedSlot *__restrict__ in, uint6
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const SavedSlot v = in[i];
         const uint32_t id = v.e.id_rc >> 1;
+        // (unpack_slots_kernel's refusal, clause for clause: change both)
         if (v.count == 0 || id > max_id || ref_lens[id] == 0 || (v.is_key0 != 0) != (v.key == 0) || v.is_key0 > 1u) {
             atomicOr(&flags[0], 1ull);
             continue;

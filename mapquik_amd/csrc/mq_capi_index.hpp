@@ -1,5 +1,6 @@
 // mq_capi_index.hpp -- C ABI, index side: mq_index_new .. mq_index_finalize (Index::new, ref_extract + add_with_mer, get_count +
-// into_read_only; src/index.rs:78-116, src/mers.rs:15-38) (part of the one translation unit mq_capi.hip).  Every entry point that can
+// into_read_only; src/index.rs:78-116, src/mers.rs:15-38), reopen / resize, and what an index says of itself (statistics, parameters,
+// reference info) and takes for mapping time (mq_index_set_map_params) (part of the one translation unit mq_capi.hip).  Every entry point that can
 // throw runs inside guarded(); what a function allocates for itself is a Buf or a Scoped handle, so every early return gives it back.
 #pragma once
 
@@ -338,8 +339,7 @@ static int retable(mq_index *idx, uint64_t nslots) {
     if ((rc = new_table(table, nslots)) || (rc = d_acc.alloc(2))) return rc;
     HIPCHK(hipMemsetAsync(d_acc, 0, 16, 0));
     const uint64_t nb1 = idx->nslots / 2 + 1;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((2 * nb1 + 256 * RETABLE_AHEAD - 1) / (256 * RETABLE_AHEAD), 1u << 16);
-    if ((rc = launch(retable_kernel, grid, 256, 0, idx->table, nb1, table, nslots - 1, d_acc))) return rc;
+    if ((rc = launch(retable_kernel, ahead_grid(2 * nb1), 256, 0, idx->table, nb1, table, nslots - 1, d_acc))) return rc;
     unsigned long long acc[2] = {0, 0};
     HIPCHK(hipMemcpy(acc, d_acc, 16, hipMemcpyDeviceToHost));
     if (acc[0] != idx->n_keys || acc[0] - acc[1] != idx->n_unique)
@@ -496,6 +496,42 @@ int mq_index_get_stats(const mq_index *idx, mq_index_stats *out) {
         out->table_slots = idx->nslots;
         out->table_bytes = table_bytes_of(idx->nslots);
         out->slot_bytes = SLOT_BYTES;
+        return MQ_OK;
+    });
+}
+
+// The parameters an index was built with (what a loaded file says: k, l, density, use_hpc and the seeding variant decide its keys).
+int mq_index_get_params(const mq_index *idx, mq_params *out) {
+    return guarded([&]() -> int {
+        if (!idx || !out) return set_err(MQ_EINVAL, "bad arguments");
+        *out = idx->params;
+        return MQ_OK;
+    });
+}
+
+// The parameters that act at mapping time only (Params.c / .s in Chain::get_match src/chain.rs:147-169, .g in the gap tests
+// src/chain.rs:132-142, and the feeder's case folding): a loaded index takes the command line's.  Launches queued before the call keep
+// the old values.
+int mq_index_set_map_params(mq_index *idx, uint32_t c, uint32_t s, uint32_t g, int fold_case) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        idx->params.c = c;
+        idx->params.s = s;
+        idx->params.g = g;
+        idx->params.flags = (idx->params.flags & ~MQ_FLAG_FOLD_CASE) | (fold_case ? MQ_FLAG_FOLD_CASE : 0u);
+        set_dev_params(idx, dev_params_from(idx->params, idx->dp.variant));
+        return MQ_OK;
+    });
+}
+
+int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        auto it = idx->refs.find(ref_id);
+        if (it == idx->refs.end()) return set_err(MQ_EINVAL, "unknown ref_id");
+        if (name) *name = it->second.first.c_str();
+        if (len) *len = it->second.second;
         return MQ_OK;
     });
 }

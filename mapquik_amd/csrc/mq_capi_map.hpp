@@ -1,5 +1,5 @@
 // mq_capi_map.hpp -- C ABI, mapping side: launch sequences (the kernel pair of each comes from MAP_KERNELS), stream-slot contexts
-// (mq_ctx_*), host-buffer and device-resident entry points, the overflow redo (through the host, and in stream), the reservation and
+// (mq_ctx_*), host-buffer and device-resident entry points (mq_map_reserve for the default context's), the overflow redo (through the host, and in stream), the reservation and
 // read-back of the pooled outputs (PooledOutput, mq_host_state.hpp: anchors and chains share every line but the chain windows),
 // device-parsed FASTA chunks, PAF formatting, page-locked host memory (part of the one translation unit mq_capi.hip).  Temporary device
 // memory is a Buf: it goes when its function returns, by whichever way.
@@ -786,6 +786,16 @@ int mq_ctx_map_batch_device(mq_ctx *ctx, const uint8_t *d_bases, const uint64_t 
     return guarded([&]() -> int {
         if (!ctx) return set_err(MQ_EINVAL, "ctx is NULL");
         return ctx_map_device(ctx, d_bases, d_offsets, n, total_bases, d_out, (hipStream_t)stream);
+    });
+}
+
+int mq_map_reserve(mq_index *idx, uint32_t n_reads, uint64_t total_bases) {
+    return guarded([&]() -> int {
+        if (!idx) return set_err(MQ_EINVAL, "idx is NULL");
+        std::lock_guard<std::mutex> lk(idx->mu);
+        int rc = use_device(idx);
+        if (rc) return rc;
+        return ctx_ensure(idx->def_ctx.get(), n_reads, total_bases, list_f16(idx));
     });
 }
 

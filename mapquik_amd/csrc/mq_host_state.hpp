@@ -7,6 +7,7 @@
 
 constexpr uint32_t MQ_MAX_REF_ID = 1u << 24;
 struct mq_index;
+using RefMap = std::map<uint32_t, std::pair<std::string, uint64_t>>;  // reference id -> (name, length): ref_map (src/closures.rs:30, 49)
 
 // The MQ_* test and diagnostic hooks.  Each is read where it acts, never cached at mq_index_new: tests change them between calls.
 static bool env_set(const char *name) { return getenv(name) != nullptr; }
@@ -352,7 +353,7 @@ struct mq_index {
     std::once_flag geometry_once;  // launch geometry is worked out once, by whichever context or entry point maps first
     int geometry_rc = MQ_OK;
     std::mutex mu;  // serialises the index-level entry points (add_ref, finalize, and everything that uses the default context)
-    std::map<uint32_t, std::pair<std::string, uint64_t>> refs;
+    RefMap refs;
     uint64_t n_kmm_total = 0;
     bool finalized = false;
     bool extending = false;     // mq_index_reopen: the table holds the keys of an earlier finalize, the next one inserts into it
@@ -524,6 +525,10 @@ static int use_device(const mq_index *idx) {
 
 // workgroups (of 256 threads) of a kernel that walks the table's nb1 buckets, two slots each
 static uint32_t bucket_walk_grid(uint64_t nb1) { return (uint32_t)std::min<uint64_t>((2 * nb1 + 255) / 256, 1u << 16); }
+// ... of a kernel that takes an array of n saved slots one per lane (unpack_slots_kernel, merge_check_slots_kernel; n >= 1)
+static uint32_t slot_array_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
+// ... of a kernel whose lanes load RETABLE_AHEAD of n slots ahead (retable_kernel, merge_table_kernel, merge_slots_kernel; n >= 1)
+static uint32_t ahead_grid(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 256 * RETABLE_AHEAD - 1) / (256 * RETABLE_AHEAD), 1u << 16)); }
 
 // a table of nslots slots, its clearing queued on the null stream: kernels launched there afterwards find it zeroed without a wait
 static int new_table(Buf<Bucket> &table, uint64_t nslots) {
@@ -770,16 +775,22 @@ static mq_ctx *ctx_create(mq_index *idx) {
     return c;
 }
 
-// ref_map lengths (src/closures.rs:49), dense by ref id
-static uint32_t max_ref_id(const mq_index *idx) { return idx->refs.empty() ? 0 : idx->refs.rbegin()->first; }
-static int upload_ref_lens(mq_index *idx) {
-    std::vector<uint64_t> lens((size_t)max_ref_id(idx) + 1, 0);
-    for (auto &kv : idx->refs) lens[kv.first] = kv.second.second;
-    int rc = idx->d_ref_lens.alloc(lens.size());
+// ref_map lengths (src/closures.rs:49), dense by ref id: one length per id up to the largest, 0 for an id the map does not have (a
+// reference of length 0 cannot own a k-min-mer, so a zero marks a hole)
+static uint32_t max_ref_id(const RefMap &refs) { return refs.empty() ? 0 : refs.rbegin()->first; }
+static std::vector<uint64_t> dense_ref_lens(const RefMap &refs) {
+    std::vector<uint64_t> lens((size_t)max_ref_id(refs) + 1, 0);
+    for (auto &kv : refs) lens[kv.first] = kv.second.second;
+    return lens;
+}
+static int upload_ref_lens(const RefMap &refs, Buf<uint64_t> &d_lens) {
+    const std::vector<uint64_t> lens = dense_ref_lens(refs);
+    int rc = d_lens.alloc(lens.size());
     if (rc) return rc;
-    HIPCHK(hipMemcpy(idx->d_ref_lens, lens.data(), lens.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_lens, lens.data(), lens.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     return MQ_OK;
 }
+static int upload_ref_lens(mq_index *idx) { return upload_ref_lens(idx->refs, idx->d_ref_lens); }
 
 static void free_build_scratch(mq_index *idx) {
     idx->stage.reset();
