@@ -286,6 +286,31 @@ mq_index *mq_index_clone_sized(const mq_index *src, int device, uint64_t table_s
  * mq_index_save of it is loadable. */
 int mq_index_merge(mq_index *dst, const mq_index *src, uint32_t id_base);
 int mq_index_merge_file(mq_index *dst, const char *path, uint32_t id_base);
+/* Index coverage: which bases of which reference the live k-min-mers of a finalized index span, and how many live k-min-mers each
+ * reference owns -- what extending, resizing and merging an index can silently change (a decoy that repeats a key of chr1 kills it for
+ * both), and where a read cannot map.  A slot is live as everywhere else (inserted once, end != 0).  A live entry of a reference of
+ * length len covers the bases [start, min(end, len - 1)], both ends inclusive: the interval the entry records, what a Match of that
+ * k-min-mer alone reports as r_start / r_end (with homopolymer compression the recorded end may stop short of the l-mer's true last
+ * base; the coverage reports the index, it does not repair it).  A live entry with start > end or start >= len covers nothing and is
+ * counted in *out_of_range (only a crafted file holds one).  Dead entries contribute nothing; a base whose only possible entry would
+ * have end == 0 is never covered.  A reference's coverage is the union of its live entries' intervals:
+ *   refs       one record per reference that exists (len > 0), in id order: its live k-min-mers, its covered bases, and its intervals
+ *              intervals[first_interval, first_interval + n_intervals)
+ *   intervals  the maximal runs of covered bases, half-open [start, end), sorted by reference id, then by start; no interval runs
+ *              from one reference into the next
+ * mq_index_coverage locks the index, waits for the device (as mq_index_resize does), computes from the table as it is now and returns
+ * host copies that stay valid until the next mq_index_coverage, mq_index_coverage_release, mq_index_reopen, mq_index_resize,
+ * mq_index_merge* or mq_index_free on the index (each drops them).  The device memory it takes (one bit per base: 390 MB for a 3.1-Gbp
+ * genome) is given back before it returns.  MQ_ESTATE: the index is not finalized, or a context of it has a submitted batch that was
+ * not waited for.  MQ_ENOMEM leaves the index usable and without a result.  Any of the five outputs may be NULL. */
+typedef struct mq_ref_coverage {   /* 48 bytes */
+    uint32_t ref_id, reserved;
+    uint64_t len, live_kminmers, covered_bases, n_intervals, first_interval;
+} mq_ref_coverage;
+typedef struct mq_cov_interval { uint32_t start, end; } mq_cov_interval;   /* [start, end), 8 bytes */
+int mq_index_coverage(mq_index *idx, const mq_ref_coverage **refs, uint64_t *n_refs,
+                      const mq_cov_interval **intervals, uint64_t *n_intervals, uint64_t *out_of_range);
+int mq_index_coverage_release(mq_index *idx);
 int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len);
 /* The parameters an index was built with (a loaded file's k, l, density, use_hpc and seeding variant decide its keys), and the ones that
  * act at mapping time only -- Params.c / .s (Chain::get_match, src/chain.rs:147-169), .g (the gap tests, src/chain.rs:132-142) and the

@@ -59,6 +59,16 @@ int mq_last_stage_clocks(mq_index *idx, uint64_t *out16);
 int mq_last_map_ms(mq_index *idx, float *ms);
 int mq_ctx_last_map_ms(mq_ctx *ctx, float *ms);
 
+/* mq_index_coverage cuts its bitmap into tiles of this many bits (64 * MQ_COV_TILE_WORDS; a tile never spans two references, a run of
+ * covered bases may): the tests place reference lengths and runs on exactly those borders.  mqdiag_coverage_held: the bytes of the
+ * host copies the index holds for the caller of mq_index_coverage (0: none -- released, or dropped by a call that changes the index). */
+uint64_t mqdiag_coverage_tile_bits(void);
+uint64_t mqdiag_coverage_held(const mq_index *idx);
+/* With MQ_COVER_TIMING=1 in the environment mq_index_coverage times its launches with events (and waits behind each); this returns
+ * the last call's of the calling thread, in ms: [0] bitmap clear, [1] cover_mark_kernel, [2] cover_count_kernel, [3] cover_scan_kernel,
+ * [4] cover_emit_kernel, [5] count_kernel's pass over the same table, the plain stream the mark pass is held against. */
+int mqdiag_coverage_ms(float *out6);
+
 #ifdef __cplusplus
 }
 #endif

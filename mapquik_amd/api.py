@@ -33,6 +33,11 @@ chain_span_dtype = np.dtype([("first", "<u4"), ("count", "<u4")])
 MQ_CHAIN_TOP = 1
 MQ_CHAINS_DROPPED = 0xFFFFFFFF
 assert chain_dtype.itemsize == 48 and chain_span_dtype.itemsize == 8
+# mq_ref_coverage / mq_cov_interval (Index.coverage): one record per reference; a maximal run of covered bases, half-open [start, end)
+ref_coverage_dtype = np.dtype([("ref_id", "<u4"), ("reserved", "<u4"), ("len", "<u8"), ("live_kminmers", "<u8"), ("covered_bases", "<u8"),
+                               ("n_intervals", "<u8"), ("first_interval", "<u8")])
+cov_interval_dtype = np.dtype([("start", "<u4"), ("end", "<u4")])
+assert ref_coverage_dtype.itemsize == 48 and cov_interval_dtype.itemsize == 8
 
 
 def hit_column(hits, name):
@@ -53,7 +58,7 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_ctx_reserve_anchors", "mq_ctx_anchors", "mq_ctx_anchors_device", "mq_map_reserve_anchors", "mq_map_anchors",
            "mq_ctx_reserve_chains", "mq_ctx_chains", "mq_ctx_chains_device", "mq_map_reserve_chains", "mq_map_chains", "mq_format_paf_chain",
            "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized",
-           "mq_index_merge", "mq_index_merge_file"]
+           "mq_index_merge", "mq_index_merge_file", "mq_index_coverage", "mq_index_coverage_release"]
 
 
 class MapquikError(RuntimeError):
@@ -210,6 +215,14 @@ def load_library(path=None):
     if hasattr(L, "mq_index_merge"):
         L.mq_index_merge.argtypes = [vp, vp, u32]
         L.mq_index_merge_file.argtypes = [vp, C.c_char_p, u32]
+    if hasattr(L, "mq_index_coverage"):
+        L.mq_index_coverage.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.mq_index_coverage_release.argtypes = [vp]
+        L.mqdiag_coverage_tile_bits.restype = u64
+        L.mqdiag_coverage_tile_bits.argtypes = []
+        L.mqdiag_coverage_held.restype = u64
+        L.mqdiag_coverage_held.argtypes = [vp]
+        L.mqdiag_coverage_ms.argtypes = [C.POINTER(C.c_float)]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -357,6 +370,23 @@ class Index:
         if self._L.mq_index_merge_file(self._h, os.fsencode(path), base) != 0:
             raise _err(self._L, "mq_index_merge_file")
         return base
+
+    def coverage(self):
+        """(refs, intervals, out_of_range) of mq_index_coverage, as numpy copies: one ref_coverage_dtype record per reference in id order
+        (its live k-min-mers, covered bases, and its intervals[first_interval : first_interval + n_intervals]), the maximal runs of
+        bases the live k-min-mers span as cov_interval_dtype [start, end), and the live entries that lie outside their reference."""
+        rp, ip = C.c_void_p(), C.c_void_p()
+        nr, ni, oor = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if self._L.mq_index_coverage(self._h, C.byref(rp), C.byref(nr), C.byref(ip), C.byref(ni), C.byref(oor)) != 0:
+            raise _err(self._L, "mq_index_coverage")
+        refs = np.frombuffer(C.string_at(rp.value, nr.value * 48), dtype=ref_coverage_dtype).copy() if nr.value else np.zeros(0, dtype=ref_coverage_dtype)
+        ivs = np.frombuffer(C.string_at(ip.value, ni.value * 8), dtype=cov_interval_dtype).copy() if ni.value else np.zeros(0, dtype=cov_interval_dtype)
+        return refs, ivs, oor.value
+
+    def coverage_release(self):
+        """the library's own copies of the last coverage() result given back (they also go with the next call that changes the index)"""
+        if self._L.mq_index_coverage_release(self._h) != 0:
+            raise _err(self._L, "mq_index_coverage_release")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -829,6 +859,27 @@ class Context:
         if self._L.mqdiag_ctx_last_map_spec(self._h, C.byref(a)) != 0:
             raise _err(self._L, "mqdiag_ctx_last_map_spec")
         return a.value
+
+
+def format_coverage_bed(index, refs, intervals):
+    """<prefix>.coverage.bed of --coverage: `r_name\tstart\tend\n` per interval of Index.coverage(), references in id order"""
+    out = []
+    for r in refs:
+        name = index.ref_info(int(r["ref_id"]))[0].encode()
+        a = int(r["first_interval"])
+        for iv in intervals[a:a + int(r["n_intervals"])]:
+            out.append(b"%s\t%d\t%d\n" % (name, int(iv["start"]), int(iv["end"])))
+    return b"".join(out)
+
+
+def format_coverage_tsv(index, refs):
+    """<prefix>.coverage.tsv of --coverage: a header line, then one line per reference; the fraction is covered / len as %.6f"""
+    out = [b"#ref\tlen\tlive_kminmers\tcovered\tfraction\tintervals\n"]
+    for r in refs:
+        name = index.ref_info(int(r["ref_id"]))[0].encode()
+        out.append(b"%s\t%d\t%d\t%d\t%.6f\t%d\n" % (name, int(r["len"]), int(r["live_kminmers"]), int(r["covered_bases"]),
+                                                    int(r["covered_bases"]) / int(r["len"]), int(r["n_intervals"])))
+    return b"".join(out)
 
 
 def ref_extract(ref_idx, inp_seq_raw, params, mers_index, name=None):

@@ -9,6 +9,7 @@ order (src/closures.rs:117-123).  No CPU compute fallback exists.
 """
 import argparse
 import gzip
+import os
 import resource
 import sys
 import time
@@ -128,7 +129,22 @@ def build_parser():
                     help="also write <prefix>.chains: one line per candidate chain of every read (one per reference with a Match run in the read, ties "
                          "included), reads in input order: the twelve PAF columns of the chain, tp:A:P for the read's unique top chain and tp:A:S "
                          "for every other, cn:i:<runs kept>, and tie:i:1 on the top chains of a tied read (extension)")
+    ap.add_argument("--coverage", action="store_true",
+                    help="once the index is complete (behind --index / --reference / --add-reference / --merge-index), also write <prefix>.coverage.bed: "
+                         "r_name, start, end of every maximal run of reference bases that the index's live k-min-mers span, and <prefix>.coverage.tsv: "
+                         "per reference its length, live k-min-mers, covered bases, covered fraction and intervals (extension)")
     return ap
+
+
+def write_coverage(index, prefix):
+    """--coverage: the two files of the finished index, and the log line"""
+    refs, ivs, out_of_range = index.coverage()
+    with open(prefix + ".coverage.bed", "wb") as f:
+        f.write(api.format_coverage_bed(index, refs, ivs))
+    with open(prefix + ".coverage.tsv", "wb") as f:
+        f.write(api.format_coverage_tsv(index, refs))
+    index.coverage_release()
+    return "Coverage: %d of %d bases in %d intervals (%d entries out of range)" % (int(refs["covered_bases"].sum()), int(refs["len"].sum()), ivs.size, out_of_range)
 
 
 def chain_lines(index, names, offs, spans, chains):
@@ -271,6 +287,14 @@ def main(argv=None):
         ts = time.time()
         index.save(opt.save_index)
         print("Saved index to %s in %s." % (opt.save_index, rust_duration(time.time() - ts)))
+    if opt.coverage:
+        try:
+            print(write_coverage(index, st["prefix"]))
+        except (api.MapquikError, OSError) as e:  # as a failure of the map phase ends the native driver: no PAF, exit status 101
+            paf.close()
+            os.remove(st["prefix"] + ".paf")
+            print("--coverage: %s" % e, file=sys.stderr)
+            raise SystemExit(101)
     print("Indexed %d unique k-min-mers in %s." % (unique, rust_duration(time.time() - t0)))  # src/closures.rs:92
 
     t0 = time.time()

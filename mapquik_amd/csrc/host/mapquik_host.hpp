@@ -139,6 +139,55 @@ class ReadOnlyIndex {
         unique_ = b.n_unique;
         return Merged{b.n_refs - a.n_refs, b.n_kminmers - a.n_kminmers};
     }
+    // Which bases of which reference the live k-min-mers span (mq_index_coverage): the library's host copies, valid until the next call
+    // that changes this index or asks again.  bed() / tsv(): the two files of --coverage.
+    struct Coverage {
+        const mq_index *index = nullptr;
+        const mq_ref_coverage *refs = nullptr;
+        const mq_cov_interval *intervals = nullptr;
+        uint64_t n_refs = 0, n_intervals = 0, out_of_range = 0;
+        uint64_t covered() const {
+            uint64_t s = 0;
+            for (uint64_t i = 0; i < n_refs; ++i) s += refs[i].covered_bases;
+            return s;
+        }
+        uint64_t total() const {
+            uint64_t s = 0;
+            for (uint64_t i = 0; i < n_refs; ++i) s += refs[i].len;
+            return s;
+        }
+        std::string name(const mq_ref_coverage &r) const {
+            const char *n = "";
+            if (mq_index_ref_info(index, r.ref_id, &n, nullptr) != MQ_OK) throw Error("Coverage: " + last_error());
+            return n;
+        }
+        std::string bed() const {  // r_name \t start \t end, one line per interval
+            std::string out;
+            for (uint64_t i = 0; i < n_refs; ++i) {
+                const std::string n = name(refs[i]);
+                for (uint64_t j = refs[i].first_interval; j < refs[i].first_interval + refs[i].n_intervals; ++j)
+                    out += n + "\t" + std::to_string(intervals[j].start) + "\t" + std::to_string(intervals[j].end) + "\n";
+            }
+            return out;
+        }
+        std::string tsv() const {
+            std::string out = "#ref\tlen\tlive_kminmers\tcovered\tfraction\tintervals\n";
+            for (uint64_t i = 0; i < n_refs; ++i) {
+                const mq_ref_coverage &r = refs[i];
+                char frac[64];
+                snprintf(frac, sizeof(frac), "%.6f", (double)r.covered_bases / (double)r.len);
+                out += name(r) + "\t" + std::to_string(r.len) + "\t" + std::to_string(r.live_kminmers) + "\t" + std::to_string(r.covered_bases) + "\t" + frac + "\t" +
+                       std::to_string(r.n_intervals) + "\n";
+            }
+            return out;
+        }
+    };
+    Coverage coverage() {
+        Coverage c;
+        c.index = h_;
+        if (mq_index_coverage(h_, &c.refs, &c.n_refs, &c.intervals, &c.n_intervals, &c.out_of_range) != MQ_OK) throw Error("ReadOnlyIndex::coverage: " + last_error());
+        return c;
+    }
 
   private:
     friend class Index;

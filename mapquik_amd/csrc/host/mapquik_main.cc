@@ -111,7 +111,7 @@ static bool is_fasta_name(const std::string &n) {
 
 struct Opt {
     std::string reads, reference, prefix;
-    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false;
+    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false, coverage = false;
     long k = -1, l = -1, c = -1, s = -1, g = -1, threads = -1, b = -1, q = -1;
     double density = -1;
     int device = 0;
@@ -138,7 +138,7 @@ struct Opt {
 static void usage() {
     puts("mapquik 0.1.0 (HIP backend)\nOriginal implementation of mapquik, a fast HiFi read mapper.\n\n"
          "USAGE:\n    mapquik [FLAGS] [OPTIONS] [reads]\n\nFLAGS:\n        --debug\n        --low-memory\n        --nohpc\n        --nosimd\n"
-         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n\nOPTIONS:\n"
+         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n        --coverage      (extension) also write <prefix>.coverage.bed (the reference bases the index's live k-min-mers span) and <prefix>.coverage.tsv (per reference: live k-min-mers, covered bases), once the index is complete\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
          "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
@@ -624,7 +624,22 @@ static void build_or_load_index(const RefPhase &rp, const Routes &rt, int device
 
 // The index built on the first GPU is finalized, saved where --save-index asks for it, and the finalized table is copied device to
 // device to the other GPUs (mq_index_clone).
-static void finalise_save_clone(const Opt &o, const Devices &dev, std::unique_ptr<Index> &building, std::vector<std::unique_ptr<ReadOnlyIndex>> &ro) {
+// --coverage: <prefix>.coverage.bed and <prefix>.coverage.tsv of the finished index (ReadOnlyIndex::coverage), and one log line
+static void write_coverage(const std::string &prefix, ReadOnlyIndex &index) {
+    const ReadOnlyIndex::Coverage c = index.coverage();
+    const std::pair<std::string, std::string> files[2] = {{prefix + ".coverage.bed", c.bed()}, {prefix + ".coverage.tsv", c.tsv()}};
+    for (const auto &f : files) {
+        FILE *fp = fopen(f.first.c_str(), "w");
+        const bool ok = fp && fwrite(f.second.data(), 1, f.second.size(), fp) == f.second.size();
+        if ((fp && fclose(fp) != 0) || !ok) throw Error("Couldn't write " + f.first);
+    }
+    printf("Coverage: %llu of %llu bases in %llu intervals (%llu entries out of range)\n", (unsigned long long)c.covered(), (unsigned long long)c.total(),
+           (unsigned long long)c.n_intervals, (unsigned long long)c.out_of_range);
+    mq_index_coverage_release(index.handle());
+}
+
+static void finalise_save_clone(const Opt &o, const Devices &dev, std::unique_ptr<Index> &building, std::vector<std::unique_ptr<ReadOnlyIndex>> &ro, const std::string &prefix,
+                                OutputFiles &out) {
     if (building) {
         ro[0].reset(new ReadOnlyIndex(std::move(*building).into_read_only()));
         tl("into_read_only returned (table allocated, k-min-mers inserted)");
@@ -640,6 +655,16 @@ static void finalise_save_clone(const Opt &o, const Devices &dev, std::unique_pt
         const auto ts = Clock::now();
         ro[0]->save(o.save_index);
         printf("Saved index to %s in %s.\n", o.save_index.c_str(), rust_duration(secs(ts)).c_str());
+    }
+    // --coverage: the index phase is complete; once, on the primary index, before the replicas are made
+    if (o.coverage) {
+        try {
+            write_coverage(prefix, *ro[0]);
+        } catch (...) {
+            out.discard_paf();  // (a failure here ends the run like one of the map phase: no PAF)
+            throw;
+        }
+        tl("coverage written");
     }
     std::vector<std::function<void()>> clones;
     for (int g = 1; g < o.gpus; ++g) clones.push_back([&, g]() { ro[g].reset(new ReadOnlyIndex(ro[0]->clone_to(dev.of(g)))); });
@@ -731,7 +756,7 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
     size_t first_ref_id = 0;
     build_or_load_index(RefPhase{o, P, building, rt.n_parse, start_feed, g_knobs.prefetch, first_ref_id}, rt, dev.of(0), preload, ro[0], slots, early);
     tl("every reference record handed to ref_extract");
-    finalise_save_clone(o, dev, building, ro);
+    finalise_save_clone(o, dev, building, ro, prefix, out);
     finish_slots_and_pool(early, slots, ro, feed, n_buffers);
     tl("replicas cloned, stream slots and first chunk buffers set up");
     printf("Indexed %llu unique k-min-mers in %s.\n", (unsigned long long)ro[0]->unique_count(), rust_duration(secs(t0)).c_str());
@@ -771,6 +796,7 @@ int main(int argc, char **argv) {
         else if (a == "--nohpc") o.nohpc = true;
         else if (a == "--parallelfastx") o.parallelfastx = true;
         else if (a == "--unmapped") o.unmapped = true;
+        else if (a == "--coverage") o.coverage = true;
         else if (a == "--anchors") o.anchors = true;
         else if (a == "--chains") o.chains = true;
         else if (a == "-p" || a == "--prefix") { o.prefix = val(); o.has_prefix = true; }

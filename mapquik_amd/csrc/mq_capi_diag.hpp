@@ -269,4 +269,14 @@ int mq_ctx_last_map_ms(mq_ctx *ctx, float *ms) {
     });
 }
 
+uint64_t mqdiag_coverage_tile_bits(void) { return 64ull * MQ_COV_TILE_WORDS; }
+uint64_t mqdiag_coverage_held(const mq_index *idx) { return idx ? idx->cov.held() : 0; }
+// MQ_COVER_TIMING=1: the last mq_index_coverage of this thread, in ms -- [0] bitmap clear [1] cover_mark_kernel [2] cover_count_kernel
+// [3] cover_scan_kernel [4] cover_emit_kernel [5] count_kernel's pass over the same table
+int mqdiag_coverage_ms(float *out6) {
+    if (!out6) return set_err(MQ_EINVAL, "bad arguments");
+    memcpy(out6, g_cover_ms, sizeof(g_cover_ms));
+    return MQ_OK;
+}
+
 }  // extern "C"

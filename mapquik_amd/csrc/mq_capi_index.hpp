@@ -465,6 +465,7 @@ int mq_index_reopen(mq_index *idx) {
         int rc = use_device(idx);
         if (rc) return rc;
         HIPCHK(hipDeviceSynchronize());
+        idx->cov.drop();  // (a coverage result describes the table as it was)
         idx->finalized = false;
         idx->extending = true;
         return MQ_OK;
@@ -479,6 +480,7 @@ int mq_index_resize(mq_index *idx, uint64_t table_slots, uint32_t slots_per_kmin
         uint64_t nslots = 0;
         int rc = sized_table_slots(table_slots, slots_per_kminmer, idx->n_kmm_total, idx->n_keys, &nslots);
         if (rc) return rc;
+        idx->cov.drop();  // (every accepted resize lets a coverage result go, the one that leaves the table as it is included)
         if (!nslots || nslots == idx->nslots) return MQ_OK;
         if ((rc = use_device(idx))) return rc;
         HIPCHK(hipDeviceSynchronize());  // launches queued on the contexts read the table that is about to go

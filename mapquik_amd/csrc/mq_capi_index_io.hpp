@@ -601,6 +601,7 @@ int mq_index_merge(mq_index *dst, const mq_index *src, uint32_t id_base) {
         std::lock_guard<std::mutex> lk1(first), lk2(second);
         int rc = merge_check_dst("mq_index_merge", dst);
         if (rc) return rc;
+        dst->cov.drop();  // (a coverage result describes the table as it was)
         if (!src->finalized) return set_err(MQ_ESTATE, "mq_index_merge: src is not finalized");
         if ((rc = merge_check_params("mq_index_merge", dst->params, src->params, "src"))) return rc;
         if ((rc = merge_check_ids("mq_index_merge", dst, src->refs, id_base))) return rc;
@@ -616,6 +617,7 @@ int mq_index_merge_file(mq_index *dst, const char *path, uint32_t id_base) {
         std::lock_guard<std::mutex> lk(dst->mu);
         int rc = merge_check_dst("mq_index_merge_file", dst);
         if (rc) return rc;
+        dst->cov.drop();
         return merge_file_locked(dst, path, id_base);
     });
 }

@@ -345,6 +345,30 @@ struct TableReservation {
     ~TableReservation() { join(); }
 };
 
+// mq_index_coverage (mq_cover_kernels.hpp): the device side of one call, all of it given back before the call returns, and the host
+// copies the caller reads until the next call that changes the index, or asks again, drops them.
+struct CoverState {
+    Buf<unsigned long long> bitmap;          // one bit per base, every existing reference on a word boundary, two words of padding
+    Buf<uint64_t> base, lens_c;              // the cover base word per reference id (dense, beside d_ref_lens); the existing references' lengths
+    Buf<unsigned long long> live;            // live entries per reference id (dense)
+    Buf<CovTile> tiles;
+    Buf<uint32_t> tile_runs;
+    Buf<unsigned long long> tile_off, ref_sums, first_interval, acc;
+    Buf<mq_cov_interval> intervals;          // allocated behind the count, at its exact size
+    std::vector<mq_ref_coverage> h_refs;
+    std::vector<mq_cov_interval> h_intervals;
+    uint64_t out_of_range = 0;
+    // (the owner has selected the index's device)
+    void free_device() { reset_all(bitmap, base, lens_c, live, tiles, tile_runs, tile_off, ref_sums, first_interval, acc, intervals); }
+    void drop() {
+        free_device();
+        std::vector<mq_ref_coverage>().swap(h_refs);
+        std::vector<mq_cov_interval>().swap(h_intervals);
+        out_of_range = 0;
+    }
+    uint64_t held() const { return h_refs.capacity() * sizeof(mq_ref_coverage) + h_intervals.capacity() * sizeof(mq_cov_interval); }
+};
+
 struct mq_index {
     mq_params params;
     DevParams dp;
@@ -384,8 +408,9 @@ struct mq_index {
     double table_alloc_ms = 0;      // what allocating + clearing the table that is in use took (hipMalloc + memset + synchronize), wherever it ran
     // What lives on the device.  ~mq_index joins the reservation and selects the device; then the members go last to first: the reserved
     // table, the k-min-mer chunks, the staged pieces (synchronised first), the build scratch, the table, the reference lengths, and
-    // last the default context (synchronised, then released).
+    // last the default context (synchronised, then released).  (The coverage state holds device memory only inside mq_index_coverage.)
     CtxPtr def_ctx;      // the context behind the index-level map entry points
+    CoverState cov;      // mq_index_coverage: the last result's host copies
     Buf<uint64_t> d_ref_lens;
     Buf<Bucket> table;   // nslots / 2 buckets + the extra bucket of the key 0
     BuildScratch bld;
