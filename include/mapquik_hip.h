@@ -311,6 +311,56 @@ typedef struct mq_cov_interval { uint32_t start, end; } mq_cov_interval;   /* [s
 int mq_index_coverage(mq_index *idx, const mq_ref_coverage **refs, uint64_t *n_refs,
                       const mq_cov_interval **intervals, uint64_t *n_intervals, uint64_t *out_of_range);
 int mq_index_coverage_release(mq_index *idx);
+/* Mapping depth: where the reads landed, per window of every reference, accumulated on the device from finished mq_hit records (the
+ * companion of the coverage: that one says "no live k-min-mer here", this one "no read landed here").  An mq_depth is bound to a
+ * snapshot of the index's reference ids and lengths, taken at mq_depth_new.
+ * Which hits count.  A hit is counted iff status == MQ_HIT_MAPPED and mapq >= min_mapq (min_mapq 0: every mapped read).  A hit with
+ * another status (MQ_HIT_UNMAPPED, MQ_HIT_OVERFLOW) is tallied as not_mapped, a mapped one with mapq < min_mapq as below_mapq.
+ * What a counted hit covers.  On a reference of length len: the bases [r_start, min(r_end, len - 1)], both ends inclusive -- columns 8
+ * and 9 as the PAF prints them.  It covers nothing, and is tallied as out_of_range instead, when r_start > r_end, when r_start >= len,
+ * when ref_id lies beyond the snapshot, or in a hole of a sparse id range (len == 0).  (The Match::check precedence quirk can make
+ * find_coords wrap, so such hits are legal outputs of the mapper.)
+ * Windows.  1 <= window <= 2^24, any integer.  Window j of a reference is [j * window, min((j + 1) * window, len)); a reference has
+ * ceil(len / window) windows, and the windows of all references lie behind one another in id order: reference r's are
+ * [first_window, first_window + n_windows) of the two window arrays.
+ *   window_bases[j]   (u64) the sum, over the counted hits, of the number of the hit's bases inside the window
+ *   window_starts[j]  (u32) the number of counted hits whose r_start lies in the window
+ *   refs              one 64-byte record per reference that exists (len > 0), in id order: reads = its counted hits, bases = the sum of
+ *                     its windows' window_bases, zero_windows = its windows with window_bases == 0, max_window_bases
+ *   totals            offered = counted + not_mapped + below_mapq + out_of_range
+ * The result is a function of the multiset of hits offered since mq_depth_new or the last mq_depth_clear: not of their order, of the
+ * batches they came in, or of the route (host or device) they took.  An accumulator refuses a batch with MQ_EINVAL once `offered` would
+ * pass 2^31 - 1 (the running count of a window is 32 bits wide).
+ *   mq_depth_new(idx, window, min_mapq, &out)   MQ_ESTATE: idx is not finalized; MQ_EINVAL: window == 0 or > 2^24; MQ_ENOMEM (nothing is
+ *                          left behind): no device memory, or more than 2^31 - 1 windows in all -- 16 bytes of accumulators per window and
+ *                          12 for a result: 90 MB for a 3.1-Gbp genome at window 1000; window 1 on a human genome is MQ_ENOMEM.
+ *   mq_depth_add(d, hits, n)                    hits in host memory: staged, accumulated, and in when the call returns.  n == 0 is legal.
+ *   mq_depth_add_device(d, d_hits, n, stream)   hits in device memory (16-byte aligned) on the index's device, asynchronous on `stream`
+ *                          (a hipStream_t, may be NULL): nothing is allocated, nothing is read by the host.  Queued behind
+ *                          mq_map_batch_device on the same stream it sees that call's final hits, the redo arena's included.
+ *   mq_depth_result(d, ...)                     waits for the device (every queued mq_depth_add_device included), computes from the
+ *                          accumulators without changing them -- more hits may follow -- and returns host copies that stay valid until
+ *                          the next mq_depth_result, mq_depth_clear or mq_depth_free on the accumulator.  Any output may be NULL.
+ *   mq_depth_clear(d)                           waits for the device; everything back to zero.
+ * Every call on one accumulator locks it: several threads, and several contexts' streams, may add to one accumulator.  The snapshot is
+ * the accumulator's own: after mq_index_reopen / mq_index_merge* of its index, hits on the ids it does not know are out_of_range.  Free
+ * every accumulator before its index, as a context; an accumulator that is only added to and read may outlive it (after mq_depth_new
+ * it uses the index's device, not the index: the native driver's second pass adds to the first pass's accumulator). */
+typedef struct mq_depth mq_depth;
+typedef struct mq_ref_depth {   /* 64 bytes */
+    uint32_t ref_id, reserved;
+    uint64_t len, n_windows, first_window, reads, bases, zero_windows, max_window_bases;
+} mq_ref_depth;
+typedef struct mq_depth_totals {   /* 40 bytes */
+    uint64_t offered, counted, not_mapped, below_mapq, out_of_range;
+} mq_depth_totals;
+int mq_depth_new(mq_index *idx, uint32_t window, uint32_t min_mapq, mq_depth **out);
+void mq_depth_free(mq_depth *d);
+int mq_depth_clear(mq_depth *d);
+int mq_depth_add(mq_depth *d, const mq_hit *hits, uint32_t n);
+int mq_depth_add_device(mq_depth *d, const mq_hit *d_hits, uint32_t n, void *stream);
+int mq_depth_result(mq_depth *d, const mq_ref_depth **refs, uint64_t *n_refs, const uint64_t **window_bases,
+                    const uint32_t **window_starts, uint64_t *n_windows, mq_depth_totals *totals);
 int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len);
 /* The parameters an index was built with (a loaded file's k, l, density, use_hpc and seeding variant decide its keys), and the ones that
  * act at mapping time only -- Params.c / .s (Chain::get_match, src/chain.rs:147-169), .g (the gap tests, src/chain.rs:132-142) and the

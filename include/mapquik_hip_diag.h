@@ -69,6 +69,13 @@ uint64_t mqdiag_coverage_held(const mq_index *idx);
  * [4] cover_emit_kernel, [5] count_kernel's pass over the same table, the plain stream the mark pass is held against. */
 int mqdiag_coverage_ms(float *out6);
 
+/* mq_depth_result walks the windows in tiles of this many (MQ_DEPTH_TILE_WINDOWS; a tile never spans two references, a hit may span
+ * many tiles): the tests place reference lengths and hits on exactly those borders. */
+uint64_t mqdiag_depth_tile_windows(void);
+/* The kernels of the last mq_depth_result of the accumulator between two device events, in ms (the sum, scan and emit launches
+ * together; tools/depth_cost.py). */
+int mqdiag_depth_result_ms(mq_depth *d, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,11 @@ ref_coverage_dtype = np.dtype([("ref_id", "<u4"), ("reserved", "<u4"), ("len", "
                                ("n_intervals", "<u8"), ("first_interval", "<u8")])
 cov_interval_dtype = np.dtype([("start", "<u4"), ("end", "<u4")])
 assert ref_coverage_dtype.itemsize == 48 and cov_interval_dtype.itemsize == 8
+# mq_ref_depth / mq_depth_totals (Depth.result): one record per reference; the accumulator's tallies
+ref_depth_dtype = np.dtype([("ref_id", "<u4"), ("reserved", "<u4"), ("len", "<u8"), ("n_windows", "<u8"), ("first_window", "<u8"), ("reads", "<u8"),
+                            ("bases", "<u8"), ("zero_windows", "<u8"), ("max_window_bases", "<u8")])
+depth_totals_dtype = np.dtype([(n, "<u8") for n in ("offered", "counted", "not_mapped", "below_mapq", "out_of_range")])
+assert ref_depth_dtype.itemsize == 64 and depth_totals_dtype.itemsize == 40
 
 
 def hit_column(hits, name):
@@ -58,7 +63,8 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_ctx_reserve_anchors", "mq_ctx_anchors", "mq_ctx_anchors_device", "mq_map_reserve_anchors", "mq_map_anchors",
            "mq_ctx_reserve_chains", "mq_ctx_chains", "mq_ctx_chains_device", "mq_map_reserve_chains", "mq_map_chains", "mq_format_paf_chain",
            "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized",
-           "mq_index_merge", "mq_index_merge_file", "mq_index_coverage", "mq_index_coverage_release"]
+           "mq_index_merge", "mq_index_merge_file", "mq_index_coverage", "mq_index_coverage_release",
+           "mq_depth_new", "mq_depth_free", "mq_depth_clear", "mq_depth_add", "mq_depth_add_device", "mq_depth_result"]
 
 
 class MapquikError(RuntimeError):
@@ -223,6 +229,17 @@ def load_library(path=None):
         L.mqdiag_coverage_held.restype = u64
         L.mqdiag_coverage_held.argtypes = [vp]
         L.mqdiag_coverage_ms.argtypes = [C.POINTER(C.c_float)]
+    if hasattr(L, "mq_depth_new"):
+        L.mq_depth_new.argtypes = [vp, u32, u32, C.POINTER(vp)]
+        L.mq_depth_free.restype = None
+        L.mq_depth_free.argtypes = [vp]
+        L.mq_depth_clear.argtypes = [vp]
+        L.mq_depth_add.argtypes = [vp, vp, u32]
+        L.mq_depth_add_device.argtypes = [vp, vp, u32, vp]
+        L.mq_depth_result.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]
+        L.mqdiag_depth_tile_windows.restype = u64
+        L.mqdiag_depth_tile_windows.argtypes = []
+        L.mqdiag_depth_result_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -859,6 +876,85 @@ class Context:
         if self._L.mqdiag_ctx_last_map_spec(self._h, C.byref(a)) != 0:
             raise _err(self._L, "mqdiag_ctx_last_map_spec")
         return a.value
+
+
+class Depth:
+    """A depth accumulator (mq_depth) on a finalized index: per window of `window` bases of every reference, how many bases of the hits
+    offered so far landed there, counting the mapped hits with mapq >= min_mapq (the rules: include/mapquik_hip.h).  It keeps its own
+    snapshot of the index's reference ids and lengths; close it before its index."""
+
+    def __init__(self, index, window=1000, min_mapq=60):
+        self._L = index._L
+        self.window, self.min_mapq = int(window), int(min_mapq)
+        if not 0 <= self.window < 1 << 32 or not 0 <= self.min_mapq < 1 << 32:
+            raise ValueError("window and min_mapq are 32-bit")
+        h = C.c_void_p()
+        if self._L.mq_depth_new(index._h, self.window, self.min_mapq, C.byref(h)) != 0:
+            raise _err(self._L, "mq_depth_new")
+        self._h = h.value
+
+    def add(self, hits):
+        """the structured array map_batch returns (host memory); the hits are in when the call returns"""
+        hits = np.ascontiguousarray(hits, dtype=hit_dtype)
+        if self._L.mq_depth_add(self._h, _p(hits), hits.size) != 0:
+            raise _err(self._L, "mq_depth_add")
+
+    def add_device(self, d_hits, n, stream=0):
+        """n hits in device memory, asynchronous on `stream`: behind map_batch_device on the same stream it sees that call's final hits"""
+        if self._L.mq_depth_add_device(self._h, C.c_void_p(d_hits), int(n), C.c_void_p(stream)) != 0:
+            raise _err(self._L, "mq_depth_add_device")
+
+    def result(self):
+        """(refs, window_bases, window_starts, totals) as numpy copies: one ref_depth_dtype record per reference in id order (its windows are
+        [first_window, first_window + n_windows) of the two window arrays), u64 bases and u32 hit starts per window, and the tallies as a
+        dict.  Waits for the device; the accumulator goes on accumulating."""
+        rp, bp, sp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nr, nw = C.c_uint64(), C.c_uint64()
+        tot = np.zeros(1, dtype=depth_totals_dtype)
+        if self._L.mq_depth_result(self._h, C.byref(rp), C.byref(nr), C.byref(bp), C.byref(sp), C.byref(nw), _p(tot)) != 0:
+            raise _err(self._L, "mq_depth_result")
+        refs = np.frombuffer(C.string_at(rp.value, nr.value * 64), dtype=ref_depth_dtype).copy() if nr.value else np.zeros(0, dtype=ref_depth_dtype)
+        wb = np.frombuffer(C.string_at(bp.value, nw.value * 8), dtype="<u8").copy() if nw.value else np.zeros(0, dtype="<u8")
+        ws = np.frombuffer(C.string_at(sp.value, nw.value * 4), dtype="<u4").copy() if nw.value else np.zeros(0, dtype="<u4")
+        return refs, wb, ws, {n: int(tot[0][n]) for n in depth_totals_dtype.names}
+
+    def clear(self):
+        if self._L.mq_depth_clear(self._h) != 0:
+            raise _err(self._L, "mq_depth_clear")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mq_depth_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def format_depth_bed(index, refs, window_bases, window_starts, window):
+    """<prefix>.depth.bed of --depth: `r_name\tstart\tend\tbases\tstarts\tmean\n` per window of Depth.result(), references in id order; mean is
+    bases / (end - start) as %.2f"""
+    out = []
+    w = int(window)
+    for r in refs:
+        name = index.ref_info(int(r["ref_id"]))[0].encode()
+        first, ln = int(r["first_window"]), int(r["len"])
+        for j in range(int(r["n_windows"])):
+            a, b = j * w, min((j + 1) * w, ln)
+            bases = int(window_bases[first + j])
+            out.append(b"%s\t%d\t%d\t%d\t%d\t%.2f\n" % (name, a, b, bases, int(window_starts[first + j]), bases / (b - a)))
+    return b"".join(out)
+
+
+def format_depth_tsv(index, refs, window):
+    """<prefix>.depth.tsv of --depth: a header line, then one line per reference; mean is bases / len, max_window_mean the largest
+    window_bases over a window's width, min(window, len), both as %.2f"""
+    out = [b"#ref\tlen\treads\tbases\tmean\tzero_windows\tmax_window_mean\n"]
+    for r in refs:
+        name = index.ref_info(int(r["ref_id"]))[0].encode()
+        ln = int(r["len"])
+        out.append(b"%s\t%d\t%d\t%d\t%.2f\t%d\t%.2f\n" % (name, ln, int(r["reads"]), int(r["bases"]), int(r["bases"]) / ln, int(r["zero_windows"]),
+                                                        int(r["max_window_bases"]) / min(int(window), ln)))
+    return b"".join(out)
 
 
 def format_coverage_bed(index, refs, intervals):

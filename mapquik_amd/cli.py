@@ -133,7 +133,31 @@ def build_parser():
                     help="once the index is complete (behind --index / --reference / --add-reference / --merge-index), also write <prefix>.coverage.bed: "
                          "r_name, start, end of every maximal run of reference bases that the index's live k-min-mers span, and <prefix>.coverage.tsv: "
                          "per reference its length, live k-min-mers, covered bases, covered fraction and intervals (extension)")
+    ap.add_argument("--depth", action="store_true",
+                    help="also write <prefix>.depth.bed: r_name, start, end, bases, starts, mean per window of every reference -- how many bases of the "
+                         "mapped reads (PAF columns 8 and 9, mapq >= --depth-min-mapq) landed in the window and how many of them start there -- and "
+                         "<prefix>.depth.tsv: per reference its length, reads, bases, mean depth, windows without a base and the deepest window's mean "
+                         "(extension; accumulated on the device from each batch's hits)")
+    ap.add_argument("--depth-window", type=int, default=1000, metavar="N", help="with --depth: bases per window, 1 .. 2^24 (default 1000)")
+    ap.add_argument("--depth-min-mapq", type=int, default=60, metavar="Q", help="with --depth: count the reads with mapq >= Q (default 60; 0: every mapped read)")
     return ap
+
+
+def depth_log_line(totals, refs, window, min_mapq):
+    """the one line both drivers print for --depth"""
+    return "Depth: %d of %d hits counted (%d not mapped, %d below mapq %d, %d out of range): %d bases in %d windows of %d" % (
+        totals["counted"], totals["offered"], totals["not_mapped"], totals["below_mapq"], min_mapq, totals["out_of_range"], int(refs["bases"].sum()),
+        int(refs["n_windows"].sum()), window)
+
+
+def write_depth(index, depth, prefix):
+    """--depth: the two files of the run's accumulator, and the log line"""
+    refs, wb, ws, totals = depth.result()
+    with open(prefix + ".depth.bed", "wb") as f:
+        f.write(api.format_depth_bed(index, refs, wb, ws, depth.window))
+    with open(prefix + ".depth.tsv", "wb") as f:
+        f.write(api.format_depth_tsv(index, refs, depth.window))
+    return depth_log_line(totals, refs, depth.window, depth.min_mapq)
 
 
 def write_coverage(index, prefix):
@@ -296,6 +320,15 @@ def main(argv=None):
             print("--coverage: %s" % e, file=sys.stderr)
             raise SystemExit(101)
     print("Indexed %d unique k-min-mers in %s." % (unique, rust_duration(time.time() - t0)))  # src/closures.rs:92
+    depth = None
+    if opt.depth:  # one accumulator on the finished index; every batch's hits go to it
+        try:
+            depth = api.Depth(index, window=opt.depth_window, min_mapq=opt.depth_min_mapq)
+        except (api.MapquikError, ValueError) as e:
+            paf.close()
+            os.remove(st["prefix"] + ".paf")
+            print("--depth: %s" % e, file=sys.stderr)
+            raise SystemExit(101)
 
     t0 = time.time()
     if opt.parallelfastx and not opt.reads.endswith((".gz", ".lz4")):
@@ -315,6 +348,8 @@ def main(argv=None):
         if chn is not None:  # (a read has no more chains than runs: the anchors' bound)
             index.reserve_chains(len(seqs), min(int(bases.size * (4.0 * st["density"] + 1.0 / 512.0)) + 64, (1 << 32) - 2))
         hits = index.map_batch(bases, offs)
+        if depth is not None:
+            depth.add(hits)
         if chn is not None:
             spans, chains, info = index.chains()
             if info["dropped_reads"]:
@@ -346,6 +381,9 @@ def main(argv=None):
             names, seqs, acc = [], [], 0
     flush(names, seqs)
     paf.close()
+    if depth is not None:
+        print(write_depth(index, depth, st["prefix"]))
+        depth.close()
     if unm is not None:
         unm.close()
     if anc is not None:

@@ -147,6 +147,7 @@ class MapPipeline {
         FILE *anchors = nullptr;  // --anchors: <prefix>.anchors, written the way the unmapped names are
         double density = 0;       // ... and what a slot's reservation is sized with (Ctx::reserve_anchors)
         FILE *chains = nullptr;   // --chains: <prefix>.chains, the same way
+        mq_depth *depth = nullptr;  // --depth: the run's accumulator; every chunk's final hits are added where the chunk goes to the formatters
     };
     // slots[w]: the stream slots of submitter w (n_sub submitters per GPU, each over its GPU's index); index: where the formatters look
     // reference names up; paf, unmapped, unmapped_fa: the open output files, the last two may be null
@@ -229,6 +230,9 @@ class MapPipeline {
                 }
                 if (p.cfg_.anchors) take_pooled(mq_ctx_anchors, "mq_ctx_anchors", "--anchors", "anchor", ctx[sl].handle(), *c, c->anchors);
                 if (p.cfg_.chains) take_pooled(mq_ctx_chains, "mq_ctx_chains", "--chains", "chain", ctx[sl].handle(), *c, c->chains);
+                // --depth: behind the wait, so the host-driven redos are in; one call per chunk, from whichever GPU's slot it came
+                if (p.cfg_.depth && !c->hits.empty() && mq_depth_add(p.cfg_.depth, c->hits.data(), (uint32_t)c->hits.size()) != MQ_OK)
+                    throw Error(std::string("mq_depth_add: ") + last_error());
             } catch (const std::exception &e) { p.fail(e.what()); }
             c->unparsed = false;
             inflight[sl] = nullptr;

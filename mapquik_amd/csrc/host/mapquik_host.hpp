@@ -188,6 +188,82 @@ class ReadOnlyIndex {
         if (mq_index_coverage(h_, &c.refs, &c.n_refs, &c.intervals, &c.n_intervals, &c.out_of_range) != MQ_OK) throw Error("ReadOnlyIndex::coverage: " + last_error());
         return c;
     }
+    // Where the reads landed (mq_depth): an accumulator on this index's device with a snapshot of its reference ids and lengths, fed with
+    // finished hits from any thread.  Names are resolved when it is made, so it may be read after the index has gone (the second pass of
+    // the native driver adds to the first pass's accumulator).  bed() / tsv() / log_line(): the two files and the log line of --depth.
+    class Depth {
+      public:
+        Depth(const ReadOnlyIndex &index, uint32_t window, uint32_t min_mapq) : window_(window), min_mapq_(min_mapq) {
+            if (mq_depth_new(index.h_, window, min_mapq, &h_) != MQ_OK) throw Error("ReadOnlyIndex::Depth: " + last_error());
+            index_ = index.h_;
+        }
+        Depth(const Depth &) = delete;
+        Depth &operator=(const Depth &) = delete;
+        ~Depth() { mq_depth_free(h_); }
+        mq_depth *handle() const { return h_; }
+        void add(const mq_hit *hits, uint32_t n) {
+            if (mq_depth_add(h_, hits, n) != MQ_OK) throw Error("mq_depth_add: " + last_error());
+        }
+        // the result (the library's host copies, valid until the next fetch) with the references' names, looked up while the index lives
+        void fetch() {
+            if (mq_depth_result(h_, &refs_, &n_refs_, &bases_, &starts_, &n_windows_, &totals_) != MQ_OK) throw Error("mq_depth_result: " + last_error());
+            if (!index_) return;
+            names_.clear();
+            for (uint64_t i = 0; i < n_refs_; ++i) {
+                const char *n = "";
+                if (mq_index_ref_info(index_, refs_[i].ref_id, &n, nullptr) != MQ_OK) throw Error("Depth: " + last_error());
+                names_.push_back(n);
+            }
+        }
+        // the index is about to go: the names are kept, later fetches do not ask it again
+        void detach() {
+            fetch();
+            index_ = nullptr;
+        }
+        std::string bed() const {  // r_name \t start \t end \t bases \t starts \t mean, one line per window
+            std::string out;
+            char mean[64];
+            for (uint64_t i = 0; i < n_refs_; ++i) {
+                const mq_ref_depth &r = refs_[i];
+                for (uint64_t j = 0; j < r.n_windows; ++j) {
+                    const uint64_t a = j * window_, b = std::min<uint64_t>((j + 1) * window_, r.len), v = bases_[r.first_window + j];
+                    snprintf(mean, sizeof(mean), "%.2f", (double)v / (double)(b - a));
+                    out += names_[i] + "\t" + std::to_string(a) + "\t" + std::to_string(b) + "\t" + std::to_string(v) + "\t" + std::to_string(starts_[r.first_window + j]) + "\t" + mean + "\n";
+                }
+            }
+            return out;
+        }
+        std::string tsv() const {
+            std::string out = "#ref\tlen\treads\tbases\tmean\tzero_windows\tmax_window_mean\n";
+            char mean[64], deepest[64];
+            for (uint64_t i = 0; i < n_refs_; ++i) {
+                const mq_ref_depth &r = refs_[i];
+                snprintf(mean, sizeof(mean), "%.2f", (double)r.bases / (double)r.len);
+                snprintf(deepest, sizeof(deepest), "%.2f", (double)r.max_window_bases / (double)std::min<uint64_t>(window_, r.len));
+                out += names_[i] + "\t" + std::to_string(r.len) + "\t" + std::to_string(r.reads) + "\t" + std::to_string(r.bases) + "\t" + mean + "\t" + std::to_string(r.zero_windows) +
+                       "\t" + deepest + "\n";
+            }
+            return out;
+        }
+        std::string log_line() const {
+            uint64_t bases = 0, windows = 0;
+            for (uint64_t i = 0; i < n_refs_; ++i) bases += refs_[i].bases, windows += refs_[i].n_windows;
+            return "Depth: " + std::to_string(totals_.counted) + " of " + std::to_string(totals_.offered) + " hits counted (" + std::to_string(totals_.not_mapped) + " not mapped, " +
+                   std::to_string(totals_.below_mapq) + " below mapq " + std::to_string(min_mapq_) + ", " + std::to_string(totals_.out_of_range) + " out of range): " +
+                   std::to_string(bases) + " bases in " + std::to_string(windows) + " windows of " + std::to_string(window_);
+        }
+
+      private:
+        mq_depth *h_ = nullptr;
+        const mq_index *index_ = nullptr;
+        uint32_t window_, min_mapq_;
+        const mq_ref_depth *refs_ = nullptr;
+        const uint64_t *bases_ = nullptr;
+        const uint32_t *starts_ = nullptr;
+        uint64_t n_refs_ = 0, n_windows_ = 0;
+        mq_depth_totals totals_ = {};
+        std::vector<std::string> names_;
+    };
 
   private:
     friend class Index;

@@ -111,7 +111,8 @@ static bool is_fasta_name(const std::string &n) {
 
 struct Opt {
     std::string reads, reference, prefix;
-    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false, coverage = false;
+    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false, coverage = false, depth = false;
+    long depth_window = 1000, depth_min_mapq = 60;
     long k = -1, l = -1, c = -1, s = -1, g = -1, threads = -1, b = -1, q = -1;
     double density = -1;
     int device = 0;
@@ -138,10 +139,10 @@ struct Opt {
 static void usage() {
     puts("mapquik 0.1.0 (HIP backend)\nOriginal implementation of mapquik, a fast HiFi read mapper.\n\n"
          "USAGE:\n    mapquik [FLAGS] [OPTIONS] [reads]\n\nFLAGS:\n        --debug\n        --low-memory\n        --nohpc\n        --nosimd\n"
-         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n        --coverage      (extension) also write <prefix>.coverage.bed (the reference bases the index's live k-min-mers span) and <prefix>.coverage.tsv (per reference: live k-min-mers, covered bases), once the index is complete\n\nOPTIONS:\n"
+         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n        --coverage      (extension) also write <prefix>.coverage.bed (the reference bases the index's live k-min-mers span) and <prefix>.coverage.tsv (per reference: live k-min-mers, covered bases), once the index is complete\n        --depth         (extension) also write <prefix>.depth.bed (per window of every reference: bases of the mapped reads that landed there, reads that start there, mean depth) and <prefix>.depth.tsv (per reference: reads, bases, mean depth, empty windows, the deepest window's mean)\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --depth-window <n> (extension, with --depth) bases per window, 1 .. 2^24 (default 1000)\n        --depth-min-mapq <q> (extension, with --depth) count the reads with mapq >= q (default 60; 0: every mapped read)\n        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -706,6 +707,22 @@ static void teardown(const Opt &o, StreamSlots &slots, std::vector<std::unique_p
     ref_reaper.join();
 }
 
+// --depth: the run's one accumulator (ReadOnlyIndex::Depth).  It is made on the first pass's primary index once the index phase is
+// complete; every chunk of every GPU's slots, and of the second pass, is added to it where the chunk goes to the formatters; the last
+// pass writes <prefix>.depth.bed and <prefix>.depth.tsv under the FIRST pass's prefix and prints the log line.
+static std::unique_ptr<ReadOnlyIndex::Depth> g_depth;
+static std::string g_depth_prefix;
+static void write_depth() {
+    g_depth->fetch();
+    const std::pair<std::string, std::string> files[2] = {{g_depth_prefix + ".depth.bed", g_depth->bed()}, {g_depth_prefix + ".depth.tsv", g_depth->tsv()}};
+    for (const auto &f : files) {
+        FILE *fp = fopen(f.first.c_str(), "w");
+        const bool ok = fp && fwrite(f.second.data(), 1, f.second.size(), fp) == f.second.size();
+        if ((fp && fclose(fp) != 0) || !ok) throw Error("Couldn't write " + f.first);
+    }
+    puts(g_depth->log_line().c_str());
+}
+
 // One run of the reference's flow (src/closures.rs:22-212): index the reference, map the reads, write <prefix>.paf in input
 // order.  second_fa != "": the reads left unmapped also go to that FASTA file (for the second pass).
 static int run_pass(const Opt &o, const Params &P, const std::string &reads_path, bool reads_fasta, bool ref_fasta, const std::string &prefix,
@@ -761,10 +778,20 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
     tl("replicas cloned, stream slots and first chunk buffers set up");
     printf("Indexed %llu unique k-min-mers in %s.\n", (unsigned long long)ro[0]->unique_count(), rust_duration(secs(t0)).c_str());
 
+    if (o.depth && !g_depth) {  // (the second pass finds the first pass's)
+        try {
+            g_depth.reset(new ReadOnlyIndex::Depth(*ro[0], (uint32_t)o.depth_window, (uint32_t)o.depth_min_mapq));
+            g_depth_prefix = prefix;
+        } catch (...) {
+            out.discard_paf();
+            throw;
+        }
+    }
+
     t0 = Clock::now();
     if (P.use_pfx && !ends_with(reads_path, ".gz") && !ends_with(reads_path, ".lz4")) puts("Warning: using experimental rust-parallelfastx (exciting!)");
     start_feed();
-    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density, out.chn});
+    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density, out.chn, g_depth ? g_depth->handle() : nullptr});
     try {
         pipeline.run();
     } catch (...) {
@@ -772,6 +799,14 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
         throw;
     }
     out.close();
+    if (g_depth) {
+        if (o.last_pass) {
+            write_depth();
+            g_depth.reset();
+        } else {
+            g_depth->detach();  // this pass's index goes; the accumulator and the names stay for the second pass
+        }
+    }
     if (g_knobs.timing) pipeline.report(secs(t0));
     printf("Mapped query sequences in %s.\n", rust_duration(secs(t0)).c_str());  // src/closures.rs:211
     tl("PAF written");
@@ -797,6 +832,15 @@ int main(int argc, char **argv) {
         else if (a == "--parallelfastx") o.parallelfastx = true;
         else if (a == "--unmapped") o.unmapped = true;
         else if (a == "--coverage") o.coverage = true;
+        else if (a == "--depth") o.depth = true;
+        else if (a == "--depth-window") {
+            o.depth_window = atol(val());
+            if (o.depth_window < 1 || o.depth_window > (1l << 24)) { fprintf(stderr, "error: --depth-window wants 1..16777216\n"); return 2; }
+        }
+        else if (a == "--depth-min-mapq") {
+            o.depth_min_mapq = atol(val());
+            if (o.depth_min_mapq < 0 || o.depth_min_mapq > 0xFFFFFFFFl) { fprintf(stderr, "error: --depth-min-mapq wants a 32-bit value\n"); return 2; }
+        }
         else if (a == "--anchors") o.anchors = true;
         else if (a == "--chains") o.chains = true;
         else if (a == "-p" || a == "--prefix") { o.prefix = val(); o.has_prefix = true; }
@@ -911,6 +955,7 @@ int main(int argc, char **argv) {
             if (rc) return rc;
         }
     } catch (const std::exception &e) {  // mapquik::Error, feeder::FeederError: the reference panics (exit code 101)
+        g_depth.reset();
         fflush(stdout);
         fprintf(stderr, "mapquik: %s\n", e.what());
         return 101;

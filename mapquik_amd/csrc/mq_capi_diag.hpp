@@ -279,4 +279,13 @@ int mqdiag_coverage_ms(float *out6) {
     return MQ_OK;
 }
 
+uint64_t mqdiag_depth_tile_windows(void) { return MQ_DEPTH_TILE_WINDOWS; }
+// the kernels of the accumulator's last mq_depth_result, between two events on its stream
+int mqdiag_depth_result_ms(mq_depth *d, float *ms) {
+    if (!d || !ms) return set_err(MQ_EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lk(d->mu);
+    *ms = d->result_ms;
+    return MQ_OK;
+}
+
 }  // extern "C"

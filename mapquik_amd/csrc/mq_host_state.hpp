@@ -369,6 +369,37 @@ struct CoverState {
     uint64_t held() const { return h_refs.capacity() * sizeof(mq_ref_coverage) + h_intervals.capacity() * sizeof(mq_cov_interval); }
 };
 
+// mq_depth (mq_depth_kernels.hpp, mq_capi_depth.hpp): a depth accumulator.  Its own object beside the index: it holds a snapshot of the
+// reference ids and lengths (plan) and nothing of the index but its device.  Everything but the hit staging and the result arrays is
+// allocated at mq_depth_new; mq_depth_add_device only points a launch's arguments here.  (Members go last to first: the buffers, the
+// events, then the stream; the owner has selected the device and waited for it.)
+struct mq_depth {
+    std::mutex mu;  // every entry point locks the accumulator
+    int device = 0;
+    uint32_t window = 0, min_mapq = 0;
+    uint32_t n_ids = 0, n_tiles = 0;
+    uint64_t n_windows = 0;
+    uint64_t offered = 0;                      // hits offered since creation or the last clear (< 2^31)
+    std::vector<mq_ref_depth> plan;            // the existing references in id order: ref_id, len, n_windows, first_window
+    ScopedStream stream;                       // the host route's launches and the result pass
+    ScopedEvent e0, e1;                        // around the result pass's kernels (mqdiag_depth_result_ms)
+    float result_ms = 0;
+    Buf<uint64_t> lens, base;                  // dense by reference id: the snapshot's lengths, every reference's first window
+    Buf<unsigned long long> edge;              // the three accumulators, n_windows each
+    Buf<int> diff;
+    Buf<uint32_t> starts;
+    Buf<unsigned long long> reads, acc;        // counted hits per reference id (dense); DEPTH_ACC_WORDS totals
+    Buf<DepthTile> tiles;
+    Buf<long long> tile_sum, tile_pref, tile_off;
+    Buf<unsigned long long> ref_sums;          // three words per existing reference
+    Buf<unsigned long long> window_bases;      // the result arrays: allocated by the first mq_depth_result
+    Buf<uint32_t> window_starts;
+    Buf<mq_hit> stage;                         // mq_depth_add's hits on their way in (grows)
+    std::vector<mq_ref_depth> h_refs;          // the caller's copies of the last result
+    std::vector<uint64_t> h_bases;
+    std::vector<uint32_t> h_starts;
+};
+
 struct mq_index {
     mq_params params;
     DevParams dp;
