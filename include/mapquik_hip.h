@@ -361,6 +361,59 @@ int mq_depth_add(mq_depth *d, const mq_hit *hits, uint32_t n);
 int mq_depth_add_device(mq_depth *d, const mq_hit *d_hits, uint32_t n, void *stream);
 int mq_depth_result(mq_depth *d, const mq_ref_depth **refs, uint64_t *n_refs, const uint64_t **window_bases,
                     const uint32_t **window_starts, uint64_t *n_windows, mq_depth_totals *totals);
+/* Coordinate order: the permutation that puts finished mq_hit records -- the PAF lines -- in the order of (reference, r_start), by a
+ * stable radix sort on the device.  An mq_sorter is an object beside the index, as mq_depth: bound to the index's device and to a
+ * snapshot of its reference ids (dense lengths, len > 0 <=> the id exists), taken at mq_sort_new.
+ * What is kept.  Hit i of an add call with first_ordinal = o carries the ordinal o + i (u32): the caller's name for the hit, typically
+ * the read's number in input order.  It is kept iff status == MQ_HIT_MAPPED, mapq >= min_mapq, and ref_id exists in the snapshot.  Any
+ * other status is tallied not_mapped; a mapped hit below min_mapq below_mapq; a mapped hit at or above min_mapq whose ref_id lies beyond
+ * the snapshot or in a hole out_of_range.  r_start is not range-checked: a wrapped find_coords value sorts where its number puts it.
+ * The order.  Kept records ascend by the 88-bit key (ref_id : 24 bits, r_start : 32 bits, ordinal : 32 bits).  Two records that agree
+ * in all three fields come out in unspecified order: the caller gave one ordinal twice.  The result is a function of the multiset of
+ * (hit, ordinal) pairs offered since mq_sort_new or the last mq_sort_clear: not of their order, their batches, the route or the stream.
+ *   order   the kept records' ordinals in that order (u32 each), n_kept of them
+ *   refs    one 24-byte record per reference that exists, in id order: its records are order[first, first + count)
+ *   totals  offered = kept + not_mapped + below_mapq + out_of_range
+ * Capacity is counted in OFFERED hits, not kept ones: the host knows every n, so no add can overflow on the device and nothing is ever
+ * dropped.  Ordinals and `offered` stay below 2^32 - 1: a call that would pass this (first_ordinal + n wrapping included) is MQ_EINVAL.
+ *   mq_sort_new(idx, capacity, min_mapq, &out)   MQ_ESTATE: idx is not finalized; MQ_EINVAL: capacity > 2^32 - 2; MQ_ENOMEM: nothing is left
+ *                          behind.  capacity 0 is legal (the host route grows).  Device memory: 12 bytes per record of capacity (an 8-byte
+ *                          key ref_id << 32 | r_start and the ordinal); the first mq_sort_result adds a second key / ordinal set, 12 bytes
+ *                          more per record, and the per-tile digit counts, 1 KB per tile of 2,048 records (0.5 byte per record): 24.5 bytes
+ *                          per record in all, 98 MB for 4 M reads.  Beside these: the snapshot (8 bytes per reference id up to the
+ *                          largest, 4 per existing reference and 16 for its first / count), a fixed 22.5 KB block of digit histograms
+ *                          and row totals, and -- the host route only -- a staging buffer of 48 bytes per hit of the largest
+ *                          mq_sort_add so far (with a quarter of slack), kept until mq_sort_free.
+ *   mq_sort_add(s, hits, n, first_ordinal)       hits in host memory: staged, filtered, appended, and in when the call returns.  Grows the
+ *                          sorter itself when offered + n > capacity, by doubling (it is synchronous anyway).  n == 0 is legal.
+ *   mq_sort_add_device(s, d_hits, n, first_ordinal, stream)   hits in device memory (16-byte aligned) on the index's device, asynchronous
+ *                          on `stream` (a hipStream_t, may be NULL): nothing is allocated, nothing is read by the host.  When
+ *                          offered + n > capacity it answers MQ_EOVERFLOW before anything is queued, and nothing has changed.  Queued
+ *                          behind mq_map_batch_device on the same stream it sees that call's final hits, the redo arena's included.
+ *   mq_sort_reserve(s, capacity)                 waits for the device, grows the sorter to `capacity` and keeps its contents; never shrinks;
+ *                          MQ_ENOMEM leaves the sorter as it was (its result scratch aside, which the next result brings back).
+ *   mq_sort_result(s, ...)                       waits for the device (every queued mq_sort_add_device included), sorts, and returns host
+ *                          copies that stay valid until the next mq_sort_result, _clear, _reserve or _free on the sorter.  More adds
+ *                          may follow, and a later result covers everything.  Any output may be NULL.
+ *   mq_sort_clear(s)                             waits for the device; the sorter is empty again, its capacity stays.
+ * Every call on one sorter locks it: several threads, and several contexts' streams, may add to one sorter.  The snapshot is the
+ * sorter's own, as an accumulator's; free every sorter before its index. */
+typedef struct mq_sorter mq_sorter;
+typedef struct mq_sort_ref {      /* 24 bytes; one per existing reference, in id order */
+    uint32_t ref_id, reserved;
+    uint64_t first, count;        /* its records: order[first, first + count) */
+} mq_sort_ref;
+typedef struct mq_sort_totals {   /* 40 bytes */
+    uint64_t offered, kept, not_mapped, below_mapq, out_of_range;   /* offered = the sum of the other four */
+} mq_sort_totals;
+int mq_sort_new(mq_index *idx, uint64_t capacity, uint32_t min_mapq, mq_sorter **out);   /* capacity 0 is legal (host route grows) */
+void mq_sort_free(mq_sorter *s);
+int mq_sort_clear(mq_sorter *s);
+int mq_sort_reserve(mq_sorter *s, uint64_t capacity);
+int mq_sort_add(mq_sorter *s, const mq_hit *hits, uint32_t n, uint32_t first_ordinal);
+int mq_sort_add_device(mq_sorter *s, const mq_hit *d_hits, uint32_t n, uint32_t first_ordinal, void *stream);
+int mq_sort_result(mq_sorter *s, const uint32_t **order, uint64_t *n_kept, const mq_sort_ref **refs, uint64_t *n_refs,
+                   mq_sort_totals *totals);
 int mq_index_ref_info(const mq_index *idx, uint32_t ref_id, const char **name, uint64_t *len);
 /* The parameters an index was built with (a loaded file's k, l, density, use_hpc and seeding variant decide its keys), and the ones that
  * act at mapping time only -- Params.c / .s (Chain::get_match, src/chain.rs:147-169), .g (the gap tests, src/chain.rs:132-142) and the

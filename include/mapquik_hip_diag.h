@@ -76,6 +76,15 @@ uint64_t mqdiag_depth_tile_windows(void);
  * together; tools/depth_cost.py). */
 int mqdiag_depth_result_ms(mq_depth *d, float *ms);
 
+/* mq_sort_result sorts in tiles of this many records (MQ_SORT_TILE): the tests place kept counts on exactly those borders. */
+uint64_t mqdiag_sort_tile_records(void);
+/* How many of the 11 digits the sorter's last mq_sort_result sorted (a digit in which all kept records agree is skipped; 0 before the
+ * first result and for fewer than two distinct keys). */
+int mqdiag_sort_passes(mq_sorter *s, uint32_t *passes);
+/* The device side of the sorter's last mq_sort_result between two events on its stream, in ms: the histogram pass and its read-back, the
+ * passes, the references (tools/sort_cost.py). */
+int mqdiag_sort_result_ms(mq_sorter *s, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,10 @@ ref_depth_dtype = np.dtype([("ref_id", "<u4"), ("reserved", "<u4"), ("len", "<u8
                             ("bases", "<u8"), ("zero_windows", "<u8"), ("max_window_bases", "<u8")])
 depth_totals_dtype = np.dtype([(n, "<u8") for n in ("offered", "counted", "not_mapped", "below_mapq", "out_of_range")])
 assert ref_depth_dtype.itemsize == 64 and depth_totals_dtype.itemsize == 40
+# mq_sort_ref / mq_sort_totals (Sorter.result): one record per reference; the sorter's tallies
+sort_ref_dtype = np.dtype([("ref_id", "<u4"), ("reserved", "<u4"), ("first", "<u8"), ("count", "<u8")])
+sort_totals_dtype = np.dtype([(n, "<u8") for n in ("offered", "kept", "not_mapped", "below_mapq", "out_of_range")])
+assert sort_ref_dtype.itemsize == 24 and sort_totals_dtype.itemsize == 40
 
 
 def hit_column(hits, name):
@@ -64,7 +68,8 @@ EXPORTS = ["mq_index_set_table_factor", "mq_ctx_submit_fastx", "mq_index_get_par
            "mq_ctx_reserve_chains", "mq_ctx_chains", "mq_ctx_chains_device", "mq_map_reserve_chains", "mq_map_chains", "mq_format_paf_chain",
            "mq_index_reopen", "mq_index_resize", "mq_index_load_sized", "mq_index_clone_sized",
            "mq_index_merge", "mq_index_merge_file", "mq_index_coverage", "mq_index_coverage_release",
-           "mq_depth_new", "mq_depth_free", "mq_depth_clear", "mq_depth_add", "mq_depth_add_device", "mq_depth_result"]
+           "mq_depth_new", "mq_depth_free", "mq_depth_clear", "mq_depth_add", "mq_depth_add_device", "mq_depth_result",
+           "mq_sort_new", "mq_sort_free", "mq_sort_clear", "mq_sort_reserve", "mq_sort_add", "mq_sort_add_device", "mq_sort_result"]
 
 
 class MapquikError(RuntimeError):
@@ -240,6 +245,19 @@ def load_library(path=None):
         L.mqdiag_depth_tile_windows.restype = u64
         L.mqdiag_depth_tile_windows.argtypes = []
         L.mqdiag_depth_result_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    if hasattr(L, "mq_sort_new"):
+        L.mq_sort_new.argtypes = [vp, u64, u32, C.POINTER(vp)]
+        L.mq_sort_free.restype = None
+        L.mq_sort_free.argtypes = [vp]
+        L.mq_sort_clear.argtypes = [vp]
+        L.mq_sort_reserve.argtypes = [vp, u64]
+        L.mq_sort_add.argtypes = [vp, vp, u32, u32]
+        L.mq_sort_add_device.argtypes = [vp, vp, u32, u32, vp]
+        L.mq_sort_result.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), vp]
+        L.mqdiag_sort_tile_records.restype = u64
+        L.mqdiag_sort_tile_records.argtypes = []
+        L.mqdiag_sort_passes.argtypes = [vp, C.POINTER(u32)]
+        L.mqdiag_sort_result_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if hasattr(L, "mqdiag_last_map_spec"):
         L.mqdiag_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.mqdiag_ctx_last_map_spec.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -928,6 +946,84 @@ class Depth:
             self._h = None
 
     __del__ = close
+
+
+class Sorter:
+    """A coordinate sorter (mq_sorter) on a finalized index: the permutation that orders the hits offered so far by (ref_id, r_start,
+    ordinal), keeping the mapped hits with mapq >= min_mapq on references of its snapshot (the rules: include/mapquik_hip.h).  `capacity`
+    counts offered hits: add() grows the sorter, add_device() never does.  Close it before its index."""
+
+    def __init__(self, index, capacity=0, min_mapq=0):
+        self._L = index._L
+        self.min_mapq = int(min_mapq)
+        if not 0 <= self.min_mapq < 1 << 32 or not 0 <= int(capacity) < 1 << 64:
+            raise ValueError("min_mapq is 32-bit, capacity 64-bit")
+        h = C.c_void_p()
+        if self._L.mq_sort_new(index._h, int(capacity), self.min_mapq, C.byref(h)) != 0:
+            raise _err(self._L, "mq_sort_new")
+        self._h = h.value
+
+    def add(self, hits, first_ordinal):
+        """the structured array map_batch returns (host memory); hit i carries the ordinal first_ordinal + i; in when the call returns"""
+        hits = np.ascontiguousarray(hits, dtype=hit_dtype)
+        if self._L.mq_sort_add(self._h, _p(hits), hits.size, int(first_ordinal)) != 0:
+            raise _err(self._L, "mq_sort_add")
+
+    def add_device(self, d_hits, n, first_ordinal, stream=0):
+        """n hits in device memory, asynchronous on `stream`: behind map_batch_device on the same stream it sees that call's final hits"""
+        if self._L.mq_sort_add_device(self._h, C.c_void_p(d_hits), int(n), int(first_ordinal), C.c_void_p(stream)) != 0:
+            raise _err(self._L, "mq_sort_add_device")
+
+    def reserve(self, capacity):
+        if self._L.mq_sort_reserve(self._h, int(capacity)) != 0:
+            raise _err(self._L, "mq_sort_reserve")
+
+    def result(self):
+        """(order, refs, totals) as numpy copies: the kept hits' ordinals in sorted order (u32), one sort_ref_dtype record per reference in
+        id order (its hits are order[first : first + count]) and the tallies as a dict.  Waits for the device; more adds may follow."""
+        op, rp = C.c_void_p(), C.c_void_p()
+        nk, nr = C.c_uint64(), C.c_uint64()
+        tot = np.zeros(1, dtype=sort_totals_dtype)
+        if self._L.mq_sort_result(self._h, C.byref(op), C.byref(nk), C.byref(rp), C.byref(nr), _p(tot)) != 0:
+            raise _err(self._L, "mq_sort_result")
+        order = np.frombuffer(C.string_at(op.value, nk.value * 4), dtype="<u4").copy() if nk.value else np.zeros(0, dtype="<u4")
+        refs = np.frombuffer(C.string_at(rp.value, nr.value * 24), dtype=sort_ref_dtype).copy() if nr.value else np.zeros(0, dtype=sort_ref_dtype)
+        return order, refs, {n: int(tot[0][n]) for n in sort_totals_dtype.names}
+
+    def passes(self):
+        """how many of the key's 11 digits the last result() sorted"""
+        v = C.c_uint32()
+        if self._L.mqdiag_sort_passes(self._h, C.byref(v)) != 0:
+            raise _err(self._L, "mqdiag_sort_passes")
+        return v.value
+
+    def result_ms(self):
+        v = C.c_float()
+        if self._L.mqdiag_sort_result_ms(self._h, C.byref(v)) != 0:
+            raise _err(self._L, "mqdiag_sort_result_ms")
+        return v.value
+
+    def clear(self):
+        if self._L.mq_sort_clear(self._h) != 0:
+            raise _err(self._L, "mq_sort_clear")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mq_sort_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def format_sorted_tsv(index, refs, line_offsets):
+    """<prefix>.sorted.tsv of --sort: a header line, then per reference of Sorter.result() its name, length, lines, first line (0-based)
+    and the byte offset of that line in <prefix>.sorted.paf -- a seek table.  line_offsets[j]: where sorted line j begins (n_kept + 1
+    entries, the last one the file's size)."""
+    out = [b"#ref\tlen\tlines\tfirst_line\toffset\n"]
+    for r in refs:
+        name, ln = index.ref_info(int(r["ref_id"]))
+        out.append(b"%s\t%d\t%d\t%d\t%d\n" % (name.encode(), ln, int(r["count"]), int(r["first"]), int(line_offsets[int(r["first"])])))
+    return b"".join(out)
 
 
 def format_depth_bed(index, refs, window_bases, window_starts, window):

@@ -140,7 +140,47 @@ def build_parser():
                          "(extension; accumulated on the device from each batch's hits)")
     ap.add_argument("--depth-window", type=int, default=1000, metavar="N", help="with --depth: bases per window, 1 .. 2^24 (default 1000)")
     ap.add_argument("--depth-min-mapq", type=int, default=60, metavar="Q", help="with --depth: count the reads with mapq >= Q (default 60; 0: every mapped read)")
+    ap.add_argument("--sort", action="store_true",
+                    help="also write <prefix>.sorted.paf: the lines of <prefix>.paf in the order of (reference id, column 8, input order), and "
+                         "<prefix>.sorted.tsv: per reference its name, length, lines, first line and the byte offset of that line in the sorted file "
+                         "(extension; each batch's hits are sorted on the device, <prefix>.paf stays as it is)")
+    ap.add_argument("--sort-min-mapq", type=int, default=0, metavar="Q", help="with --sort: keep the lines with mapq >= Q (default 0: every PAF line)")
     return ap
+
+
+def sort_log_line(totals, refs, min_mapq):
+    """the one line both drivers print for --sort"""
+    return "Sorted: %d of %d hits kept (%d not mapped, %d below mapq %d, %d out of range): %d lines on %d references" % (
+        totals["kept"], totals["offered"], totals["not_mapped"], totals["below_mapq"], min_mapq, totals["out_of_range"], int(refs["count"].sum()),
+        int((refs["count"] > 0).sum()))
+
+
+def write_sorted(index, sorter, prefix, line_at, line_len):
+    """--sort: <prefix>.sorted.paf gathered from <prefix>.paf (mapped, its lines written one by one: neither file is held in memory;
+    line_at / line_len: per read number, where its line lies there and how long it is, -1 / 0 without one), <prefix>.sorted.tsv, and the
+    log line.  A failure leaves none of the three files behind, as a failure of the map phase leaves no PAF."""
+    import mmap
+    names = [prefix + ".paf", prefix + ".sorted.paf", prefix + ".sorted.tsv"]
+    try:
+        order, refs, totals = sorter.result()
+        offsets = np.zeros(order.size + 1, dtype=np.int64)
+        with open(names[0], "rb") as src, open(names[1], "wb") as f:
+            paf = mmap.mmap(src.fileno(), 0, access=mmap.ACCESS_READ) if order.size else b""
+            for j, o in enumerate(order.tolist()):
+                if o >= len(line_at) or line_at[o] < 0 or line_at[o] + line_len[o] > len(paf):
+                    raise api.MapquikError("--sort: read %d was kept but has no PAF line" % o)
+                f.write(paf[line_at[o]:line_at[o] + line_len[o]])
+                offsets[j + 1] = offsets[j] + line_len[o]
+            if order.size:
+                paf.close()
+        with open(names[2], "wb") as f:
+            f.write(api.format_sorted_tsv(index, refs, offsets))
+    except (api.MapquikError, OSError, ValueError):
+        for n in names:
+            if os.path.exists(n):
+                os.remove(n)
+        raise
+    return sort_log_line(totals, refs, sorter.min_mapq)
 
 
 def depth_log_line(totals, refs, window, min_mapq):
@@ -329,6 +369,16 @@ def main(argv=None):
             os.remove(st["prefix"] + ".paf")
             print("--depth: %s" % e, file=sys.stderr)
             raise SystemExit(101)
+    sorter = None
+    if opt.sort:  # one sorter on the finished index; every batch's hits go to it under their reads' numbers in input order
+        try:
+            sorter = api.Sorter(index, min_mapq=opt.sort_min_mapq)
+        except (api.MapquikError, ValueError) as e:
+            paf.close()
+            os.remove(st["prefix"] + ".paf")
+            print("--sort: %s" % e, file=sys.stderr)
+            raise SystemExit(101)
+    line_at, line_len, paf_bytes = [], [], [0]  # --sort: per read number, its line in <prefix>.paf
 
     t0 = time.time()
     if opt.parallelfastx and not opt.reads.endswith((".gz", ".lz4")):
@@ -364,8 +414,17 @@ def main(argv=None):
                                  % (info["dropped_reads"], info["needed"], info["stored"]))
             for ln in anchor_lines(names, hits, spans, anchors, lambda r: index.ref_info(r)[0]):
                 anc.write(ln + "\n")
-        for ln in index.paf_lines(names, offs, hits):  # input order, unmapped reads write nothing (src/closures.rs:117-123)
+        lines = index.paf_lines(names, offs, hits)  # input order, unmapped reads write nothing (src/closures.rs:117-123)
+        for ln in lines:
             paf.write(ln + "\n")
+        if sorter is not None:
+            sorter.add(hits, len(line_at))
+            it = iter(lines)
+            for h in hits:
+                n = len(next(it).encode()) + 1 if int(h["status"]) == api.MQ_HIT_MAPPED else 0
+                line_at.append(paf_bytes[0] if n else -1)
+                line_len.append(n)
+                paf_bytes[0] += n
         if unm is not None:
             for nm, h in zip(names, hits):
                 if int(h["status"]) != api.MQ_HIT_MAPPED:
@@ -384,6 +443,13 @@ def main(argv=None):
     if depth is not None:
         print(write_depth(index, depth, st["prefix"]))
         depth.close()
+    if sorter is not None:
+        try:
+            print(write_sorted(index, sorter, st["prefix"], line_at, line_len))
+        except (api.MapquikError, OSError, ValueError) as e:
+            print("--sort: %s" % e, file=sys.stderr)
+            raise SystemExit(101)
+        sorter.close()
     if unm is not None:
         unm.close()
     if anc is not None:

@@ -138,6 +138,16 @@ inline std::string format_chunk(feeder::Chunk &c, PafWriter &pw, bool want_unmap
     return std::string();
 }
 
+// --sort: the pass's sorter and, per read number in input order, where the read's line lies in <prefix>.paf and how long it is (0: the
+// read has no line).  The ordered writer fills it: only there is a chunk's first read number known (a chunk whose records the device
+// finds says how many reads it holds when it comes back, and chunks come back in any order).
+struct SortLines {
+    mq_sorter *sorter = nullptr;
+    std::vector<uint64_t> at;
+    std::vector<uint32_t> len;
+    uint64_t paf_bytes = 0;
+};
+
 class MapPipeline {
   public:
     struct Config {
@@ -148,6 +158,7 @@ class MapPipeline {
         double density = 0;       // ... and what a slot's reservation is sized with (Ctx::reserve_anchors)
         FILE *chains = nullptr;   // --chains: <prefix>.chains, the same way
         mq_depth *depth = nullptr;  // --depth: the run's accumulator; every chunk's final hits are added where the chunk goes to the formatters
+        SortLines *sort = nullptr;  // --sort: every chunk's final hits are added by the ordered writer, under the reads' numbers in input order
     };
     // slots[w]: the stream slots of submitter w (n_sub submitters per GPU, each over its GPU's index); index: where the formatters look
     // reference names up; paf, unmapped, unmapped_fa: the open output files, the last two may be null
@@ -349,6 +360,7 @@ class MapPipeline {
                 done_.erase(it);
             }
             const auto tw0 = Clock::now();
+            if (cfg_.sort && !sort_chunk(*c)) return;
             if (!c->paf.empty()) fwrite(c->paf.data(), 1, c->paf.size(), paf_);
             if (unm_ && !c->unmapped.empty()) fwrite(c->unmapped.data(), 1, c->unmapped.size(), unm_);
             if (ufa_ && !c->unmapped_fa.empty()) fwrite(c->unmapped_fa.data(), 1, c->unmapped_fa.size(), ufa_);
@@ -357,6 +369,30 @@ class MapPipeline {
             feed_.recycle(c);
             t_write_us_ += us_since(tw0);
         }
+    }
+
+    // --sort: one mq_sort_add per chunk, first_ordinal = the number of the chunk's first read in input order (the hits are final: the chunk
+    // is behind its wait), and the chunk's lines -- one per mapped read, in read order -- entered into the line table.  false: it failed.
+    bool sort_chunk(const Chunk &c) {
+        SortLines &S = *cfg_.sort;
+        const uint64_t first = S.len.size();
+        if (!c.hits.empty() && (first > 0xFFFFFFFFull || mq_sort_add(S.sorter, c.hits.data(), (uint32_t)c.hits.size(), (uint32_t)first) != MQ_OK)) {
+            fail(first > 0xFFFFFFFFull ? std::string("--sort: more than 2^32 reads") : std::string("mq_sort_add: ") + last_error());
+            return false;
+        }
+        size_t pos = 0;
+        for (const mq_hit &h : c.hits) {
+            size_t n = 0;
+            if (h.status == MQ_HIT_MAPPED && pos < c.paf.size()) {
+                const void *e = memchr(c.paf.data() + pos, '\n', c.paf.size() - pos);
+                n = e ? (size_t)((const char *)e - (c.paf.data() + pos)) + 1 : 0;
+            }
+            S.at.push_back(S.paf_bytes + pos);
+            S.len.push_back((uint32_t)n);
+            pos += n;
+        }
+        S.paf_bytes += c.paf.size();
+        return true;
     }
 
     feeder::Feeder &feed_;

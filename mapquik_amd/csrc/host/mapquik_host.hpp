@@ -7,6 +7,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -263,6 +264,69 @@ class ReadOnlyIndex {
         uint64_t n_refs_ = 0, n_windows_ = 0;
         mq_depth_totals totals_ = {};
         std::vector<std::string> names_;
+    };
+    // The coordinate order of a run's hits (mq_sorter): a sorter on this index's device with a snapshot of its reference ids, fed with
+    // finished hits under their reads' numbers in input order.  It lives inside its index's lifetime.  fetch() / gather() / tsv() /
+    // log_line(): the two files and the log line of --sort.
+    class Sorter {
+      public:
+        Sorter(const ReadOnlyIndex &index, uint32_t min_mapq) : index_(index.h_), min_mapq_(min_mapq) {
+            if (mq_sort_new(index.h_, 0, min_mapq, &h_) != MQ_OK) throw Error("ReadOnlyIndex::Sorter: " + last_error());
+        }
+        Sorter(const Sorter &) = delete;
+        Sorter &operator=(const Sorter &) = delete;
+        ~Sorter() { mq_sort_free(h_); }
+        mq_sorter *handle() const { return h_; }
+        void add(const mq_hit *hits, uint32_t n, uint32_t first_ordinal) {
+            if (mq_sort_add(h_, hits, n, first_ordinal) != MQ_OK) throw Error("mq_sort_add: " + last_error());
+        }
+        // the result (the library's host copies, valid until the next fetch)
+        void fetch() {
+            if (mq_sort_result(h_, &order_, &n_kept_, &refs_, &n_refs_, &totals_) != MQ_OK) throw Error("mq_sort_result: " + last_error());
+        }
+        const uint32_t *order() const { return order_; }
+        uint64_t n_kept() const { return n_kept_; }
+        // <prefix>.sorted.paf: the lines of the paf_size bytes at `paf` (<prefix>.paf, mapped) written to `out` in sorted order, one line at a
+        // time -- nothing of either file is held in memory; at[o], len[o]: where read number o's line lies there and how long it is (0: it
+        // has none).  offsets gets where every sorted line begins, and the size behind the last.  false: a write failed.
+        bool gather(const char *paf, uint64_t paf_size, const std::vector<uint64_t> &at, const std::vector<uint32_t> &len, FILE *out, std::vector<uint64_t> &offsets) const {
+            offsets.assign(1, 0);
+            offsets.reserve(n_kept_ + 1);
+            for (uint64_t j = 0; j < n_kept_; ++j) {
+                const uint32_t o = order_[j];
+                if (o >= len.size() || !len[o] || at[o] + len[o] > paf_size) throw Error("--sort: read " + std::to_string(o) + " was kept but has no PAF line");
+                if (fwrite(paf + at[o], 1, len[o], out) != len[o]) return false;
+                offsets.push_back(offsets.back() + len[o]);
+            }
+            return true;
+        }
+        std::string tsv(const std::vector<uint64_t> &offsets) const {  // a seek table: per reference its lines and where the first begins
+            std::string out = "#ref\tlen\tlines\tfirst_line\toffset\n";
+            for (uint64_t i = 0; i < n_refs_; ++i) {
+                const mq_sort_ref &r = refs_[i];
+                const char *name = "";
+                uint64_t len = 0;
+                if (mq_index_ref_info(index_, r.ref_id, &name, &len) != MQ_OK) throw Error("Sorter: " + last_error());
+                out += std::string(name) + "\t" + std::to_string(len) + "\t" + std::to_string(r.count) + "\t" + std::to_string(r.first) + "\t" + std::to_string(offsets.at(r.first)) + "\n";
+            }
+            return out;
+        }
+        std::string log_line() const {
+            uint64_t lines = 0, with = 0;
+            for (uint64_t i = 0; i < n_refs_; ++i) lines += refs_[i].count, with += refs_[i].count != 0;
+            return "Sorted: " + std::to_string(totals_.kept) + " of " + std::to_string(totals_.offered) + " hits kept (" + std::to_string(totals_.not_mapped) + " not mapped, " +
+                   std::to_string(totals_.below_mapq) + " below mapq " + std::to_string(min_mapq_) + ", " + std::to_string(totals_.out_of_range) + " out of range): " +
+                   std::to_string(lines) + " lines on " + std::to_string(with) + " references";
+        }
+
+      private:
+        mq_sorter *h_ = nullptr;
+        const mq_index *index_;
+        uint32_t min_mapq_;
+        const uint32_t *order_ = nullptr;
+        const mq_sort_ref *refs_ = nullptr;
+        uint64_t n_kept_ = 0, n_refs_ = 0;
+        mq_sort_totals totals_ = {};
     };
 
   private:

@@ -23,8 +23,11 @@
 #include <thread>
 #include <vector>
 
+#include <fcntl.h>
+#include <sys/mman.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include "fastx_feeder.hpp"
 #include "map_pipeline.hpp"
@@ -111,8 +114,8 @@ static bool is_fasta_name(const std::string &n) {
 
 struct Opt {
     std::string reads, reference, prefix;
-    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false, coverage = false, depth = false;
-    long depth_window = 1000, depth_min_mapq = 60;
+    bool has_prefix = false, debug = false, low_memory = false, nosimd = false, nohpc = false, parallelfastx = false, unmapped = false, anchors = false, chains = false, coverage = false, depth = false, sort = false;
+    long depth_window = 1000, depth_min_mapq = 60, sort_min_mapq = 0;
     long k = -1, l = -1, c = -1, s = -1, g = -1, threads = -1, b = -1, q = -1;
     double density = -1;
     int device = 0;
@@ -139,10 +142,10 @@ struct Opt {
 static void usage() {
     puts("mapquik 0.1.0 (HIP backend)\nOriginal implementation of mapquik, a fast HiFi read mapper.\n\n"
          "USAGE:\n    mapquik [FLAGS] [OPTIONS] [reads]\n\nFLAGS:\n        --debug\n        --low-memory\n        --nohpc\n        --nosimd\n"
-         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n        --coverage      (extension) also write <prefix>.coverage.bed (the reference bases the index's live k-min-mers span) and <prefix>.coverage.tsv (per reference: live k-min-mers, covered bases), once the index is complete\n        --depth         (extension) also write <prefix>.depth.bed (per window of every reference: bases of the mapped reads that landed there, reads that start there, mean depth) and <prefix>.depth.tsv (per reference: reads, bases, mean depth, empty windows, the deepest window's mean)\n\nOPTIONS:\n"
+         "        --parallelfastx\n        --unmapped      (extension) also write <prefix>.unmapped.out\n        --anchors       (extension) also write <prefix>.anchors: the Match runs of every mapped read's winning chain\n        --chains        (extension) also write <prefix>.chains: every candidate chain of every read, ties included\n        --coverage      (extension) also write <prefix>.coverage.bed (the reference bases the index's live k-min-mers span) and <prefix>.coverage.tsv (per reference: live k-min-mers, covered bases), once the index is complete\n        --depth         (extension) also write <prefix>.depth.bed (per window of every reference: bases of the mapped reads that landed there, reads that start there, mean depth) and <prefix>.depth.tsv (per reference: reads, bases, mean depth, empty windows, the deepest window's mean)\n        --sort          (extension) also write <prefix>.sorted.paf (the lines of <prefix>.paf in the order of reference id, column 8, input order; sorted on the device) and <prefix>.sorted.tsv (per reference: lines, first line, byte offset of its first line in the sorted file)\n\nOPTIONS:\n"
          "    -b <b>\n    -c, --chain <chain>\n    -d, --density <density>\n    -g, --gap-diff <gap-diff>\n    -k <k>\n    -l <l>\n"
          "    -p, --prefix <prefix>\n    -q <q>\n        --reference <reference>\n    -s, --seed <seed>\n        --threads <threads>\n"
-         "        --depth-window <n> (extension, with --depth) bases per window, 1 .. 2^24 (default 1000)\n        --depth-min-mapq <q> (extension, with --depth) count the reads with mapq >= q (default 60; 0: every mapped read)\n        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
+         "        --depth-window <n> (extension, with --depth) bases per window, 1 .. 2^24 (default 1000)\n        --depth-min-mapq <q> (extension, with --depth) count the reads with mapq >= q (default 60; 0: every mapped read)\n        --sort-min-mapq <q> (extension, with --sort) keep the lines with mapq >= q (default 0: every PAF line)\n        --device <n>    (extension) first HIP device ordinal\n        --gpus <n>      (extension) shard read batches over n GPUs, index replicated\n        --batch-bases <n> (extension) raw input bytes per chunk\n        --table-factor <n> (extension) index table slots per k-min-mer (default 2 here: a file-fed run is host-bound; the library's default for HBM-resident batches is 8)\n        --ref-join <device|host> (extension) where the lines of a line-wrapped reference FASTA are joined: host (default: such a file is read into host memory) or device (streamed like a single-line file, never in host memory)\n        --reads-join <device|host> (extension) where the lines of a line-wrapped reads FASTA are joined: host (default: such a chunk is parsed and compacted by a host thread) or device (the chunk goes to the GPU as it lies in the file; headers found and lines joined there)\n        --save-index <file> (extension) write the finalized index (occupied slots only) for later runs\n        --index <file>  (extension) map against a saved index instead of indexing --reference (same -k -l -d --nohpc as it was built with); with --table-factor its table gets that size on load\n        --add-reference <fasta> (extension, with --index) add the file's records to the loaded index (ids continue behind its largest), then map; --save-index writes the extended index\n        --merge-index <file> (extension, repeatable) merge this saved index (same seeding parameters) into the one --index / --reference / --add-reference produced, ids continuing behind its largest, in command-line order; --save-index writes the merged index\n        --seeding-variant <v> (extension) reading of the k-min-mer iterator's unpinned decisions, bits 1 2 4 8 16 32 (include/mapquik_hip.h); 0 = frozen\n        --fast-kh       (extension) cheap k-min-mer tuple hash instead of SipHash-1-3: same PAF (the hash acts through equality only), fewer instructions\n        --second-pass <k2,l2,d2> (extension) map the unmapped reads again with these parameters: <prefix>-k2-l2-d2.{fa,paf,unmapped.out}\n\nARGS:\n    <reads>");
 }
 
 // the last two lines of a run (src/main.rs:270-271)
@@ -723,6 +726,39 @@ static void write_depth() {
     puts(g_depth->log_line().c_str());
 }
 
+// --sort: <prefix>.sorted.paf gathered from the <prefix>.paf this pass has just closed (mapped, its lines written one by one: neither
+// file is held in memory), <prefix>.sorted.tsv, and the log line.  A failure leaves none of the three files behind, as a failure of the
+// map phase leaves no PAF.
+static void write_sorted(ReadOnlyIndex::Sorter &sorter, const SortLines &lines, const std::string &prefix) {
+    const std::string paf_path = prefix + ".paf", sorted_path = prefix + ".sorted.paf", tsv_path = prefix + ".sorted.tsv";
+    void *map = MAP_FAILED;
+    const size_t size = (size_t)lines.paf_bytes;
+    try {
+        sorter.fetch();
+        if (size) {
+            const int fd = open(paf_path.c_str(), O_RDONLY);
+            struct stat sb;
+            if (fd >= 0 && fstat(fd, &sb) == 0 && (size_t)sb.st_size == size) map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (fd >= 0) close(fd);
+            if (map == MAP_FAILED) throw Error("Couldn't read " + paf_path);
+        }
+        std::vector<uint64_t> offsets;
+        FILE *fp = fopen(sorted_path.c_str(), "w");
+        const bool ok = fp && sorter.gather((const char *)map, size, lines.at, lines.len, fp, offsets);
+        if ((fp && fclose(fp) != 0) || !ok) throw Error("Couldn't write " + sorted_path);
+        const std::string tsv = sorter.tsv(offsets);
+        fp = fopen(tsv_path.c_str(), "w");
+        const bool wrote = fp && fwrite(tsv.data(), 1, tsv.size(), fp) == tsv.size();
+        if ((fp && fclose(fp) != 0) || !wrote) throw Error("Couldn't write " + tsv_path);
+    } catch (...) {
+        if (map != MAP_FAILED) munmap(map, size);
+        for (const std::string *f : {&paf_path, &sorted_path, &tsv_path}) remove(f->c_str());
+        throw;
+    }
+    if (map != MAP_FAILED) munmap(map, size);
+    puts(sorter.log_line().c_str());
+}
+
 // One run of the reference's flow (src/closures.rs:22-212): index the reference, map the reads, write <prefix>.paf in input
 // order.  second_fa != "": the reads left unmapped also go to that FASTA file (for the second pass).
 static int run_pass(const Opt &o, const Params &P, const std::string &reads_path, bool reads_fasta, bool ref_fasta, const std::string &prefix,
@@ -787,11 +823,22 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
             throw;
         }
     }
+    std::unique_ptr<ReadOnlyIndex::Sorter> sorter;  // --sort: one per pass, on the pass's primary index (it goes before the index does)
+    SortLines sort_lines;
+    if (o.sort) {
+        try {
+            sorter.reset(new ReadOnlyIndex::Sorter(*ro[0], (uint32_t)o.sort_min_mapq));
+            sort_lines.sorter = sorter->handle();
+        } catch (...) {
+            out.discard_paf();
+            throw;
+        }
+    }
 
     t0 = Clock::now();
     if (P.use_pfx && !ends_with(reads_path, ".gz") && !ends_with(reads_path, ".lz4")) puts("Warning: using experimental rust-parallelfastx (exciting!)");
     start_feed();
-    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density, out.chn, g_depth ? g_depth->handle() : nullptr});
+    MapPipeline pipeline(feed, slots.of, *ro[0], out.paf, out.unm, out.ufa, MapPipeline::Config{rt.n_format, rt.fx_format, g_knobs.fail_at, out.anc, P.density, out.chn, g_depth ? g_depth->handle() : nullptr, sorter ? &sort_lines : nullptr});
     try {
         pipeline.run();
     } catch (...) {
@@ -806,6 +853,10 @@ static int run_pass(const Opt &o, const Params &P, const std::string &reads_path
         } else {
             g_depth->detach();  // this pass's index goes; the accumulator and the names stay for the second pass
         }
+    }
+    if (sorter) {
+        write_sorted(*sorter, sort_lines, prefix);
+        sorter.reset();
     }
     if (g_knobs.timing) pipeline.report(secs(t0));
     printf("Mapped query sequences in %s.\n", rust_duration(secs(t0)).c_str());  // src/closures.rs:211
@@ -840,6 +891,11 @@ int main(int argc, char **argv) {
         else if (a == "--depth-min-mapq") {
             o.depth_min_mapq = atol(val());
             if (o.depth_min_mapq < 0 || o.depth_min_mapq > 0xFFFFFFFFl) { fprintf(stderr, "error: --depth-min-mapq wants a 32-bit value\n"); return 2; }
+        }
+        else if (a == "--sort") o.sort = true;
+        else if (a == "--sort-min-mapq") {
+            o.sort_min_mapq = atol(val());
+            if (o.sort_min_mapq < 0 || o.sort_min_mapq > 0xFFFFFFFFl) { fprintf(stderr, "error: --sort-min-mapq wants a 32-bit value\n"); return 2; }
         }
         else if (a == "--anchors") o.anchors = true;
         else if (a == "--chains") o.chains = true;

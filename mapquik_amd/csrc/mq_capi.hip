@@ -44,6 +44,7 @@ using namespace mq;
 #include "mq_build_kernels.hpp"  // index build, on-disk form, lookup
 #include "mq_cover_kernels.hpp"  // index coverage: bitmap of covered bases, intervals
 #include "mq_depth_kernels.hpp"  // mapping depth: per-window accumulators fed from finished hits
+#include "mq_sort_kernels.hpp"   // coordinate order of finished hits: a stable LSD radix sort
 #include "mq_host_buf.hpp"       // error text, owning buffers and handles, the guard of the extern "C" boundary
 #include "mq_host_state.hpp"     // mq_index, mq_ctx, the map kernels' table, geometry, scratch
 #include "mq_capi_index.hpp"     // mq_index_new .. mq_index_finalize
@@ -51,5 +52,6 @@ using namespace mq;
 #include "mq_capi_index_io.hpp"  // save / load / clone / merge
 #include "mq_capi_cover.hpp"     // mq_index_coverage
 #include "mq_capi_depth.hpp"     // mq_depth_*
+#include "mq_capi_sort.hpp"      // mq_sort_*
 #include "mq_capi_map.hpp"       // contexts, map entry points, FASTA chunks, PAF, host memory
 #include "mq_capi_diag.hpp"      // include/mapquik_hip_diag.h

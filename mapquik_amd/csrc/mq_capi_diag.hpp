@@ -288,4 +288,19 @@ int mqdiag_depth_result_ms(mq_depth *d, float *ms) {
     return MQ_OK;
 }
 
+uint64_t mqdiag_sort_tile_records(void) { return MQ_SORT_TILE; }
+// the digits the sorter's last mq_sort_result sorted (of 11), and that result's device time between two events on its stream
+int mqdiag_sort_passes(mq_sorter *s, uint32_t *passes) {
+    if (!s || !passes) return set_err(MQ_EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *passes = s->passes;
+    return MQ_OK;
+}
+int mqdiag_sort_result_ms(mq_sorter *s, float *ms) {
+    if (!s || !ms) return set_err(MQ_EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lk(s->mu);
+    *ms = s->result_ms;
+    return MQ_OK;
+}
+
 }  // extern "C"

@@ -400,6 +400,36 @@ struct mq_depth {
     std::vector<uint32_t> h_starts;
 };
 
+// mq_sorter (mq_sort_kernels.hpp, mq_capi_sort.hpp): the coordinate order of the hits offered to it.  Its own object beside the index, as
+// mq_depth: a snapshot of the reference ids (dense lengths) and the index's device.  The kept records always lie in key / ord, `capacity`
+// elements each; key2 / ord2 / counts are the result pass's and come with the first mq_sort_result (a pass sorts from one set into the
+// other, and the sets are swapped behind every pass, so the records are in key / ord again).  mq_sort_add_device only points a launch's
+// arguments here.  (Members go last to first, as mq_depth's.)
+struct mq_sorter {
+    std::mutex mu;  // every entry point locks the sorter
+    int device = 0;
+    uint32_t min_mapq = 0, n_ids = 0;
+    uint64_t capacity = 0;                     // records key / ord hold: counted in OFFERED hits
+    uint64_t offered = 0;                      // hits offered since creation or the last clear (< 2^32 - 1)
+    uint32_t passes = 0;                       // digits the last result sorted (mqdiag_sort_passes)
+    std::vector<uint32_t> ref_ids;             // the existing references, ascending
+    ScopedStream stream;                       // the host route's launches and the result pass
+    ScopedEvent e0, e1;                        // around the result pass (mqdiag_sort_result_ms)
+    float result_ms = 0;
+    Buf<uint64_t> lens;                        // dense by reference id: the snapshot's lengths
+    Buf<uint32_t> ids;                         // ref_ids on the device
+    Buf<unsigned long long> acc;               // SORT_ACC_WORDS: the append cursor (= kept) and three tallies
+    Buf<unsigned long long> key, key2;         // ref_id << 32 | r_start
+    Buf<uint32_t> ord, ord2;                   // the ordinals beside them
+    Buf<uint32_t> counts, totals;              // [256][tiles of capacity] per-tile digit counts / their row prefixes; the 256 row sums
+    Buf<unsigned long long> hist;              // 11 x 256: the digit histograms
+    Buf<unsigned long long> ref_out;           // first, count per existing reference
+    Buf<mq_hit> stage;                         // mq_sort_add's hits on their way in (grows)
+    std::vector<uint32_t> h_order;             // the caller's copies of the last result
+    std::vector<mq_sort_ref> h_refs;
+    mq_sort_totals h_totals = {};
+};
+
 struct mq_index {
     mq_params params;
     DevParams dp;
